@@ -1,11 +1,14 @@
 """Benchmark of the 12.5 Hz full-duplex frame step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload duplex|mimi|lm] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload duplex|mimi|lm] [--batch B] [--full] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch of synthetic input: B concurrent sessions each advance by
 one 80 ms frame (Mimi encode -> LMGen.step -> Mimi decode).  `value` = frames/s summed over all ranks; sessions
 shard data-parallel (one process per GPU, no data-path collective), so scaling is weak.
-Prints ONE JSON line on rank 0 (contract in the task statement) incl. the `roofline` and `cpu_baseline` objects.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline; `--full` adds
+the figures that take passes of their own: p50 / p95 latency, the `roofline` object, the extras of the default
+configuration (`kv_depth_start`, `full_context`, `c3`, `c5`, `c2`) and the `cpu_baseline` leg.
+`--dump-outputs DIR` writes what the last timed step returned (rank 0) as DIR/<name>.npy, float32 or float64.
 """
 from __future__ import annotations
 
@@ -61,7 +64,36 @@ def parse():
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the extra figures of the default line: `full_context` (every session 3000 positions deep), `c3` (one session), `c5` (64 sessions, int8 x int8) and `c2` (the codec alone, 8 streams)")
     ap.add_argument("--no-pin", action="store_true", help="do not pin the rank's host thread to its own block of cores")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes passes of its own: p50 / p95 latency, the roofline (dominant kernel, "
+                         "sites, whole step), the extras (unless --no-extras) and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the arrays the last timed step returned (rank 0's) as DIR/<name>.npy (float32, or float64 for tokens)")
     return ap.parse_args()
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """What a caller of the timed path received from its last step, as DIR/<name>.npy: floats as float32, integers (tokens) as
+    float64 (exact).  Above 64 MB in all, every array is cut to the same share of its elements by a fixed, seeded sample."""
+    d = Path(d)
+    d.mkdir(parents=True, exist_ok=True)
+    arrs = {}
+    for name, x in arrays.items():
+        if x is None:
+            continue
+        x = x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+        arrs[name] = x.astype(np.float64 if x.dtype.kind in "iub" or x.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in arrs.values())
+    for name, a in arrs.items():
+        if total > DUMP_CAP_BYTES:
+            k = max(1, int(a.size * DUMP_CAP_BYTES / total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(d / f"{name}.npy", a)
+    return sorted(arrs)
 
 
 def pin_host_thread(rank, world):
@@ -250,14 +282,15 @@ def served_main(args, rank, world, dist, dev, mimi, mcfg, B):
     rng = np.random.default_rng(1000 + rank)
     frames = (0.1 * rng.standard_normal((B, mcfg.frame_size))).astype(np.float32)
     chans = [batcher.open() for _ in range(B)]
+    popped = []
 
     def step():
         for i, ch in enumerate(chans):
             batcher.push(ch, frames[i])
         n = batcher.step()
         assert n == B
-        got = sum(batcher.pop(ch) is not None for ch in chans)
-        return got
+        popped[:] = [batcher.pop(ch) for ch in chans]
+        return sum(p is not None for p in popped)
     for _ in range(args.warmup):
         step()
     if dist is not None:
@@ -269,6 +302,10 @@ def served_main(args, rank, world, dist, dev, mimi, mcfg, B):
         played += step()
     torch.cuda.synchronize(dev)
     dt = job_time(time.perf_counter() - t0, dist, dev)
+    if args.dump_outputs and rank == 0:
+        got = [p for p in popped if p is not None]
+        dump_outputs(args.dump_outputs, {"pcm": np.stack([p[0] for p in got]) if got else None,
+                                         "tokens": np.stack([p[1] for p in got]) if got else None})
     if dist is not None:
         dist.barrier()
     st = batcher.stats()
@@ -414,9 +451,10 @@ def main():
         step()
     sync()
     trace("warm")
+    last = None
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     join()
     torch.cuda.synchronize(dev)
     dt_local = time.perf_counter() - t0
@@ -430,6 +468,11 @@ def main():
     ms = 1e3 * dt / args.steps
     value = job_value(world, B, args.steps, dt)
     trace("timed region done")
+    if args.dump_outputs and rank == 0:
+        # duplex / mimi: the decoded PCM [B, 1, frame_size]; lm: the tokens [B, 1 + dep_q, 1] LMGen.step returned
+        if last is None:
+            sys.stderr.write("bench.py: the last timed step returned nothing (inside the LM's delay): no outputs written\n")
+        dump_outputs(args.dump_outputs, {("tokens" if workload == "lm" else "pcm"): last})
     if args.launch_lists and rank == 0:
         d = Path(args.launch_lists)
         d.mkdir(parents=True, exist_ok=True)
@@ -441,40 +484,44 @@ def main():
         for k, v in lists.items():
             (d / f"launch_list_{k}.tsv").write_text("".join("\t".join(str(x) for x in row) + "\n" for row in v))
 
-    # p50 / p95 latency of a single step (BASELINE.json's second figure): a separate, untimed-for-`value` pass with a
-    # device event before and after every step and no host synchronisation inside the loop.  Pipelined: every frame completes
-    # before the next is submitted, so the figure is PCM-in -> PCM-out of ONE frame with nothing else in flight (what a
-    # session waits for), not the steady-state step interval `ms_per_step` reports.
-    n_lat = max(8, min(args.steps, 40))
-    join()
-    torch.cuda.synchronize(dev)
-    if dup is not None:
-        # one frame alone through the pipeline: device timestamps from the submit reaching the caller's stream (PCM in) to the end
-        # of the frame's decode (PCM out) - mmi_duplex_get_timeline - with the host waiting for the frame (mmi_duplex_flush)
-        dup.timeline(True)
-        lat = []
-        for _ in range(n_lat):
-            out = step()
-            dup.flush()
-            if out is not None:
-                lat.append(dup.timeline()["decode"][1])
-        dup.timeline(False)
-        lat.sort()
-    else:
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_lat)]
-        for a_ev, b_ev in evs:
-            a_ev.record()
-            step()
-            b_ev.record()
+    # --full only from here on: the figures beyond the headline, each from passes of its own after the timed region
+    latency = {}
+    if args.full:
+        # p50 / p95 latency of a single step (BASELINE.json's second figure): a separate, untimed-for-`value` pass with a
+        # device event before and after every step and no host synchronisation inside the loop.  Pipelined: every frame completes
+        # before the next is submitted, so the figure is PCM-in -> PCM-out of ONE frame with nothing else in flight (what a
+        # session waits for), not the steady-state step interval `ms_per_step` reports.
+        n_lat = max(8, min(args.steps, 40))
+        join()
         torch.cuda.synchronize(dev)
-        lat = sorted(a_ev.elapsed_time(b_ev) for a_ev, b_ev in evs)
-    p50, p95 = lat[len(lat) // 2], lat[min(len(lat) - 1, int(0.95 * len(lat)))]
-    trace("latency pass done")
-    p50, p95, p50_ranks, p95_ranks = job_latency(p50, p95, dist, dev, world)
+        if dup is not None:
+            # one frame alone through the pipeline: device timestamps from the submit reaching the caller's stream (PCM in) to the end
+            # of the frame's decode (PCM out) - mmi_duplex_get_timeline - with the host waiting for the frame (mmi_duplex_flush)
+            dup.timeline(True)
+            lat = []
+            for _ in range(n_lat):
+                out = step()
+                dup.flush()
+                if out is not None:
+                    lat.append(dup.timeline()["decode"][1])
+            dup.timeline(False)
+            lat.sort()
+        else:
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_lat)]
+            for a_ev, b_ev in evs:
+                a_ev.record()
+                step()
+                b_ev.record()
+            torch.cuda.synchronize(dev)
+            lat = sorted(a_ev.elapsed_time(b_ev) for a_ev, b_ev in evs)
+        p50, p95 = lat[len(lat) // 2], lat[min(len(lat) - 1, int(0.95 * len(lat)))]
+        trace("latency pass done")
+        p50, p95, p50_ranks, p95_ranks = job_latency(p50, p95, dist, dev, world)
+        latency = {"p50_ms_per_step": p50, "p95_ms_per_step": p95, "p50_ms_per_rank": p50_ranks, "p95_ms_per_rank": p95_ranks}
     out = {
         "metric": "12.5 Hz frames/s end-to-end Mimi+Moshi-7B" if workload == "duplex" else f"12.5 Hz frames/s ({workload} only)",
         "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms, "p50_ms_per_step": p50, "p95_ms_per_step": p95, "p50_ms_per_rank": p50_ranks, "p95_ms_per_rank": p95_ranks,
+        "ms_per_step": ms, **latency,
         "ms_per_step_per_rank": ms_ranks, "load_s": load_s, "load_s_per_rank": load_ranks, "ranks": ranks_info,
         "host_affinity": {"cores_per_rank": None if not cores else len(cores), "first_core_per_rank": [int(c) for c in first_core],
                           "note": "each rank's main thread (the duplex pipeline's host-kept gate) and the HIP runtime threads it starts are "
@@ -504,7 +551,7 @@ def main():
                    "kv_positions_at_start": ([base_depth[0], base_depth[-1]] if lm_gen is not None else None),
                    "kv_positions_at_end": ([base_depth[b] + args.warmup + args.steps for b in (0, B - 1)] if lm_gen is not None else None)},
     }
-    if rank == 0:
+    if rank == 0 and args.full:
         if workload == "mimi":
             frames = args.warmup + args.steps
             nbytes = mimi_algorithmic_bytes(mcfg, B, frames)
@@ -561,6 +608,7 @@ def main():
                 from bench_lm import cpu_baseline_duplex
                 base = cpu_baseline_duplex(base, args, dev=dev)
             out["cpu_baseline"] = base
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

@@ -231,7 +231,7 @@ def extra_c5(args):
     import sys
     out = {}
     for key, kv in (("fp8_ring", "fp8"), ("bf16_ring", "bf16")):
-        cmd = [sys.executable, str(Path(__file__).resolve().parent / "bench.py"), "--no-cpu-baseline", "--no-extras", "--batch", "64",
+        cmd = [sys.executable, str(Path(__file__).resolve().parent / "bench.py"), "--full", "--no-cpu-baseline", "--no-extras", "--batch", "64",
                "--quant", "q8", "--kv", kv, "--steps", str(min(args.steps, 40)), "--warmup", str(min(args.warmup, 8))]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
@@ -252,7 +252,7 @@ def extra_c2(args):
     this very benchmark with `--workload mimi --batch 8` (fp32 codec, the reference's own width - what keeps the codes bit-exact)."""
     import subprocess
     import sys
-    cmd = [sys.executable, str(Path(__file__).resolve().parent / "bench.py"), "--no-cpu-baseline", "--no-extras", "--workload", "mimi", "--batch", "8",
+    cmd = [sys.executable, str(Path(__file__).resolve().parent / "bench.py"), "--full", "--no-cpu-baseline", "--no-extras", "--workload", "mimi", "--batch", "8",
            "--steps", str(max(args.steps, 60)), "--warmup", str(max(args.warmup, 12))]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)

@@ -8,7 +8,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out
 line() { grep '"metric"' $1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('ms/step %.3f p50 %.3f frames/s %.0f' % (d['ms_per_step'], d['p50_ms_per_step'], d['value']))"; }
 run() {   # name, env..., -- bench args
   name=$1; shift
-  ( env "$@" timeout 300 python bench.py --no-cpu-baseline --no-extras $BARGS ) > $O/ab_$name.log 2>&1
+  ( env "$@" timeout 300 python bench.py --full --no-cpu-baseline --no-extras $BARGS ) > $O/ab_$name.log 2>&1
   echo "$name: $(line $O/ab_$name.log)" | tee -a $O/ab_lines.txt
 }
 rm -f $O/ab_lines.txt
@@ -30,9 +30,9 @@ run c3_new X=1
 # per-site kernel time, serial schedule, new default and round 5's plan
 prof() {
   name=$1; shift
-  cd /tmp && env "$@" timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -o duplex -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-extras --serial --launch-lists $O/launch_lists_$name > $O/rocprof_$name.log 2>&1
+  cd /tmp && env "$@" timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_$name -o duplex -- python "$OLDPWD"/bench.py --full --no-cpu-baseline --no-extras --serial --launch-lists $O/launch_lists_$name > $O/rocprof_$name.log 2>&1
   cd $GRAFT_REPO_ROOT
-  python scripts/rocpd_stats.py /tmp/prof_$name/duplex_results.db --header "rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --no-extras --serial ($name)" > $O/duplex_b32_serial_${name}_kernel_stats.csv
+  python scripts/rocpd_stats.py /tmp/prof_$name/duplex_results.db --header "rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --no-extras --serial ($name)" > $O/duplex_b32_serial_${name}_kernel_stats.csv
   python scripts/rocpd_sites.py /tmp/prof_$name/duplex_results.db $O/launch_lists_$name --header "per-site kernel time, serial schedule, 32 sessions ($name)" > $O/duplex_b32_serial_${name}_sites.csv
   grep "^lm" $O/duplex_b32_serial_${name}_sites.csv | cut -c1-120
 }

@@ -7,7 +7,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out
 line() { grep '"metric"' $1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('ms/step %.3f p50 %.3f frames/s %.0f' % (d['ms_per_step'], d['p50_ms_per_step'], d['value']))"; }
 run() {
   name=$1; shift
-  ( env "$@" timeout 300 python bench.py --no-cpu-baseline --no-extras $BARGS ) > $O/ab_$name.log 2>&1
+  ( env "$@" timeout 300 python bench.py --full --no-cpu-baseline --no-extras $BARGS ) > $O/ab_$name.log 2>&1
   echo "$name: $(line $O/ab_$name.log)" | tee -a $O/ab_lines_b.txt
 }
 rm -f $O/ab_lines_b.txt

@@ -4,7 +4,7 @@ mkdir -p gpurun_out
 O=$GRAFT_REPO_ROOT/gpurun_out
 rm -f $O/k_*.log $O/k_lines.txt
 line() { grep '"metric"' $1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('ms/step %.3f p50 %.3f value %.0f' % (d['ms_per_step'], d['p50_ms_per_step'], d['value']))"; }
-run() { name=$1; shift; ( env "$@" timeout 300 python bench.py --no-cpu-baseline --no-extras $BARGS ) > $O/k_$name.log 2>&1; echo "$name: $(line $O/k_$name.log)" | tee -a $O/k_lines.txt; }
+run() { name=$1; shift; ( env "$@" timeout 300 python bench.py --full --no-cpu-baseline --no-extras $BARGS ) > $O/k_$name.log 2>&1; echo "$name: $(line $O/k_$name.log)" | tee -a $O/k_lines.txt; }
 BARGS=""
 run default_1 X=1
 run dev_kernarg_1 HIP_FORCE_DEV_KERNARG=1

@@ -8,12 +8,12 @@
 cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out; export TMPDIR=/tmp; O=$GRAFT_REPO_ROOT/gpurun_out
 run() {   # name, counters, bench args...
   local name=$1 ctrs=$2; shift 2
-  ( cd /tmp && MMI_NO_GRAPH=1 timeout 200 rocprofv3 --pmc $ctrs --kernel-trace -d /tmp/pmc_$name -o pmc -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --no-extras --workload lm --steps 2 --warmup 1 "$@" > $O/pmc_$name.log 2>&1 ); echo "$name rc=$?"
+  ( cd /tmp && MMI_NO_GRAPH=1 timeout 200 rocprofv3 --pmc $ctrs --kernel-trace -d /tmp/pmc_$name -o pmc -- python "$OLDPWD"/bench.py --full --no-cpu-baseline --no-extras --workload lm --steps 2 --warmup 1 "$@" > $O/pmc_$name.log 2>&1 ); echo "$name rc=$?"
 }
 post() {  # name, header, clusters-substring, extra flags
   PMC_ROWS=60 python scripts/rocpd_pmc.py /tmp/pmc_$1/pmc_results.db --header "$2" --clusters "$3" $4 > $O/r05_pmc_$1.csv 2>&1
 }
-HDR="MMI_NO_GRAPH=1 python bench.py --no-cpu-baseline --no-extras --workload lm --steps 2 --warmup 1"
+HDR="MMI_NO_GRAPH=1 python bench.py --full --no-cpu-baseline --no-extras --workload lm --steps 2 --warmup 1"
 for ctr in FETCH_SIZE WRITE_SIZE; do
   run b32_$ctr $ctr --batch 32
   post b32_$ctr "rocprofv3 --pmc $ctr --kernel-trace -- $HDR --batch 32 (bf16, mid-run ring depth 250 + 8 b)" "k_" ""

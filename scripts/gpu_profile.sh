@@ -6,13 +6,13 @@ cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out
-cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_serial -o duplex -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --serial --launch-lists $O/launch_lists > $O/rocprof_serial.log 2>&1
+cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_serial -o duplex -- python "$OLDPWD"/bench.py --full --no-cpu-baseline --serial --launch-lists $O/launch_lists > $O/rocprof_serial.log 2>&1
 cd $GRAFT_REPO_ROOT
-python scripts/rocpd_stats.py /tmp/prof_serial/duplex_results.db --header "rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline --serial   (duplex, 32 sessions, one stream)" > $O/duplex_b32_serial_kernel_stats.csv
+python scripts/rocpd_stats.py /tmp/prof_serial/duplex_results.db --header "rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline --serial   (duplex, 32 sessions, one stream)" > $O/duplex_b32_serial_kernel_stats.csv
 python scripts/rocpd_sites.py /tmp/prof_serial/duplex_results.db $O/launch_lists --header "per-site kernel time, serial schedule, 32 sessions" > $O/duplex_b32_serial_sites.csv
-cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_pipe -o duplex -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline --launch-lists $O/launch_lists_pipe > $O/rocprof_pipe.log 2>&1
+cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_pipe -o duplex -- python "$OLDPWD"/bench.py --full --no-cpu-baseline --launch-lists $O/launch_lists_pipe > $O/rocprof_pipe.log 2>&1
 cd $GRAFT_REPO_ROOT
-python scripts/rocpd_stats.py /tmp/prof_pipe/duplex_results.db --header "rocprofv3 --kernel-trace --stats -- python bench.py --no-cpu-baseline   (the default benchmark command: duplex, 32 sessions, three streams)" > $O/duplex_b32_pipelined_kernel_stats.csv
+python scripts/rocpd_stats.py /tmp/prof_pipe/duplex_results.db --header "rocprofv3 --kernel-trace --stats -- python bench.py --full --no-cpu-baseline   (the default benchmark command: duplex, 32 sessions, three streams)" > $O/duplex_b32_pipelined_kernel_stats.csv
 python scripts/rocpd_sites.py /tmp/prof_pipe/duplex_results.db $O/launch_lists_pipe --header "per-site kernel time, pipelined schedule (under the tracer the LM's queue does not overlap the codec's), 32 sessions" > $O/duplex_b32_pipelined_sites.csv
 python scripts/rocpd_overlap.py /tmp/prof_pipe/duplex_results.db 40 | grep "^#" > $O/duplex_b32_pipelined_queues.txt
 timeout 300 python scripts/duplex_timeline.py 2>&1 | grep -v amdgpu.ids > $O/duplex_timeline.txt

@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out
 rm -rf $O/trprof; mkdir -p $O/trprof
-MMI_MIMI_TR=phases timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/trprof -- python bench.py --workload mimi --batch ${1:-8} --steps 30 --warmup 5 --no-cpu-baseline --no-extras > $O/trprof/bench.log 2>&1
+MMI_MIMI_TR=phases timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/trprof -- python bench.py --full --workload mimi --batch ${1:-8} --steps 30 --warmup 5 --no-cpu-baseline --no-extras > $O/trprof/bench.log 2>&1
 python - <<'PY'
 import csv, glob, os, collections
 O = os.environ.get("GRAFT_REPO_ROOT", ".") + "/gpurun_out/trprof"

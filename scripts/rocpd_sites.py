@@ -9,7 +9,7 @@ step issued which kernel (`mmi_lm_launch_list` / `mmi_mimi_launch_list`, one "si
 
 --last N: average the LAST N steps of the trace instead of its last half.  bench.py moves the sessions to their mid-run ring depth
 only after the staggered start (248 steps at 32 sessions), so "the last half" of a default run still holds shallow, partly masked
-steps; the steps after the seek are warm-up + timed + latency + profile passes (>= 120 with the default flags).
+steps; the steps after the seek are warm-up + timed + latency + profile passes (>= 120 with `--full` and the default flags).
 
 Columns: program, site, launches per step, mean us per step, mean us per launch, algorithmic MB per launch (the packed weight
 bytes the engine recorded for the launch - third column of the launch list, right for bf16, int8 and fp8 weights alike; the

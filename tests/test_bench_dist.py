@@ -116,3 +116,38 @@ def test_bench_rejects_rank_count_mismatch():
     r = _run_bench(["--gpus", "4", "--workload", "launchcheck"],
                    {"MMI_BENCH_BACKEND": "gloo", "RANK": "0", "LOCAL_RANK": "0", "WORLD_SIZE": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29617"})
     assert r.returncode != 0 and "rank(s)" in (r.stderr + r.stdout)
+
+
+def test_bench_plain_run_by_default_and_dump_outputs_option(monkeypatch):
+    """`--full` (the passes beyond the headline) is off unless asked for; `--dump-outputs DIR` names the directory."""
+    sys.path.insert(0, str(ROOT))
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, "", 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+
+
+def test_dump_outputs_dtypes_and_size_cap(tmp_path, monkeypatch):
+    """Floats are written as float32, tokens as float64 (exact); above the cap every array becomes the same fixed, seeded sample."""
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import bench
+    g = torch.Generator().manual_seed(0)
+    pcm = torch.randn(3, 1, 40, generator=g)
+    tok = torch.randint(-2, 2048, (3, 9, 1), generator=g)
+    assert bench.dump_outputs(tmp_path / "a", {"pcm": pcm, "tokens": tok, "absent": None}) == ["pcm", "tokens"]
+    p, t = np.load(tmp_path / "a" / "pcm.npy"), np.load(tmp_path / "a" / "tokens.npy")
+    assert p.dtype == np.float32 and np.array_equal(p, pcm.numpy())
+    assert t.dtype == np.float64 and np.array_equal(t, tok.numpy().astype(np.float64))
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 256)
+    for d in ("b", "c"):
+        bench.dump_outputs(tmp_path / d, {"pcm": pcm, "tokens": tok})
+    sizes = [(tmp_path / "b" / f"{n}.npy") for n in ("pcm", "tokens")]
+    assert sum(np.load(f).nbytes for f in sizes) <= 256
+    for n in ("pcm", "tokens"):
+        b, c = np.load(tmp_path / "b" / f"{n}.npy"), np.load(tmp_path / "c" / f"{n}.npy")
+        assert b.size > 0 and np.array_equal(b, c)
+        assert np.isin(b, np.load(tmp_path / "a" / f"{n}.npy").reshape(-1)).all()
