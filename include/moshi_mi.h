@@ -206,6 +206,32 @@ typedef struct mmi_lm mmi_lm;
  * stay bf16.  The linears must be all bf16, all int8 or all fp8. */
 int mmi_lm_create(const mmi_lm_cfg* cfg, const mmi_tensor_desc* weights, int32_t n_weights,
                   int32_t max_batch, mmi_lm** out);
+
+/* Options of the TTS-family LMs (kyutai's TTS checkpoints), next to mmi_lm_cfg so that its layout stays that of ABI version 3.
+ * All zero = the model mmi_lm_create builds. */
+struct mmi_lm_cfg_ext {
+    /* depformer_weights_per_step_schedule (models/lm.py:125-127, 174-179; modules/transformer.py:291-318, 395-401, 684-688):
+     * micro-step k runs the depformer weight set schedule[k] - `depformer_in.{w}`, `depformer.layers.*.self_attn.{in,out}_projs.{w}`
+     * and `depformer.layers.*.gating.{w}` exist for w = 0..max(schedule) (values without gaps), `linears.{k}` for every k.
+     * depformer_schedule_len: 0 = none (one set per step), else dep_q. */
+    int32_t depformer_schedule[64];
+    int32_t depformer_schedule_len;
+    /* depformer_low_rank_embeddings (models/lm.py:180; models/lm_utils.py:80-94, 117-124): `depformer_emb.{k}.weight` [card+1, r]
+     * and `depformer_text_emb.weight` [text_card+1, r], each followed by `<name>.low_rank.weight` [depformer_dim, r].  The
+     * tables are expanded once at create, bf16(E @ low_rank^T) with fp32 sums, and gathered like full-rank ones.  0 = none. */
+    int32_t depformer_low_rank;
+    /* demux_second_text_stream (models/lm.py:135-139, 190-194; models/lm_utils.py:95-116; models/loaders.py:395-396): a text token
+     * t is the pair (t % (text_card+1), t / (text_card+1) - 1) and embeds as bf16(out1(E[first]) + (second >= 0 ? out2(E[second]) : 0))
+     * for `text_emb` ([dim, dim] `out1` / `out2`) and `depformer_text_emb` ([depformer_dim, r or depformer_dim]); out1(E) and out2(E)
+     * are expanded once at create.  Needs depformer_dim to be a multiple of the 16- / 32-row tile. */
+    int32_t demux_second_text_stream;
+};
+typedef struct mmi_lm_cfg_ext mmi_lm_cfg_ext;
+
+/* mmi_lm_create with the options above; ext == NULL is mmi_lm_create.  Linears must be bf16 when low-rank or demuxed embeddings
+ * are used.  dep_q up to 32, n_q == dep_q allowed (no user audio stream: mmi_lm_step takes n_user = 0). */
+int mmi_lm_create_ext(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ext, const mmi_tensor_desc* weights, int32_t n_weights,
+                      int32_t max_batch, mmi_lm** out);
 void mmi_lm_destroy(mmi_lm* lm);
 
 /* LMGen.streaming(batch) enter/exit (lm.py:605-666). */

@@ -51,6 +51,12 @@ class LMCfg(C.Structure):
                 ("cross_attention", C.c_int32)]
 
 
+class LMCfgExt(C.Structure):
+    """struct mmi_lm_cfg_ext: the TTS-family options of mmi_lm_create_ext."""
+    _fields_ = [("depformer_schedule", C.c_int32 * 64), ("depformer_schedule_len", C.c_int32), ("depformer_low_rank", C.c_int32),
+                ("demux_second_text_stream", C.c_int32)]
+
+
 class Sampling(C.Structure):
     _fields_ = [("use_sampling", C.c_int32), ("temp", C.c_float), ("temp_text", C.c_float), ("top_k", C.c_int32),
                 ("top_k_text", C.c_int32), ("seed", C.c_uint64)]
@@ -112,6 +118,7 @@ SIGNATURES = {
     "mmi_duplex_get_timeline": (C.c_int, [_P, _P]),
     "mmi_duplex_get_stamps": (C.c_int, [_P, _P, _P]),
     "mmi_lm_create": (C.c_int, [C.POINTER(LMCfg), C.POINTER(TensorDesc), C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "mmi_lm_create_ext": (C.c_int, [C.POINTER(LMCfg), C.POINTER(LMCfgExt), C.POINTER(TensorDesc), C.c_int32, C.c_int32, C.POINTER(_P)]),
     "mmi_lm_destroy": (None, [_P]),
     "mmi_lm_streaming_start": (C.c_int, [_P, C.c_int32, C.POINTER(Sampling), _P]),
     "mmi_lm_streaming_start_guided": (C.c_int, [_P, C.c_int32, C.POINTER(Sampling), C.POINTER(Guidance), _P]),

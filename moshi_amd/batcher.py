@@ -26,6 +26,13 @@ from .lm import LMModel
 from .mimi import MimiModel
 
 
+def _require_duplex_model(cfg, who: str) -> None:
+    """Both serving pipelines feed the user's encoded speech in as the n_q - dep_q user codebooks of a duplex model."""
+    if cfg.n_q == cfg.dep_q or cfg.demux_second_text_stream:
+        raise NotImplementedError(f"{who} serves duplex models (user audio in, n_q > dep_q); a TTS-family model (no user stream "
+                                  "or a demuxed text stream) is stepped with LMGen directly")
+
+
 class SessionBatcher:
     def __init__(self, mimi: MimiModel, lm_model: LMModel, slots: int, use_sampling: bool = True, temp: float = 0.8,
                  temp_text: float = 0.7, top_k: int = 250, top_k_text: int = 25, seed: int = 0,
@@ -33,6 +40,7 @@ class SessionBatcher:
                  cfg_is_no_text: bool = False, cfg_is_masked_until=None, condition_tensors=None):
         assert mimi._lib is lm_model._lib, "both models must live in the same engine library"
         assert not mimi.is_streaming, "the batcher puts the models into streaming mode itself"
+        _require_duplex_model(lm_model.config, "SessionBatcher")
         self.mimi, self.lm_model = mimi, lm_model
         self._lib = mimi._lib
         self.frame_size = mimi.frame_size

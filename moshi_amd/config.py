@@ -8,7 +8,7 @@ architecture are used by the tests (oracle-sized).
 from __future__ import annotations
 
 from dataclasses import dataclass, field
-from typing import List
+from typing import List, Optional
 
 
 @dataclass
@@ -114,6 +114,12 @@ class LMConfig:
     extra_heads_dim: int = 6
     kv_cache_dtype: str = "bf16"        # "fp8": e4m3 ring for the temporal transformer's keys / values (engine option)
     cross_attention: bool = False       # every temporal layer attends to the fuser's `cross` condition (transformer.py:727-731, 779-786)
+    # TTS family (lm.py:58-127, 174-208; lm_utils.py:66-124): micro-step k runs depformer weight set schedule[k] (dep_q entries,
+    # values 0..max without gaps); low-rank depformer embeddings of this rank (a multiple of 8) + a `low_rank` linear; text tokens
+    # that mux two streams, (second + 1) * (text_card + 1) + first, embedded through `out1` / `out2`
+    depformer_weights_per_step_schedule: Optional[List[int]] = None
+    depformer_low_rank_embeddings: Optional[int] = None
+    demux_second_text_stream: bool = False
 
     @staticmethod
     def _gating_hidden(dim: int, dim_feedforward: int) -> int:
@@ -129,6 +135,12 @@ class LMConfig:
     @property
     def depformer_ffn_hidden(self) -> int:
         return self._gating_hidden(self.depformer_dim, self.depformer_dim_feedforward)
+
+    @property
+    def depformer_num_weights(self) -> int:
+        """Weight sets of the depformer: max(schedule) + 1 with a schedule, else one per micro-step (transformer.py:395-401)."""
+        s = self.depformer_weights_per_step_schedule
+        return max(s) + 1 if s else self.dep_q
 
     @property
     def num_codebooks(self) -> int:
@@ -155,6 +167,11 @@ class LMConfig:
             **({"extra_heads_num_heads": self.extra_heads_num_heads, "extra_heads_dim": self.extra_heads_dim}
                if self.extra_heads_num_heads else {}),
             **({"cross_attention": True} if self.cross_attention else {}),
+            **({"depformer_weights_per_step_schedule": list(self.depformer_weights_per_step_schedule)}
+               if self.depformer_weights_per_step_schedule is not None else {}),
+            **({"depformer_low_rank_embeddings": self.depformer_low_rank_embeddings}
+               if self.depformer_low_rank_embeddings is not None else {}),
+            **({"demux_second_text_stream": True} if self.demux_second_text_stream else {}),
         }
 
 
@@ -165,6 +182,17 @@ def tiny_stt_config() -> LMConfig:
     return LMConfig(dim=128, num_heads=4, num_layers=2, hidden_scale=4.125, context=12, n_q=8, dep_q=0, card=64, text_card=96,
                     depformer_dim=64, depformer_dim_feedforward=int(4.125 * 64), depformer_num_heads=2, depformer_num_layers=2,
                     delays=[2] + [0] * 8, extra_heads_num_heads=2, extra_heads_dim=6)
+
+
+def tiny_tts_config() -> LMConfig:
+    """A TTS-family model at oracle size (the reference's kyutai/tts-* family, tts.py): every codebook is generated
+    (n_q = dep_q, no user stream) with more micro-steps than Moshi's 16-row depformer attention holds, depformer weights shared
+    by a schedule, low-rank depformer embeddings, a demuxed text stream and cross-attention conditioning."""
+    return LMConfig(dim=128, num_heads=4, num_layers=2, hidden_scale=4.125, context=12, n_q=20, dep_q=20, card=64, text_card=96,
+                    depformer_dim=64, depformer_dim_feedforward=int(4.125 * 64), depformer_num_heads=2, depformer_num_layers=2,
+                    delays=[0, 0] + [1] * 19, cross_attention=True,
+                    depformer_weights_per_step_schedule=list(range(6)) + [6] * 14, depformer_low_rank_embeddings=16,
+                    demux_second_text_stream=True)
 
 
 def tiny_lm_config() -> LMConfig:

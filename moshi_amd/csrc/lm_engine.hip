@@ -65,7 +65,13 @@ struct mmi_lm {
     std::vector<GemmW> dep_in, dep_lin;
     GemmW dep_in_all;               // the dep_q depformer_in linears as one [dep_q * depformer_dim, dim] GEMM
     bool dep_in_grouped = false;
-    std::vector<uint16_t*> dep_emb; // [0] = depformer_text_emb, [k>=1] = depformer_emb[k-1]
+    std::vector<uint16_t*> dep_emb; // [0] = depformer_text_emb, [k>=1] = depformer_emb[k-1] (low-rank ones expanded at create)
+    // mmi_lm_cfg_ext (TTS family): micro-step k runs depformer weight set dep_sched[k] of dep_nw (identity without a schedule);
+    // a demuxed text stream embeds through text_emb | text_emb2 (out1 / out2 of text_emb) and dep_emb[0] | dep_emb2
+    std::vector<int> dep_sched;
+    int dep_nw = 0;
+    bool demux = false;
+    uint16_t *text_emb2 = nullptr, *dep_emb2 = nullptr;
     std::vector<DepLayerW> dep_layers;
     // parity tap (mmi_lm_debug_linear): every packed linear / every norm vector by its state-dict key
     std::map<std::string, GemmW> linear_by_name;
@@ -267,6 +273,23 @@ int load_copy(mmi_lm* lm, const MmiWeights& W, const std::string& name, int ndim
     MMI_HIP_CHECK(hipMemcpy(dst, d->data, n * sizeof(uint16_t), hipMemcpyDeviceToDevice));
     if (out) *out = dst;
     lm->vector_by_name[name] = dst;
+    return MMI_OK;
+}
+
+// `<stem>.weight` [V][R] through the nn.Linear(R, D) `<stem><suffix>` [D][R], expanded once into a full [V][D] bf16 table
+// (k_expand_emb): what a low-rank or demuxed embedding (lm_utils.py:95-124) computes for every token, gathered per step
+int load_expanded(mmi_lm* lm, const MmiWeights& W, const std::string& stem, int V, int R, int D, const char* suffix, uint16_t** out) {
+    const mmi_tensor_desc *e, *w;
+    int rc = need(W, stem + ".weight", 2, &e);
+    if (rc || (rc = need(W, stem + suffix, 2, &w))) return rc;
+    if (e->shape[0] != V || e->shape[1] != R) return mmi_fail(MMI_ERR_SHAPE, "shape mismatch for " + stem + ".weight");
+    if (w->shape[0] != D || w->shape[1] != R) return mmi_fail(MMI_ERR_SHAPE, "shape mismatch for " + stem + suffix);
+    uint16_t* dst = nullptr;
+    MMI_HIP_CHECK(lm->wts.alloc(&dst, (size_t)V * D));
+    MMI_LAUNCH(k_expand_emb, dim3(mmi_cdiv(D, 256), V), 256, 0, (hipStream_t)0, (const uint16_t*)e->data, R, (const uint16_t*)w->data, D, dst);
+    MMI_CHECK_LAUNCH();
+    *out = dst;
+    lm->vector_by_name[stem + suffix] = dst;
     return MMI_OK;
 }
 
@@ -792,7 +815,7 @@ void add_sample(mmi_lm* lm, uint16_t* logits, int ld, int V, bool text, int site
     sa.nx_dup = guided ? lm->gen_batch : 0;
     if (next_k >= 0) {
         const int dd = lm->cfg.depformer_dim;
-        sa.nx_pre = lm->dpre + (size_t)next_k * dd; sa.nx_ld = lm->cfg.dep_q * dd;
+        sa.nx_pre = lm->dpre + (size_t)lm->dep_sched[next_k] * dd; sa.nx_ld = lm->dep_nw * dd;
         sa.nx_emb = lm->dep_emb[next_k]; sa.nx_out = lm->dx;
         sa.nx_D = dd; sa.nx_T = lm->Td; sa.nx_ksteps = packed_ksteps_t(lm, lm->Td, dd);
     }
@@ -933,11 +956,14 @@ int build_program(mmi_lm* lm) {
         const bool guided = lm->cfg_coef != 1.f;
         const int* masked_until = lm->masked_until; const int no_text = lm->cfg_no_text; long* offsets_m = lm->offsets_m;
         const uint16_t* cond = lm->cond;
+        const uint16_t* temb2 = lm->demux ? lm->text_emb2 : nullptr; const int text_n = c.text_card + 1;
         P.add([=](hipStream_t s) {
             MMI_LAUNCH(k_lm_prepare, mmi_cdiv(G * NC + G * (Dh / 2), 128), 128, 0, s, t, user, n_user, tokens, rope, Dh, max_period);
             if (guided)
                 MMI_LAUNCH(k_lm_cfg_twins, mmi_cdiv(G * NC + G * Dh + G, 128), 128, 0, s, t, tokens, masked_until, no_text, offsets_m, rope, Dh);
-            MMI_LAUNCH(k_lm_embed, dim3(mmi_cdiv(d, 256), B), 256, 0, s, (const int*)tokens, NC, emb, card1, temb, x, d, T, xks, cond);
+            if (temb2) MMI_LAUNCH(k_lm_embed_demux, dim3(mmi_cdiv(d, 256), B), 256, 0, s, (const int*)tokens, NC, emb, card1, temb, temb2,
+                                  text_n, x, d, T, xks, cond);
+            else MMI_LAUNCH(k_lm_embed, dim3(mmi_cdiv(d, 256), B), 256, 0, s, (const int*)tokens, NC, emb, card1, temb, x, d, T, xks, cond);
             MMI_CHECK_LAUNCH();
             return (int)MMI_OK;
         });
@@ -1050,9 +1076,28 @@ int build_program(mmi_lm* lm) {
     const bool grouped = lm->dep_in_grouped;
     lm->op_depformer = P.ops.size();
     P.site("dep.in_all");
-    if (grouped) add_gemm(lm, lm->dep_in_all, tout_in, lm->dpre, c.dep_q * dd, false, MMI_EPI_STORE, nullptr, nullptr, nullptr, 0, false, nullptr, qt);
+    if (grouped) add_gemm(lm, lm->dep_in_all, tout_in, lm->dpre, lm->dep_nw * dd, false, MMI_EPI_STORE, nullptr, nullptr, nullptr, 0, false, nullptr, qt);
     P.site("text_sample");
-    add_sample(lm, lm->text_logits, c.text_card_out, c.text_card_out, true, 0, lm->text_tok, 1, grouped ? 0 : -1);
+    // a demuxed text stream: the first input row is written by its own launch behind the sampler (and behind an on_text_hook,
+    // which may mux a second token into the one sampled)
+    add_sample(lm, lm->text_logits, c.text_card_out, c.text_card_out, true, 0, lm->text_tok, 1, grouped && !lm->demux ? 0 : -1);
+    if (lm->demux && c.dep_q > 0) {
+        P.site("dep.in_demux");
+        SampleArgs na;
+        memset(&na, 0, sizeof(na));
+        na.nx_pre = lm->dpre + (size_t)lm->dep_sched[0] * dd; na.nx_ld = lm->dep_nw * dd;
+        na.nx_emb = lm->dep_emb[0]; na.nx_out = lm->dx;
+        na.nx_D = dd; na.nx_T = lm->Td; na.nx_ksteps = packed_ksteps_t(lm, lm->Td, dd);
+        na.nx_dup = lm->cfg_coef != 1.f ? lm->gen_batch : 0;
+        na.out_stride = 1;
+        const int G = lm->gen_batch, N = c.text_card + 1;
+        const int* tt = lm->text_tok; const uint16_t* e2 = lm->dep_emb2;
+        P.add([=](hipStream_t s) {
+            MMI_LAUNCH(k_dep_next_input_demux, G, 128, 0, s, na, tt, e2, N);
+            MMI_CHECK_LAUNCH();
+            return (int)MMI_OK;
+        });
+    }
     // ---- depformer: dep_q sequential micro-steps
     const size_t dkv_layer = (size_t)B * Hd * c.dep_q * Dhd;
     for (int k = 0; k < c.dep_q; ++k) {
@@ -1078,11 +1123,13 @@ int build_program(mmi_lm* lm) {
             da.T = lm->Td; da.out_ksteps = packed_ksteps_t(lm, lm->Td, dd);
             P.site("dep.attn");
             const bool attn8 = Dhd % 8 == 0 && c.dep_q <= 8;        // else the general one-wave-per-(session, head) kernel
+            const bool rows32 = c.dep_q > 16;                        // its 32-row form: the TTS family's 17..32 micro-steps
             const bool attn_in_gemm = !skip_attn0 && attn8 && dep_attn_fusable(lm, L.out_proj[k], Hd, Dhd, c.dep_q);
             if (!skip_attn0 && !attn_in_gemm)
             P.add([=](hipStream_t s) {
                 if (attn8) MMI_LAUNCH((k_dep_attn8<4>), mmi_cdiv(B * Hd, 4), 256, 0, s, da);
-                else MMI_LAUNCH(k_dep_attn, B * Hd, 64, 0, s, da);
+                else if (rows32) MMI_LAUNCH((k_dep_attn<32>), B * Hd, 64, 0, s, da);
+                else MMI_LAUNCH((k_dep_attn<16>), B * Hd, 64, 0, s, da);
                 MMI_CHECK_LAUNCH();
                 return (int)MMI_OK;
             });
@@ -1156,7 +1203,7 @@ int check_cfg(const mmi_lm_cfg& c) {
     if (c.kv_cache_dtype == MMI_F8E4M3 && (c.dim / c.num_heads) % 16) return mmi_fail(MMI_ERR_UNSUPPORTED, "fp8 KV needs a head dim multiple of 16");
     if (c.card % 8 || c.text_card_out % 8 || c.card > 32768 || c.text_card_out > 32768)
         return mmi_fail(MMI_ERR_UNSUPPORTED, "vocabulary sizes must be multiples of 8 and at most 32768");
-    if (c.dep_q < 0 || c.dep_q > 16 || c.n_q < c.dep_q || c.n_q + 1 > 64) return mmi_fail(MMI_ERR_UNSUPPORTED, "bad n_q / dep_q");
+    if (c.dep_q < 0 || c.dep_q > 32 || c.n_q < c.dep_q || c.n_q + 1 > 64) return mmi_fail(MMI_ERR_UNSUPPORTED, "bad n_q / dep_q");
     if (c.dim > 8 * 1024 * MMI_NORM_MAXP || c.depformer_dim > 8 * 1024 * MMI_NORM_MAXP)
         return mmi_fail(MMI_ERR_UNSUPPORTED, "model width above the RMSNorm kernel's register budget");
     if (c.dim % 8 || c.depformer_dim % 8 || c.ffn_hidden % 8 || c.depformer_ffn_hidden % 8)
@@ -1204,6 +1251,11 @@ int run_step_with_hooks(mmi_lm* lm, hipStream_t s) {
 // ===============================================================================================
 extern "C" int mmi_lm_create(const mmi_lm_cfg* cfg, const mmi_tensor_desc* weights, int32_t n_weights, int32_t max_batch,
                              mmi_lm** out) {
+    return mmi_lm_create_ext(cfg, nullptr, weights, n_weights, max_batch, out);
+}
+
+extern "C" int mmi_lm_create_ext(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ext, const mmi_tensor_desc* weights, int32_t n_weights,
+                                 int32_t max_batch, mmi_lm** out) {
     if (!cfg || !weights || !out || max_batch <= 0) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_create: bad argument");
     if (max_batch > 64) return mmi_fail(MMI_ERR_UNSUPPORTED, "max_batch > 64 sessions per GPU is not supported yet");
     mmi_lm_cfg norm_cfg = *cfg;
@@ -1213,7 +1265,34 @@ extern "C" int mmi_lm_create(const mmi_lm_cfg* cfg, const mmi_tensor_desc* weigh
     }
     int rc = check_cfg(norm_cfg);
     if (rc) return rc;
+    mmi_lm_cfg_ext x;
+    memset(&x, 0, sizeof(x));
+    if (ext) x = *ext;
+    // depformer weight schedule (lm.py:125-127, transformer.py:395-401): dep_q entries 0..max without gaps
+    std::vector<int> sched(norm_cfg.dep_q);
+    int nw = norm_cfg.dep_q;
+    for (int k = 0; k < norm_cfg.dep_q; ++k) sched[k] = k;
+    if (x.depformer_schedule_len) {
+        if (x.depformer_schedule_len != norm_cfg.dep_q || norm_cfg.dep_q == 0)
+            return mmi_fail(MMI_ERR_INVALID, "depformer_weights_per_step_schedule must have dep_q entries");
+        nw = 0;
+        for (int k = 0; k < norm_cfg.dep_q; ++k) {
+            sched[k] = x.depformer_schedule[k];
+            if (sched[k] < 0 || sched[k] >= norm_cfg.dep_q) return mmi_fail(MMI_ERR_INVALID, "depformer schedule entries must be in [0, dep_q)");
+            nw = sched[k] + 1 > nw ? sched[k] + 1 : nw;
+        }
+        std::vector<char> seen(nw, 0);
+        for (int k = 0; k < norm_cfg.dep_q; ++k) seen[sched[k]] = 1;
+        for (int w = 0; w < nw; ++w)
+            if (!seen[w]) return mmi_fail(MMI_ERR_INVALID, "depformer schedule must use every weight index 0..max (no gaps)");
+    }
+    const int low_rank = x.depformer_low_rank;
+    if (low_rank < 0 || low_rank % 8) return mmi_fail(MMI_ERR_INVALID, "depformer_low_rank_embeddings must be a multiple of 8");
+    const bool demux = x.demux_second_text_stream != 0;
     mmi_lm* lm = new mmi_lm();
+    lm->dep_sched = sched;
+    lm->dep_nw = nw;
+    lm->demux = demux;
     if (hipGetDevice(&lm->device) != hipSuccess) lm->device = -1;
     lm->cfg = norm_cfg;
     lm->max_batch = max_batch;
@@ -1237,11 +1316,29 @@ extern "C" int mmi_lm_create(const mmi_lm_cfg* cfg, const mmi_tensor_desc* weigh
         if (hipSuccess != lm->wts.alloc(&lm->emb, per * c.n_q)) return fail(mmi_fail(MMI_ERR_HIP, "out of device memory"));
         for (int i = 0; i < c.n_q; ++i)
             if ((rc = load_copy(lm, W, "emb." + std::to_string(i) + ".weight", 2, per, nullptr, lm->emb + per * i))) return fail(rc);
-        if ((rc = load_copy(lm, W, "text_emb.weight", 2, (size_t)(c.text_card + 1) * d, &lm->text_emb))) return fail(rc);
+        const int N = c.text_card + 1;
+        if (demux) {
+            if ((rc = load_expanded(lm, W, "text_emb", N, d, d, ".out1.weight", &lm->text_emb))) return fail(rc);
+            if ((rc = load_expanded(lm, W, "text_emb", N, d, d, ".out2.weight", &lm->text_emb2))) return fail(rc);
+        } else if ((rc = load_copy(lm, W, "text_emb.weight", 2, (size_t)N * d, &lm->text_emb))) return fail(rc);
         lm->dep_emb.resize(c.dep_q);
-        if (c.dep_q > 0 && (rc = load_copy(lm, W, "depformer_text_emb.weight", 2, (size_t)(c.text_card + 1) * dd, &lm->dep_emb[0]))) return fail(rc);
-        for (int k = 1; k < c.dep_q; ++k)
-            if ((rc = load_copy(lm, W, "depformer_emb." + std::to_string(k - 1) + ".weight", 2, (size_t)(c.card + 1) * dd, &lm->dep_emb[k]))) return fail(rc);
+        const int r = low_rank ? low_rank : dd;
+        if (c.dep_q > 0) {
+            // lm_utils.py:95-124: a demuxed table goes through out1 / out2 (its `low_rank` linear is not applied), a low-rank one
+            // through `low_rank`
+            if (demux) {
+                if ((rc = load_expanded(lm, W, "depformer_text_emb", N, r, dd, ".out1.weight", &lm->dep_emb[0]))) return fail(rc);
+                if ((rc = load_expanded(lm, W, "depformer_text_emb", N, r, dd, ".out2.weight", &lm->dep_emb2))) return fail(rc);
+            } else if (low_rank) {
+                if ((rc = load_expanded(lm, W, "depformer_text_emb", N, r, dd, ".low_rank.weight", &lm->dep_emb[0]))) return fail(rc);
+            } else if ((rc = load_copy(lm, W, "depformer_text_emb.weight", 2, (size_t)N * dd, &lm->dep_emb[0]))) return fail(rc);
+        }
+        for (int k = 1; k < c.dep_q; ++k) {
+            const std::string name = "depformer_emb." + std::to_string(k - 1);
+            if (low_rank) rc = load_expanded(lm, W, name, c.card + 1, r, dd, ".low_rank.weight", &lm->dep_emb[k]);
+            else rc = load_copy(lm, W, name + ".weight", 2, (size_t)(c.card + 1) * dd, &lm->dep_emb[k]);
+            if (rc) return fail(rc);
+        }
     }
     // temporal transformer (lm.py:146-158)
     lm->layers.resize(c.num_layers);
@@ -1278,7 +1375,7 @@ extern "C" int mmi_lm_create(const mmi_lm_cfg* cfg, const mmi_tensor_desc* weigh
             if ((rc = load_copy(lm, W, "extra_heads." + std::to_string(i) + ".weight", 2, per, nullptr, lm->extra_heads_all + per * i))) return fail(rc);
     }
     // depformer (lm.py:179-232; per-step weights transformer.py:291-318)
-    lm->dep_in.resize(c.dep_q);
+    lm->dep_in.resize(nw);
     lm->dep_lin.resize(c.dep_q);
     {
         // depformer_in[k] all read transformer_out, so they are packed back to back and run as ONE GEMM with
@@ -1290,28 +1387,34 @@ extern "C" int mmi_lm_create(const mmi_lm_cfg* cfg, const mmi_tensor_desc* weigh
         if (group) {
             const int NT = dd / lm->T, ksteps = mmi_cdiv(d, mmi_kstep(lm->T));
             per = lm->q8 >= 1 ? (size_t)NT * mmi_cdiv(ksteps, 2) * 1024 : (size_t)NT * ksteps * 512 * sizeof(uint16_t);
-            if (lm->wts.alloc(&wp_all, per * c.dep_q) != hipSuccess) return fail(mmi_fail(MMI_ERR_HIP, "out of device memory (depformer_in)"));
-            if (lm->q8 >= 1 && lm->wts.alloc(&scale_all, (size_t)dd * c.dep_q) != hipSuccess)
+            if (lm->wts.alloc(&wp_all, per * nw) != hipSuccess) return fail(mmi_fail(MMI_ERR_HIP, "out of device memory (depformer_in)"));
+            if (lm->q8 >= 1 && lm->wts.alloc(&scale_all, (size_t)dd * nw) != hipSuccess)
                 return fail(mmi_fail(MMI_ERR_HIP, "out of device memory (depformer_in scales)"));
-            if (lm->q8 == 1 && lm->wts.alloc(&scb_all, (size_t)dd * c.dep_q) != hipSuccess)
+            if (lm->q8 == 1 && lm->wts.alloc(&scb_all, (size_t)dd * nw) != hipSuccess)
                 return fail(mmi_fail(MMI_ERR_HIP, "out of device memory (depformer_in scales)"));
         }
-        for (int k = 0; k < c.dep_q; ++k) {
+        for (int k = 0; k < nw; ++k) {
             if ((rc = load_linear(lm, W, "depformer_in." + std::to_string(k) + ".weight", dd, d, 0, &lm->dep_in[k],
                                   group ? wp_all + per * k : nullptr, scale_all ? scale_all + (size_t)dd * k : nullptr,
                                   scb_all ? scb_all + (size_t)dd * k : nullptr)))
                 return fail(rc);
         }
-        for (int k = 1; group && k < c.dep_q; ++k)
+        for (int k = 1; group && k < nw; ++k)
             if (lm->dep_in[k].xinv != lm->dep_in[0].xinv)
                 return fail(mmi_fail(MMI_ERR_UNSUPPORTED, "the depformer_in linears read the same tensor and must share one input_scale"));
         if (group) {
             lm->dep_in_all = lm->dep_in[0];
-            lm->dep_in_all.N = dd * c.dep_q;
-            lm->dep_in_all.NT = lm->dep_in[0].NT * c.dep_q;
-            lm->dep_in_all.bytes = lm->dep_in[0].bytes * c.dep_q;
+            lm->dep_in_all.N = dd * nw;
+            lm->dep_in_all.NT = lm->dep_in[0].NT * nw;
+            lm->dep_in_all.bytes = lm->dep_in[0].bytes * nw;
             lm->dep_in_grouped = true;
         }
+        if (demux && c.dep_q > 0 && !group)
+            return fail(mmi_fail(MMI_ERR_UNSUPPORTED, "a demuxed text stream needs depformer_dim to be a multiple of the GEMM tile"));
+        // micro-step k reads weight set sched[k]: the per-step lists alias the nw packed sets (transformer.py:291-318)
+        std::vector<GemmW> per_set = lm->dep_in;
+        lm->dep_in.resize(c.dep_q);
+        for (int k = 0; k < c.dep_q; ++k) lm->dep_in[k] = per_set[sched[k]];
     }
     // the depth transformer's own tile (mmi_lm::Td): two 16-row batch tiles at 17..32 sessions.  Needs the grouped depformer_in
     // (its row-major output is the boundary between the two tiles) and bf16 weights (the int8 / fp8 forms of the 16-row kernels
@@ -1329,16 +1432,25 @@ extern "C" int mmi_lm_create(const mmi_lm_cfg* cfg, const mmi_tensor_desc* weigh
         DepLayerW& L = lm->dep_layers[l];
         std::string p = "depformer.layers." + std::to_string(l);
         L.in_proj.resize(c.dep_q); L.out_proj.resize(c.dep_q); L.ffn_in.resize(c.dep_q); L.ffn_out.resize(c.dep_q);
-        for (int k = 0; k < c.dep_q; ++k) {
+        for (int k = 0; k < nw; ++k) {
             std::string ks = std::to_string(k);
             if ((rc = load_linear(lm, W, p + ".self_attn.in_projs." + ks + ".weight", 3 * dd, dd, 0, &L.in_proj[k], nullptr, nullptr, nullptr, Td))) return fail(rc);
             if ((rc = load_linear(lm, W, p + ".self_attn.out_projs." + ks + ".weight", dd, dd, 0, &L.out_proj[k], nullptr, nullptr, nullptr, Td))) return fail(rc);
             if ((rc = load_linear(lm, W, p + ".gating." + ks + ".linear_in.weight", 2 * c.depformer_ffn_hidden, dd, c.depformer_ffn_hidden, &L.ffn_in[k], nullptr, nullptr, nullptr, Td))) return fail(rc);
             if ((rc = load_linear(lm, W, p + ".gating." + ks + ".linear_out.weight", dd, c.depformer_ffn_hidden, 0, &L.ffn_out[k], nullptr, nullptr, nullptr, Td))) return fail(rc);
         }
+        {   // the sets were loaded at indices 0..nw-1; step k aliases set sched[k]
+            const DepLayerW sets = L;
+            for (int k = 0; k < c.dep_q; ++k) {
+                L.in_proj[k] = sets.in_proj[sched[k]]; L.out_proj[k] = sets.out_proj[sched[k]];
+                L.ffn_in[k] = sets.ffn_in[sched[k]]; L.ffn_out[k] = sets.ffn_out[sched[k]];
+            }
+        }
         if ((rc = load_copy(lm, W, p + ".norm1.alpha", 3, dd, &L.n1))) return fail(rc);
         if ((rc = load_copy(lm, W, p + ".norm2.alpha", 3, dd, &L.n2))) return fail(rc);
     }
+    if ((low_rank || demux) && lm->q8 > 0)   // the reference would quantise `low_rank` / `out1` / `out2` as well (utils/quantize.py)
+        return fail(mmi_fail(MMI_ERR_UNSUPPORTED, "quantised linears with low-rank or demuxed embeddings are not supported"));
     if (hipSuccess != lm->wts.alloc(&lm->delays_dev, (size_t)lm->NC)) return fail(mmi_fail(MMI_ERR_HIP, "out of device memory"));
     if (hipSuccess != hipMemcpy(lm->delays_dev, c.delays, lm->NC * sizeof(int), hipMemcpyHostToDevice)) return fail(mmi_fail(MMI_ERR_HIP, "memcpy"));
     if (hipDeviceSynchronize() != hipSuccess) return fail(mmi_fail(MMI_ERR_HIP, "weight packing failed"));
@@ -1573,16 +1685,18 @@ extern "C" int mmi_lm_reset(mmi_lm* lm, const uint8_t* mask, mmi_stream stream) 
 extern "C" int mmi_lm_step(mmi_lm* lm, const int64_t* user_codes, int32_t n_user, int64_t* out_tokens, float* opt_text_logits,
                            float* opt_audio_logits, const float* opt_noise, int32_t batch, int32_t* valid, mmi_stream stream) {
     MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
-    if (!lm || !user_codes || !out_tokens) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (!lm || !out_tokens) return mmi_fail(MMI_ERR_INVALID, "null argument");
     if (!lm->streaming)
         return mmi_fail(MMI_ERR_STATE, "You should wrap those calls with a `with lm_gen.streaming(): ...`.");   // lm.py:673-676
+    if (!user_codes && lm->cfg.n_q > lm->cfg.dep_q) return mmi_fail(MMI_ERR_INVALID, "null argument");   // n_q == dep_q (TTS): no user stream
     if (batch != lm->gen_batch) return mmi_fail(MMI_ERR_SHAPE, "Got a different batch size than the streaming batch");   // lm.py:681
     const mmi_lm_cfg& c = lm->cfg;
     const int need_user = c.n_q - c.dep_q;
     if (n_user < need_user) return mmi_fail(MMI_ERR_SHAPE, "not enough user tokens");   // lm.py:683-686
     hipStream_t s = (hipStream_t)stream;
     const int B = batch;
-    MMI_LAUNCH(k_i64_to_i32, mmi_cdiv(B * need_user, 256), 256, 0, s, (const long*)user_codes, (long)n_user, lm->user_i32, B, need_user);
+    if (need_user > 0)
+        MMI_LAUNCH(k_i64_to_i32, mmi_cdiv(B * need_user, 256), 256, 0, s, (const long*)user_codes, (long)n_user, lm->user_i32, B, need_user);
     if (opt_noise && lm->samp.use_sampling && (lm->samp.top_k == 0 || lm->samp.top_k_text == 0))
         return mmi_fail(MMI_ERR_UNSUPPORTED, "supplied noise is indexed by rank in the top-k: not available with top_k = 0");
     if (opt_noise) {

@@ -1544,6 +1544,52 @@ __global__ void k_lm_embed(const int* __restrict__ tokens, int n_codebooks, cons
     x[mmi_xp_index(T, b, d, ksteps)] = mmi_f32_to_bf16(acc);
 }
 
+// The same sum for a model whose text stream is demuxed (demux_second_text_stream, lm_utils.py:95-116): text token t is the pair
+// (t % N, t / N - 1), N = text_card + 1, and embeds as bf16(T1[first] + T2[second]) (second < 0: T1[first] alone), where
+// T1 = out1(E) and T2 = out2(E) were expanded at load (k_expand_emb).  t == -1 is the zero row; a second index beyond the table
+// (a muxed token above N * N - 1) reads its last row.
+__global__ void k_lm_embed_demux(const int* __restrict__ tokens, int n_codebooks, const uint16_t* __restrict__ emb,
+                                 int card1, const uint16_t* __restrict__ text_t1, const uint16_t* __restrict__ text_t2, int N,
+                                 uint16_t* __restrict__ x, int D, int T, int ksteps, const uint16_t* __restrict__ cond) {
+    const int b = blockIdx.y;
+    const int d = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (d >= D) return;
+    const int* tk = tokens + (long)b * n_codebooks;
+    float acc = 0.f;
+    for (int c = 1; c < n_codebooks; ++c) {
+        int t = tk[c];
+        float v = 0.f;
+        if (t != -1) v = mmi_bf16_to_f32(emb[((long)(c - 1) * card1 + (t < 0 ? 0 : t)) * D + d]);
+        acc = c == 1 ? v : mmi_round_bf16(acc + v);
+    }
+    int t0 = tk[0];
+    float tv = 0.f;
+    if (t0 != -1) {
+        const int t = t0 < 0 ? 0 : t0;
+        int second = t / N - 1;
+        if (second > N - 1) second = N - 1;
+        tv = mmi_bf16_to_f32(text_t1[(long)(t % N) * D + d]);
+        if (second >= 0) tv = mmi_round_bf16(tv + mmi_bf16_to_f32(text_t2[(long)second * D + d]));
+    }
+    acc = n_codebooks > 1 ? mmi_round_bf16(acc + tv) : tv;
+    if (cond) acc = acc + mmi_bf16_to_f32(cond[(long)b * D + d]);
+    x[mmi_xp_index(T, b, d, ksteps)] = mmi_f32_to_bf16(acc);
+}
+
+// Load time: out[v][j] = bf16(sum_i E[v][i] * W[j][i]) for E [V][R], W [D][R] (nn.Linear(R, D) applied to every row of an
+// embedding table: the low-rank projection, lm_utils.py:117-124, or a demux stream's out1 / out2, :106-116), fp32 sums in i order.
+// grid (cdiv(D, 256), V), 256 threads.
+__global__ void k_expand_emb(const uint16_t* __restrict__ E, int R, const uint16_t* __restrict__ W, int D, uint16_t* __restrict__ out) {
+    const int v = blockIdx.y;
+    const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (j >= D) return;
+    const uint16_t* e = E + (long)v * R;
+    const uint16_t* w = W + (long)j * R;
+    float acc = 0.f;
+    for (int i = 0; i < R; ++i) acc += mmi_bf16_to_f32(e[i]) * mmi_bf16_to_f32(w[i]);
+    out[(long)v * D + j] = mmi_f32_to_bf16(acc);
+}
+
 // ------------------------------------------------------------------------------------------------
 // temporal attention: RoPE + ring-KV write, split decode attention over the VALID part of the ring, combine
 // ------------------------------------------------------------------------------------------------
@@ -1987,6 +2033,8 @@ struct DepAttnArgs {
     int T, out_ksteps;
 };
 
+// ROWS: the rows of the frame's cache held in registers, >= steps (16: up to 16 micro-steps; 32: the TTS family's 17..32)
+template <int ROWS>
 __global__ __launch_bounds__(64) void k_dep_attn(DepAttnArgs a) {
     const int b = blockIdx.x / a.H, h = blockIdx.x % a.H;
     const int lane = threadIdx.x, Dh = a.Dh, HD = a.H * Dh;
@@ -2004,19 +2052,19 @@ __global__ __launch_bounds__(64) void k_dep_attn(DepAttnArgs a) {
         vcb[(long)a.k * Dh + lane] = vn;
     }
     const float scale = 1.0f / sqrtf((float)Dh);
-    // rows 0..k-1 of this frame's cache, all requested up front (unconditional loads from a clamped row); steps <= 16
-    float kr[16], vr[16];
+    // rows 0..k-1 of this frame's cache, all requested up front (unconditional loads from a clamped row); steps <= ROWS
+    float kr[ROWS], vr[ROWS];
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
+    for (int j = 0; j < ROWS; ++j) {
         const int jc = j < a.k ? j : (a.k > 0 ? a.k - 1 : 0);
         const int lc = on ? lane : 0;
         kr[j] = mmi_bf16_to_f32(kcb[(long)jc * Dh + lc]);
         vr[j] = mmi_bf16_to_f32(vcb[(long)jc * Dh + lc]);
     }
-    float sc[16];
+    float sc[ROWS];
     float mx = -INFINITY;
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
+    for (int j = 0; j < ROWS; ++j) {
         if (j <= a.k) {
             float kv = 0.f;
             if (on) kv = (j == a.k) ? mmi_bf16_to_f32(kn) : kr[j];
@@ -2029,7 +2077,7 @@ __global__ __launch_bounds__(64) void k_dep_attn(DepAttnArgs a) {
     }
     float den = 0.f, o = 0.f;
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
+    for (int j = 0; j < ROWS; ++j) {
         if (j <= a.k) {
             float p = expf(sc[j] - mx);
             den += p;
@@ -2245,6 +2293,42 @@ __device__ __forceinline__ void mmi_sample_next_input(const SampleArgs& a, int b
 // the depth transformer's first input row rebuilt from tok[b] (a step hook changed the text token after the sampler ran)
 __global__ void k_dep_next_input(SampleArgs a, const int* __restrict__ tok) {
     mmi_sample_next_input(a, (int)blockIdx.x, tok[(long)blockIdx.x * a.out_stride]);
+}
+
+// The depth transformer's first input row of a demuxed text stream (demux_second_text_stream): x0[b] = nx_pre[b] +
+// bf16(nx_emb[first] + emb2[second]) with the pair of k_lm_embed_demux, launched after the text sampler (and after an on_text_hook
+// that may have replaced the token with a muxed one).  One workgroup per session.
+__global__ void k_dep_next_input_demux(SampleArgs a, const int* __restrict__ tok, const uint16_t* __restrict__ emb2, int N) {
+    const int b0 = (int)blockIdx.x;
+    const int t0 = tok[(long)b0 * a.out_stride];
+    const int t = t0 < 0 ? 0 : t0;
+    int second = t / N - 1;
+    if (second > N - 1) second = N - 1;
+    const int first = t % N;
+    const int per = a.nx_D / 8;
+    for (int gg = (int)threadIdx.x; gg < (a.nx_dup ? 2 : 1) * per; gg += (int)blockDim.x) {
+        const int g = gg % per, b = b0 + (gg / per) * a.nx_dup;
+        const int n0 = 8 * g;
+        const u32x4 pv = *reinterpret_cast<const u32x4*>(a.nx_pre + (long)b * a.nx_ld + n0);
+        u32x4 e1 = {0u, 0u, 0u, 0u}, e2 = {0u, 0u, 0u, 0u};
+        if (t0 != -1) {
+            e1 = *reinterpret_cast<const u32x4*>(a.nx_emb + (long)first * a.nx_D + n0);
+            if (second >= 0) e2 = *reinterpret_cast<const u32x4*>(emb2 + (long)second * a.nx_D + n0);
+        }
+        u32x4 ov;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            float elo = mmi_bf16_to_f32((uint16_t)(e1[e] & 0xffffu)), ehi = mmi_bf16_to_f32((uint16_t)(e1[e] >> 16));
+            if (second >= 0) {
+                elo = mmi_round_bf16(elo + mmi_bf16_to_f32((uint16_t)(e2[e] & 0xffffu)));
+                ehi = mmi_round_bf16(ehi + mmi_bf16_to_f32((uint16_t)(e2[e] >> 16)));
+            }
+            const float lo = mmi_bf16_to_f32((uint16_t)(pv[e] & 0xffffu)) + elo;
+            const float hi = mmi_bf16_to_f32((uint16_t)(pv[e] >> 16)) + ehi;
+            ov[e] = mmi_pack_bf16x2(lo, hi);
+        }
+        *reinterpret_cast<u32x4*>(a.nx_out + mmi_xp_index(a.nx_T, b, n0, a.nx_ksteps)) = ov;
+    }
 }
 
 __device__ __forceinline__ int mmi_apply_forced(const SampleArgs& a, int b, int tok) {

@@ -28,6 +28,8 @@ class DuplexStream:
     def __init__(self, mimi: MimiModel, lm_gen: LMGen, depth: int = 4):
         assert depth >= 3, "two frames may be in flight when `step` returns"
         assert mimi._lib is lm_gen._lib, "both models must come from the same engine library"
+        from .batcher import _require_duplex_model
+        _require_duplex_model(lm_gen.lm_model.config, "DuplexStream")
         self._lib = mimi._lib
         self.mimi, self.lm_gen = mimi, lm_gen
         self.device = mimi.device

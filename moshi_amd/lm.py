@@ -46,6 +46,22 @@ def _lm_cfg_struct(cfg: LMConfig) -> _capi.LMCfg:
     return s
 
 
+def _lm_cfg_ext_struct(cfg: LMConfig) -> Optional[_capi.LMCfgExt]:
+    """The TTS-family options (mmi_lm_create_ext), or None for a model that has none of them."""
+    sched, r = cfg.depformer_weights_per_step_schedule, cfg.depformer_low_rank_embeddings
+    if sched is None and not r and not cfg.demux_second_text_stream:
+        return None
+    x = _capi.LMCfgExt()
+    if sched is not None:
+        assert len(sched) == cfg.dep_q <= 64, "depformer_weights_per_step_schedule must have dep_q entries"
+        for k, v in enumerate(sched):
+            x.depformer_schedule[k] = int(v)
+        x.depformer_schedule_len = len(sched)
+    x.depformer_low_rank = int(r or 0)
+    x.demux_second_text_stream = 1 if cfg.demux_second_text_stream else 0
+    return x
+
+
 class ConditionFuser:
     """The part of the reference's `ConditionFuser` that `LMGen` uses (conditioners/base.py:349-421): which named condition
     tensors are summed into the model input (`sum`) and which are concatenated along time into the source every temporal
@@ -128,6 +144,10 @@ class LMModel:
             # linears bf16: fail here, with the reason, instead of inside mmi_lm_create
             raise NotImplementedError("quantised linears (int8 / fp8) are not supported for models with cross-attention layers; "
                                       "load the bf16 checkpoint (quantize=False)")
+        if self.quantized and (self.config.depformer_low_rank_embeddings or self.config.demux_second_text_stream):
+            # the reference would quantise the `low_rank` / `out1` / `out2` linears as well (utils/quantize.py): not built
+            raise NotImplementedError("quantised linears (int8 / fp8) are not supported with low-rank or demuxed embeddings; "
+                                      "load the bf16 checkpoint (quantize=False)")
 
         def place(k, v):     # quantised weights and their fp32 scales keep their dtype (utils/quantize.py:29-34); the rest is bf16
             if v.dtype in (torch.int8, torch.float8_e4m3fn):
@@ -137,10 +157,14 @@ class LMModel:
         sd = {k: place(k, v) for k, v in state_dict.items()}
         descs, keep = _capi.tensor_descs(sd)
         cfg = _lm_cfg_struct(self.config)
+        ext = _lm_cfg_ext_struct(self.config)
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         with _capi.device_scope(self.device):             # the handle binds to the device current at create
-            lib.check(lib.mmi_lm_create(C.byref(cfg), descs, len(sd), max_batch, C.byref(self._handle)))
+            if ext is None:
+                lib.check(lib.mmi_lm_create(C.byref(cfg), descs, len(sd), max_batch, C.byref(self._handle)))
+            else:
+                lib.check(lib.mmi_lm_create_ext(C.byref(cfg), C.byref(ext), descs, len(sd), max_batch, C.byref(self._handle)))
         del keep, sd
         self.max_batch = max_batch
         self.training = False
@@ -564,7 +588,8 @@ class LMGen:
 
     @torch.no_grad()
     def step(self, input_tokens: torch.Tensor, depformer_replace_tokens: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
-        """[B, >=8, 1] int64 user codes -> [B, 1 + dep_q, 1] int64 (text + generated audio) or None during the delay."""
+        """[B, >= n_q - dep_q, 1] int64 user codes (8 for Moshi, none - [B, 0, 1] - for a TTS model where n_q == dep_q) ->
+        [B, 1 + dep_q, 1] int64 (text + generated audio) or None during the delay."""
         forced = None
         if depformer_replace_tokens is not None:   # lm.py:751-755
             assert depformer_replace_tokens.dim() == 3

@@ -96,16 +96,25 @@ def lm_config_from_kwargs(lm_kwargs: Optional[dict]) -> LMConfig:
     if lm_kwargs is None:
         return LMConfig()
     kw = dict(lm_kwargs)
+    if "demux_second_stream" in kw:                      # moved parameter (loaders.py:395-396)
+        kw["demux_second_text_stream"] = kw.pop("demux_second_stream")
     for key, allowed in (("causal", (True,)), ("layer_scale", (None,)), ("gating", ("silu",)), ("norm", ("rms_norm_f32",)),
                          ("positional_embedding", ("rope",)), ("depformer_layer_scale", (None,)), ("depformer_multi_linear", (True,)),
                          ("depformer_gating", ("silu",)), ("depformer_pos_emb", ("none",)), ("depformer_weights_per_step", (True,)),
-                         ("demux_second_text_stream", (False,)), ("demux_second_stream", (False,)),
-                         ("depformer_low_rank_embeddings", (None,)), ("text_card_out", (None, kw.get("text_card")))):
+                         ("text_card_out", (None, kw.get("text_card")))):
         _require(kw, key, allowed, "Moshi LM")
     if "depformer_context" in kw and kw["depformer_context"] < kw["dep_q"]:
         raise ValueError("depformer_context must cover the dep_q micro-steps")
-    if kw.get("depformer_weights_per_step_schedule") is not None:
-        raise ValueError("depformer_weights_per_step_schedule is not implemented by the engine")
+    schedule = kw.get("depformer_weights_per_step_schedule")
+    if schedule is not None:                             # lm.py:125-127; transformer.py:395-401 sizes the weight sets by max + 1
+        schedule = [int(v) for v in schedule]
+        if len(schedule) != kw["dep_q"]:
+            raise ValueError(f"depformer_weights_per_step_schedule has {len(schedule)} entries, expected dep_q = {kw['dep_q']}")
+        if not schedule or sorted(set(schedule)) != list(range(max(schedule) + 1)):
+            raise ValueError(f"depformer_weights_per_step_schedule must use the weight indices 0..max without gaps: {schedule}")
+    low_rank = kw.get("depformer_low_rank_embeddings")
+    if low_rank is not None and (int(low_rank) <= 0 or int(low_rank) % 8):
+        raise ValueError(f"depformer_low_rank_embeddings = {low_rank!r} is not implemented by the engine (a positive multiple of 8)")
     return LMConfig(
         dim=kw["dim"], num_heads=kw["num_heads"], num_layers=kw["num_layers"], hidden_scale=kw.get("hidden_scale", 4.125),
         context=kw["context"], max_period=float(kw.get("max_period", 10000)), n_q=kw["n_q"], dep_q=kw["dep_q"], card=kw["card"],
@@ -114,7 +123,10 @@ def lm_config_from_kwargs(lm_kwargs: Optional[dict]) -> LMConfig:
         depformer_dim=kw["depformer_dim"], depformer_dim_feedforward=int(kw["depformer_dim_feedforward"]),
         depformer_num_heads=kw["depformer_num_heads"], depformer_num_layers=kw["depformer_num_layers"],
         delays=list(kw["delays"]), extra_heads_num_heads=kw.get("extra_heads_num_heads", 0),
-        extra_heads_dim=kw.get("extra_heads_dim", 6), cross_attention=bool(kw.get("cross_attention", False)))
+        extra_heads_dim=kw.get("extra_heads_dim", 6), cross_attention=bool(kw.get("cross_attention", False)),
+        depformer_weights_per_step_schedule=schedule,
+        depformer_low_rank_embeddings=None if low_rank is None else int(low_rank),
+        demux_second_text_stream=bool(kw.get("demux_second_text_stream", False)))
 
 
 def get_mimi(filename: str | Path | None, mimi_config: dict | None = None, device: torch.device | str = "cuda",

@@ -96,6 +96,9 @@ def lm_state_spec(cfg: LMConfig) -> Spec:
     for i in range(cfg.n_q):
         spec.append((f"emb.{i}.weight", (cfg.card + 1, d), f"emb:{d}"))
     spec.append(("text_emb.weight", (cfg.text_card + 1, d), f"emb:{d}"))
+    if cfg.demux_second_text_stream:       # lm_utils.py:95-98: one table, two linears
+        spec.append(("text_emb.out1.weight", (d, d), f"fan:{d}"))
+        spec.append(("text_emb.out2.weight", (d, d), f"fan:{d}"))
     spec.append(("text_linear.weight", (cfg.text_card, d), f"fan:{d}"))
     spec.append(("out_norm.alpha", (1, 1, d), "alpha"))
     for l in range(cfg.num_layers):
@@ -111,20 +114,31 @@ def lm_state_spec(cfg: LMConfig) -> Spec:
             spec.append((p + ".cross_attention.out_projs.0.weight", (d, d), f"fan:{d}"))
             spec.append((p + ".norm_cross.weight", (d,), "norm_w"))
             spec.append((p + ".norm_cross.bias", (d,), "norm_b"))
-    for k in range(cfg.dep_q):
+    nw = cfg.depformer_num_weights         # shared weight sets under a schedule (lm.py:174-179, transformer.py:395-401, 684-688)
+    r = cfg.depformer_low_rank_embeddings  # low-rank tables [V, r] + `low_rank` nn.Linear(r, dd) (lm_utils.py:80-94)
+    for k in range(nw):
         spec.append((f"depformer_in.{k}.weight", (dd, d), f"fan:{d}"))
     for k in range(cfg.dep_q - 1):
-        spec.append((f"depformer_emb.{k}.weight", (cfg.card + 1, dd), f"emb:{dd}"))
+        if r:
+            spec.append((f"depformer_emb.{k}.weight", (cfg.card + 1, r), f"emb:{dd}"))
+            spec.append((f"depformer_emb.{k}.low_rank.weight", (dd, r), f"fan:{r}"))
+        else:
+            spec.append((f"depformer_emb.{k}.weight", (cfg.card + 1, dd), f"emb:{dd}"))
     if cfg.dep_q > 0:                      # "No-Depformer --- e.g., an ASR model" (lm.py:187-221): none of the depth weights exist
-        spec.append(("depformer_text_emb.weight", (cfg.text_card + 1, dd), f"emb:{dd}"))
+        spec.append(("depformer_text_emb.weight", (cfg.text_card + 1, r or dd), f"emb:{dd}"))
+        if r:                              # kept on the demux branch too, where the reference does not apply it (lm_utils.py:106-116)
+            spec.append(("depformer_text_emb.low_rank.weight", (dd, r), f"fan:{r}"))
+        if cfg.demux_second_text_stream:
+            spec.append(("depformer_text_emb.out1.weight", (dd, r or dd), f"fan:{r or dd}"))
+            spec.append(("depformer_text_emb.out2.weight", (dd, r or dd), f"fan:{r or dd}"))
     for l in range(cfg.depformer_num_layers if cfg.dep_q > 0 else 0):
         p = f"depformer.layers.{l}"
-        for k in range(cfg.dep_q):
+        for k in range(nw):
             spec.append((p + f".self_attn.in_projs.{k}.weight", (3 * dd, dd), f"fan:{dd}"))
             spec.append((p + f".self_attn.out_projs.{k}.weight", (dd, dd), f"fan:{dd}"))
         spec.append((p + ".norm1.alpha", (1, 1, dd), "alpha"))
         spec.append((p + ".norm2.alpha", (1, 1, dd), "alpha"))
-        for k in range(cfg.dep_q):
+        for k in range(nw):
             spec.append((p + f".gating.{k}.linear_in.weight", (2 * dh, dd), f"fan:{dd}"))
             spec.append((p + f".gating.{k}.linear_out.weight", (dd, dh), f"fan:{dh}"))
     for k in range(cfg.dep_q):
@@ -205,7 +219,7 @@ def normalize_lm_state_dict(sd: Dict[str, torch.Tensor], cfg: LMConfig) -> Dict[
             out[key] = val
             continue
         prefix, dst = hit
-        mult = cfg.dep_q if prefix.startswith("depformer.") else 1
+        mult = cfg.depformer_num_weights if prefix.startswith("depformer.") else 1
         assert val.shape[0] % mult == 0, f"{key}: leading dimension {val.shape[0]} is not a multiple of {mult} steps"
         parts = val.view(mult, -1, *val.shape[1:])
         for i in range(mult):
