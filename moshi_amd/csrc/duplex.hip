@@ -51,6 +51,7 @@ enum { F_ENC = 0, F_LM = 1, F_DEC = 2, F_IN = 3, F_COUNT = 4 };
 }  // namespace
 
 struct mmi_duplex {
+    MmiKnobs knobs;                                // the MMI_* environment as it was when the pipeline was created (mmi_knobs.h)
     mmi_mimi* mimi = nullptr;
     mmi_lm* lm = nullptr;
     int device = -1;
@@ -176,11 +177,11 @@ int create_impl(mmi_duplex* d) {
     MMI_HIP_CHECK(hipMalloc((void**)&d->flags, (size_t)F_COUNT * 16 * sizeof(long)));
     MMI_HIP_CHECK(hipMemset(d->flags, 0, (size_t)F_COUNT * 16 * sizeof(long)));
     int lo = 0, hi = 0;
-    // MMI_DUPLEX_CODEC_CUS=n (experiment, round 6): the codec streams confined to n of the CUs (a CU mask of n bits, which the driver
+    // knobs.duplex_codec_cus = n (experiment, round 6): the codec streams confined to n of the CUs (a CU mask of n bits, which the driver
     // deals out over the XCDs), so that the depth transformer's launches - 96..176 workgroups that need a whole CU's wave slots each -
     // find free CUs while the codec of the neighbouring frames runs beside them; such streams have the default priority
-    const int codec_cus = getenv("MMI_DUPLEX_CODEC_CUS") ? atoi(getenv("MMI_DUPLEX_CODEC_CUS")) : 0;
-    if (codec_cus > 0 && codec_cus < 256) {
+    const int codec_cus = d->knobs.duplex_codec_cus;
+    if (codec_cus > 0) {
         unsigned mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (int i = 0; i < codec_cus; ++i) mask[i >> 5] |= 1u << (i & 31);
         int plo = 0, phi = 0;
@@ -193,10 +194,10 @@ int create_impl(mmi_duplex* d) {
         // The LM's stream in the high-priority pool, the codec's two in the low one: the step's critical path is the LM's launch
         // chain, the codec only has to be done by the time the next step wants its codes.  Same-box pairs (round 6,
         // profiles/r06_logs/ab_stream_priorities.txt): -0.02 ms per 32-session step on average against the reverse (rounds 3-5),
-        // -0.06 ms at 64 sessions; equal priorities: +0.5 ms.  MMI_DUPLEX_PRIO = codec / none select those for an A/B.
-        const char* pe = getenv("MMI_DUPLEX_PRIO");
+        // -0.06 ms at 64 sessions; equal priorities: +0.5 ms.  knobs.duplex_prio 'c' (codec) / 'n' (none) select those for an A/B.
+        const char pe = d->knobs.duplex_prio;
         const int mid = (lo + hi) / 2;
-        const int pl = pe && pe[0] == 'c' ? lo : (pe && pe[0] == 'n' ? mid : hi), pc = pe && pe[0] == 'c' ? hi : (pe && pe[0] == 'n' ? mid : lo);
+        const int pl = pe == 'c' ? lo : (pe == 'n' ? mid : hi), pc = pe == 'c' ? hi : (pe == 'n' ? mid : lo);
         MMI_HIP_CHECK(hipStreamCreateWithPriority(&d->sL, hipStreamNonBlocking, pl));
         MMI_HIP_CHECK(hipStreamCreateWithPriority(&d->sE, hipStreamNonBlocking, pc));
         MMI_HIP_CHECK(hipStreamCreateWithPriority(&d->sD, hipStreamNonBlocking, pc));
@@ -243,9 +244,11 @@ int enqueue_decode(mmi_duplex* d, int p, bool host_saw_step) {
 
 extern "C" int mmi_duplex_create(mmi_mimi* mimi, mmi_lm* lm, mmi_duplex** out) {
     MmiDeviceGuard dev_guard_(lm ? mmi_lm_device(lm) : -1);
+    const MmiKnobs knobs = mmi_knobs_from_env();     // the handle's one reading of the environment
     if (!mimi || !lm || !out) return mmi_fail(MMI_ERR_INVALID, "null argument");
     if (mmi_lm_device(lm) != mmi_mimi_device(mimi)) return mmi_fail(MMI_ERR_INVALID, "the codec and the LM live on different devices");
     mmi_duplex* d = new mmi_duplex();
+    d->knobs = knobs;
     d->mimi = mimi;
     d->lm = lm;
     d->device = mmi_lm_device(lm);

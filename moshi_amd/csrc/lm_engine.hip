@@ -42,11 +42,12 @@ struct EvPair { hipEvent_t a, b; };
 }  // namespace
 
 struct mmi_lm {
+    MmiKnobs knobs;                 // the MMI_* environment as it was when the handle was created (mmi_knobs.h)
     mmi_lm_cfg cfg;
     int device = -1;                // HIP device the handle lives on (current at create); see MmiDeviceGuard
     int max_batch = 0;
     int T = 32;                     // MFMA tile of the temporal transformer and the heads: 16 when max_batch <= 16, else 32 (lm_kernels.h)
-    int Td = 32;                    // MFMA tile of the depth transformer (its linears, dx / dxn / datt / dhb): T.  MMI_DEP_TILE=16 (17..32
+    int Td = 32;                    // MFMA tile of the depth transformer (its linears, dx / dxn / datt / dhb): T.  knobs.dep_tile = 16 (17..32
                                     // sessions, bf16): two 16-row batch tiles per 16-row weight tile - measured in round 6 inside the step
                                     // (profiles/r06_logs/ab_dep_tile_once.txt): in_proj -0.14 us, linear_out -0.6, but the gated
                                     // linear_in +3.0 (352 tiles at 128 registers: spills) and out_proj +0.3 -> +0.15 ms per step; the
@@ -110,7 +111,7 @@ struct mmi_lm {
     float* partial = nullptr;                       // [4][B][max(dim, depformer_dim)] split-K partial sums
     float* rope = nullptr;                          // [B][Dh/2][2] (cos, sin) of the step's new position
     // int8 activations (BASELINE configs[4], the reference's own arithmetic: QLinear.forward -> bitsandbytes' int8 x int8 matmul,
-    // utils/quantize.py:24-40): on for int8 linears unless MMI_Q8_ACT=bf16 (weight-only, rounds 1-3) or the model has
+    // utils/quantize.py:24-40): on for int8 linears unless knobs.q8_act_bf16 (weight-only, rounds 1-3) or the model has
     // cross-attention layers.  xnq / attq / hbq / toutq: the int8 operand Xq[mt][kp][lane][16] next to its bf16 tensor, sx_*: its
     // rows' absmax (bitsandbytes' SCA).  Who quantises: the norm kernel for its own output (one workgroup per row); a
     // k_quant_rows_i8 launch for the temporal attention output and the gated FFN tensor (rows written by many workgroups); the
@@ -148,7 +149,7 @@ struct mmi_lm {
     bool precapture_failed = false; // capturing the second attention program ahead of time failed once: not tried again for this stream
     bool dominant_xlds = false;     // the profiled (dominant) GEMM ran on k_gemm_xlds
     MmiProgram prog;
-    // MMI_DEBUG_TRACE=<prefix> (debug: finding which launch of the step is not reproducible): every step runs its launch list
+    // knobs.debug_trace (debug: finding which launch of the step is not reproducible): every step runs its launch list
     // eagerly and, after EVERY op, checksums every allocation of the streaming state; lines "step op site allocation bytes
     // checksum" for the allocations an op changed go to <prefix>.<n> (n = streaming sessions of the process so far).  Two
     // sessions fed the same inputs must write the same file.
@@ -298,16 +299,13 @@ struct GemmPlan { int waves, ntw, ksplit, u, osplit; };
 
 // How a GEMM is cut into workgroups (measured on MI355X with scripts/gemm_microbench.hip): enough workgroups to
 // cover the 256 CUs, K split over the waves of a workgroup, more waves per workgroup when there are few n-tiles.
-GemmPlan plan_gemm(const GemmW& g, bool may_split) {
+GemmPlan plan_gemm(const MmiKnobs& k, const GemmW& g, bool may_split) {
     GemmPlan p;
     p.ntw = 1;
     p.ksplit = 1;
     // few n-tiles (N = 4096 at the 32-row tile): split K over workgroups so that every CU streams weights
     if (may_split && g.NT < 200 && g.KSTEPS >= 128) p.ksplit = g.NT <= 64 ? 4 : 2;
-    if (const char* ek = getenv("MMI_GEMM_KSPLIT")) {      // test hook: force the split-K path on small shapes
-        const int v = atoi(ek);
-        if (may_split && v >= 1 && v <= 4 && g.KSTEPS >= v) p.ksplit = v;
-    }
+    if (k.gemm_ksplit && may_split && g.KSTEPS >= k.gemm_ksplit) p.ksplit = k.gemm_ksplit;      // test hook: force the split-K path
     const int ks = g.KSTEPS / p.ksplit;
     p.waves = ks >= 32 ? 8 : 4;
     // fragments in flight per register buffer: 2 for the widest GEMM (the temporal FFN linear_in, 704 n-tiles: fewer
@@ -323,17 +321,15 @@ GemmPlan plan_gemm(const GemmW& g, bool may_split) {
 
 // Octet sharing of k_gemm_xp (GemmArgs::osplit): GEMMs with so few n-tiles that most CUs would idle while each busy one is
 // bound by what a single CU can pull (~25 GB/s) - the depth transformer's N = 1024 linears: 32 tiles of 64-180 KB.
-// MMI_GEMM_OSPLIT: "0" = off, "2" / "4" = force (test hook / A-B), default = as many parts as bring the launch to >= 128 workgroups.
-int plan_osplit(const GemmW& g, const GemmPlan& p, int epi, int T) {
+// knobs.gemm_osplit: 0 = off, 2 / 4 = force (test hook / A-B), default = as many parts as bring the launch to >= 128 workgroups.
+int plan_osplit(const MmiKnobs& k, const GemmW& g, const GemmPlan& p, int epi, int T) {
     if (epi == MMI_EPI_GATE || g.wq != 0 || p.ntw != 1 || (T != 32 && T != 16)) return 1;
     const int octs = T / 8;
     int os = 1;
-    const char* e = getenv("MMI_GEMM_OSPLIT");
-    if (e && e[0]) {
-        const int v = atoi(e);
-        if (v <= 1) return 1;
-        os = v < octs ? v : octs;
-        if (e[1] == 'a') return os;            // "4a": every eligible GEMM (tests)
+    if (k.gemm_osplit != MmiKnobs::UNSET) {
+        if (k.gemm_osplit <= 1) return 1;
+        os = k.gemm_osplit < octs ? k.gemm_osplit : octs;
+        if (k.gemm_osplit_all) return os;      // "4a": every eligible GEMM (tests)
         return (long)g.NT * p.ksplit <= 64 ? os : 1;
     }
     while (os < octs && (long)g.NT * p.ksplit * os < 128) os *= 2;
@@ -353,14 +349,13 @@ int launch_gemm_q(hipStream_t s, dim3 groups, int waves, const GemmArgs& a) {
 }
 
 template <int TN, int MT, int NTW>
-int launch_gemm_w(hipStream_t s, dim3 groups, int waves, int u, int wq, const GemmArgs& a) {
+int launch_gemm_w(hipStream_t s, dim3 groups, int waves, int u, int wq, bool q8_u2, const GemmArgs& a) {
     if (wq == 1) return launch_gemm_q<TN, MT, NTW, 1>(s, groups, waves, a);
     if (wq == 2) return launch_gemm_q<TN, MT, NTW, 2>(s, groups, waves, a);
     if (wq == 3) {
-        // int8 x int8 has no conversion to hold in registers: four entries per register buffer instead of two (MMI_Q8_U=2: the
+        // int8 x int8 has no conversion to hold in registers: four entries per register buffer instead of two (q8_u2: the
         // weight-only depth, same-box A/B)
-        static const bool u4 = !(getenv("MMI_Q8_U") && getenv("MMI_Q8_U")[0] == '2');
-        if (u4 && waves == 8) {
+        if (!q8_u2 && waves == 8) {
             if constexpr (MT * NTW <= 2) {
                 MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 8, 4, 3>), groups, 512, 0, s, a);
                 MMI_CHECK_LAUNCH();
@@ -386,29 +381,29 @@ int launch_gemm_w(hipStream_t s, dim3 groups, int waves, int u, int wq, const Ge
 }
 
 template <int TN>
-int launch_gemm_t(hipStream_t s, const GemmPlan& p, int NT, int mt, const GemmArgs& a) {
+int launch_gemm_t(hipStream_t s, const GemmPlan& p, int NT, int mt, bool q8_u2, const GemmArgs& a) {
     const dim3 groups(mmi_cdiv(NT, p.ntw) * (a.osplit > 1 ? a.osplit : 1), p.ksplit);
     const int w8 = a.wq;
-    if (mt == 1) return launch_gemm_w<TN, 1, 1>(s, groups, p.waves, p.u, w8, a);     // one n-tile per workgroup (two measured slower
-    if (mt == 2) return launch_gemm_w<TN, 2, 1>(s, groups, p.waves, p.u, w8, a);     // in the step, DESIGN 9e: not instantiated)
+    if (mt == 1) return launch_gemm_w<TN, 1, 1>(s, groups, p.waves, p.u, w8, q8_u2, a);     // one n-tile per workgroup (two measured slower
+    if (mt == 2) return launch_gemm_w<TN, 2, 1>(s, groups, p.waves, p.u, w8, q8_u2, a);     // in the step, DESIGN 9e: not instantiated)
     return mmi_fail(MMI_ERR_UNSUPPORTED, "batch too large for the skinny GEMM");
 }
 
-// k_gemm_xlds (activations resident in LDS, one workgroup per CU): which GEMMs take it, and how.  MMI_GEMM_LDS: "2" = with
+// k_gemm_xlds (activations resident in LDS, one workgroup per CU): which GEMMs take it, and how.  knobs.gemm_lds: '2' = with
 // the staggered tail (each tile's epilogue under the last chunk's weight stream; the DEFAULT for bf16 weights at the 32-row
 // tile: same-box A/B of the default benchmark 8.10 / 8.12 ms against 8.17 / 8.20 ms with k_gemm_xp, dominant kernel 38.6
-// against 40.2 us live, profiles/r02_logs/ab_gemm_xlds_stagger_in_step.txt), "1" = plain tails (also what int8 / fp8 weight
-// entries take when asked for; they stay on k_gemm_xp by default), "0" = k_gemm_xp everywhere.
+// against 40.2 us live, profiles/r02_logs/ab_gemm_xlds_stagger_in_step.txt), '1' = plain tails (also what int8 / fp8 weight
+// entries take when asked for; they stay on k_gemm_xp by default), '0' = k_gemm_xp everywhere.
 struct XldsPlan { bool on; int kc, grid; size_t smem; bool stagger; };
 XldsPlan plan_xlds(const mmi_lm* lm, const GemmW& g, const GemmArgs& a, int mt) {
     XldsPlan p{false, 0, 0, 0, false};
-    const char* en = getenv("MMI_GEMM_LDS");
-    const char mode = en && en[0] ? en[0] : (g.wq == 0 ? '2' : '0');
+    const MmiKnobs& k = lm->knobs;
+    const char mode = k.gemm_lds ? k.gemm_lds : (g.wq == 0 ? '2' : '0');
     if (mode == '0' || g.T != 32 || mt > 2) return p;
     if (a.epi != MMI_EPI_GATE && a.epi != MMI_EPI_ROPE_KV && a.epi != MMI_EPI_STORE) return p;   // no prefetched addend, no split-K
     int cus = 256;                                             // MI355X: 256 CUs
-    const char* tg = getenv("MMI_GEMM_LDS_GRID");              // test hook: small grids / short chunks for the tiny shapes
-    if (tg && atoi(tg) > 0) cus = atoi(tg);
+    const bool tg = k.gemm_lds_grid != MmiKnobs::UNSET;        // test hook: small grids / short chunks for the tiny shapes
+    if (k.gemm_lds_grid > 0) cus = k.gemm_lds_grid;
     const int xs = (g.wq && a.wq != 3) ? 2 : 1;                // activation fragments per weight entry (int8 activations: one entry)
     const int big = ((g.wq && a.wq != 3) ? 32 : 64) / mt;      // 64 KiB of activations per chunk buffer (int8 activations: 1 KiB per entry)
     if (g.KSTEPS % big == 0 && g.NT >= 128) p.kc = big;       // the large temporal GEMMs
@@ -463,11 +458,10 @@ int launch_xlds(hipStream_t s, const XldsPlan& p, const GemmArgs& a) {
 // dependent memory round trips although they are a latency chain, not a stream: bf16 weights behind at most 256 workgroups of 8
 // waves whose slice is longer than the two register buffers of k_gemm_xp (2 x 4 k-steps) and short enough for the registers -
 // the depth transformer's linear_out (2816 -> 1024: 22 k-steps per wave at the 32-row tile, 11 at the 16-row tile).
-// Returns the instantiated slice length, 0 = k_gemm_xp.  MMI_GEMM_ONCE=0: off (same-box A/B; bit-identical either way); "a": every
+// Returns the instantiated slice length, 0 = k_gemm_xp.  knobs.gemm_once '0': off (same-box A/B; bit-identical either way); 'a': every
 // bf16 GEMM whose slices fit (test hook: the tiny shapes, always on 8 waves).
-int once_kmax(const GemmW& g, const GemmPlan& p, int mt, const GemmArgs& a) {
-    const char* e = getenv("MMI_GEMM_ONCE");
-    const bool off = e && e[0] == '0', all = e && e[0] == 'a';
+int once_kmax(char gemm_once, const GemmW& g, const GemmPlan& p, int mt, const GemmArgs& a) {
+    const bool off = gemm_once == '0', all = gemm_once == 'a';
     if (off || a.wq != 0 || p.ntw != 1 || a.epi == MMI_EPI_GATE) return 0;
     const int kper = mmi_cdiv(mmi_cdiv(g.KSTEPS, p.ksplit), 8);
     if (!all) {
@@ -494,8 +488,9 @@ int launch_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, GemmArgs a, bool is_d
     a.wq = (g.wq == 1 && a.wq >= 3) ? a.wq : g.wq;             // int8 linears: 3 / 4 = int8 activations (set by the program builder)
     a.xinv = g.xinv;
     const int mt = mmi_cdiv(a.B, g.T);
-    const GemmPlan p = plan_gemm(g, a.epi == MMI_EPI_PARTIAL);
-    a.osplit = plan_osplit(g, p, a.epi, g.T);
+    const MmiKnobs& k = lm->knobs;
+    const GemmPlan p = plan_gemm(k, g, a.epi == MMI_EPI_PARTIAL);
+    a.osplit = plan_osplit(k, g, p, a.epi, g.T);
     const XldsPlan xl = plan_xlds(lm, g, a, mt);
     EvPair* ev = nullptr;
     if (lm->profiling && is_dominant) {
@@ -515,15 +510,18 @@ int launch_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, GemmArgs a, bool is_d
     if (xl.on) {
         lm->xlds_launches += 1;
         rc = mt == 1 ? launch_xlds<1>(s, xl, a) : launch_xlds<2>(s, xl, a);
-    } else if (const int kmax = once_kmax(g, p, mt, a)) {
+    } else if (const int kmax = once_kmax(k.gemm_once, g, p, mt, a)) {
         rc = launch_once(s, g.T, mt, kmax, dim3(g.NT * (a.osplit > 1 ? a.osplit : 1), p.ksplit), a);
     } else {
-        rc = g.T == 32 ? launch_gemm_t<32>(s, p, g.NT, mt, a) : launch_gemm_t<16>(s, p, g.NT, mt, a);
+        rc = g.T == 32 ? launch_gemm_t<32>(s, p, g.NT, mt, k.q8_u2, a) : launch_gemm_t<16>(s, p, g.NT, mt, k.q8_u2, a);
     }
     if (rc) return rc;
     if (ev) MMI_HIP_CHECK(hipEventRecord(ev->b, s));
     return MMI_OK;
 }
+
+// int8 activations (see mmi_lm::act8)
+bool act8_of(const mmi_lm* lm) { return lm->q8 == 1 && !lm->cfg.cross_attention && !lm->knobs.q8_act_bf16; }
 
 // number of bf16 elements of a packed activation buffer with `features` columns
 // k-steps of a packed activation buffer with `features` columns (even when the linears are int8: their weight entries
@@ -563,11 +561,11 @@ void add_gemm(mmi_lm* lm, const GemmW& g, const uint16_t* x, uint16_t* out, int 
 // The depth transformer's attention inside its out_proj (k_dep_attn_out_proj): ONE session at the 16-row tile (the real-time
 // configuration), bf16 weights, a wave's K-slice = one or two whole heads.  Same-box at 1 / 2 / 4 sessions: -0.06 / +0.04 / +0.27 ms
 // per step (a wave works through its 2 B pairs one after the other; profiles/r04_logs/call_o2_summary.txt), hence one session only.
-// MMI_NO_DEP_ATTN_FUSION=1: the two launches (A/B and the bit-equality test)
+// knobs.no_dep_attn_fusion: the two launches (A/B and the bit-equality test)
 bool dep_attn_fusable(const mmi_lm* lm, const GemmW& g, int H, int Dh, int steps) {
-    if (g.T != 16 || lm->batch != 1 || lm->act8 || g.wq != 0 || getenv("MMI_NO_DEP_ATTN_FUSION")) return false;
+    if (g.T != 16 || lm->batch != 1 || lm->act8 || g.wq != 0 || lm->knobs.no_dep_attn_fusion) return false;
     if (Dh % 8 || Dh > 64 || steps > 8 || g.KSTEPS * 32 != H * Dh) return false;
-    const GemmPlan p = plan_gemm(g, false);
+    const GemmPlan p = plan_gemm(lm->knobs, g, false);
     const int kper = mmi_cdiv(g.KSTEPS, p.waves);
     return kper <= 4 && (kper * 32) % Dh == 0 && kper * 32 / Dh <= 2;
 }
@@ -586,8 +584,8 @@ void add_dep_attn_out_proj(mmi_lm* lm, const GemmW& g, const DepAttnArgs& da, ui
     a.out = x; a.epi = MMI_EPI_RESID; a.resid = x; a.B = lm->batch; a.tok_rows = lm->gen_batch;
     a.out_mode = MMI_OUT_PACKED; a.out_ld = features; a.out_ksteps = packed_ksteps_t(lm, g.T, features);
     a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT; a.wscale = g.scale; a.xinv = g.xinv;
-    const GemmPlan p = plan_gemm(g, false);
-    a.osplit = plan_osplit(g, p, a.epi, g.T);
+    const GemmPlan p = plan_gemm(lm->knobs, g, false);
+    a.osplit = plan_osplit(lm->knobs, g, p, a.epi, g.T);
     const int groups = g.NT * (a.osplit > 1 ? a.osplit : 1), waves = p.waves;
     const long bytes = (long)g.bytes;
     lm->prog.add([=](hipStream_t s) {
@@ -603,7 +601,7 @@ struct Pending { int P = 0; const float* sx = nullptr; const float* scb = nullpt
 // K-split GEMM whose partial sums (lm->partial) the following add_resid_rmsnorm folds into the residual stream.
 // Returns the partials, P = 0 when the GEMM is not split (then it applied the residual itself, in place on x).
 Pending add_gemm_resid(mmi_lm* lm, const GemmW& g, const uint16_t* in, uint16_t* x, int features, const Q8* q8 = nullptr) {
-    const GemmPlan p = plan_gemm(g, true);
+    const GemmPlan p = plan_gemm(lm->knobs, g, true);
     if (p.ksplit <= 1) {
         add_gemm(lm, g, in, x, features, true, MMI_EPI_RESID, x, nullptr, nullptr, 0, false, nullptr, q8);
         return Pending{};
@@ -650,22 +648,17 @@ void add_hidden_tap(mmi_lm* lm, int which) {
     });
 }
 
-// k_gemm_q8 at 33..64 sessions: one batch tile per workgroup (grid.y = tiles; the default) or both tiles walked by one workgroup
-// (MMI_Q8_TILES=serial: the round-4 form, same-box A/B)
-static bool q8_tiles_over_grid() {
-    const char* e = getenv("MMI_Q8_TILES");
-    return !(e && e[0] == 's');
-}
-
 // RMSNorm fused in front of a short-row GEMM (k_gemm_xp_norm; int8 x int8: k_gemm_q8<NORM>): the launch by tile / batch tiles / weight format
-int launch_norm_fused(hipStream_t s, int T, int mt, int wq, int NT, const GemmArgs& a) {
+// tiles_over_grid (k_gemm_q8 at 33..64 sessions): one batch tile per workgroup (grid.y = tiles; the default) or both tiles walked by
+// one workgroup (knobs.q8_tiles_serial: the round-4 form, same-box A/B)
+int launch_norm_fused(hipStream_t s, int T, int mt, int wq, int NT, bool tiles_over_grid, const GemmArgs& a) {
     if (wq == 1) {
         if (T == 32 && mt == 1) MMI_LAUNCH((k_gemm_xp_norm<32, 1, 8, 4, 1>), NT, 512, 0, s, a);
         else if (T == 32) MMI_LAUNCH((k_gemm_xp_norm<32, 2, 8, 4, 1>), NT, 512, 0, s, a);
         else MMI_LAUNCH((k_gemm_xp_norm<16, 1, 8, 4, 1>), NT, 512, 0, s, a);
     } else if (wq == 3) {
         if (T == 32 && mt == 1) MMI_LAUNCH((k_gemm_q8<32, 1, 8, 4, true>), NT, 512, 0, s, a);
-        else if (T == 32 && q8_tiles_over_grid()) MMI_LAUNCH((k_gemm_q8<32, 1, 8, 4, true>), dim3(NT, mt), 512, 0, s, a);
+        else if (T == 32 && tiles_over_grid) MMI_LAUNCH((k_gemm_q8<32, 1, 8, 4, true>), dim3(NT, mt), 512, 0, s, a);
         else if (T == 32) MMI_LAUNCH((k_gemm_q8<32, 2, 8, 4, true>), NT, 512, 0, s, a);
         else MMI_LAUNCH((k_gemm_q8<16, 1, 8, 4, true>), NT, 512, 0, s, a);
     } else if (wq == 2) {
@@ -688,15 +681,15 @@ int launch_norm_fused(hipStream_t s, int T, int mt, int wq, int NT, const GemmAr
 }
 
 // k_gemm_q8 without a norm: the row quantisation inside the GEMM (kmax = 4: rows of <= 32 entries, 11: <= 88)
-int launch_q8_fused(hipStream_t s, int T, int mt, int kmax, int NT, const GemmArgs& a) {
+int launch_q8_fused(hipStream_t s, int T, int mt, int kmax, int NT, bool tiles_over_grid, const GemmArgs& a) {
     if (kmax == 4) {
         if (T == 32 && mt == 1) MMI_LAUNCH((k_gemm_q8<32, 1, 8, 4, false>), NT, 512, 0, s, a);
-        else if (T == 32 && q8_tiles_over_grid()) MMI_LAUNCH((k_gemm_q8<32, 1, 8, 4, false>), dim3(NT, mt), 512, 0, s, a);
+        else if (T == 32 && tiles_over_grid) MMI_LAUNCH((k_gemm_q8<32, 1, 8, 4, false>), dim3(NT, mt), 512, 0, s, a);
         else if (T == 32) MMI_LAUNCH((k_gemm_q8<32, 2, 8, 4, false>), NT, 512, 0, s, a);
         else MMI_LAUNCH((k_gemm_q8<16, 1, 8, 4, false>), NT, 512, 0, s, a);
     } else {
         if (T == 32 && mt == 1) MMI_LAUNCH((k_gemm_q8<32, 1, 8, 11, false>), NT, 512, 0, s, a);
-        else if (T == 32 && q8_tiles_over_grid()) MMI_LAUNCH((k_gemm_q8<32, 1, 8, 11, false>), dim3(NT, mt), 512, 0, s, a);
+        else if (T == 32 && tiles_over_grid) MMI_LAUNCH((k_gemm_q8<32, 1, 8, 11, false>), dim3(NT, mt), 512, 0, s, a);
         else if (T == 32) MMI_LAUNCH((k_gemm_q8<32, 2, 8, 11, false>), NT, 512, 0, s, a);
         else MMI_LAUNCH((k_gemm_q8<16, 1, 8, 11, false>), NT, 512, 0, s, a);
     }
@@ -704,9 +697,9 @@ int launch_q8_fused(hipStream_t s, int T, int mt, int kmax, int NT, const GemmAr
     return (int)MMI_OK;
 }
 static int q8_fused_kmax(const GemmW& g) { return g.KSTEPS <= 32 ? 4 : (g.KSTEPS <= 88 ? 11 : 0); }
-static int q8_fused_osplit(const GemmW& g, int epi, int T) {
+static int q8_fused_osplit(const MmiKnobs& k, const GemmW& g, int epi, int T) {
     int os = 1;
-    if (epi != MMI_EPI_GATE && !getenv("MMI_GEMM_OSPLIT")) {
+    if (epi != MMI_EPI_GATE && !k.gemm_osplit_set) {
         const int octs = T / 8;
         while (os < octs && (long)g.NT * os < 128) os *= 2;
         if (g.NT > 64) os = 1;
@@ -721,7 +714,7 @@ void add_norm_gemm(mmi_lm* lm, const GemmW& g, uint16_t* x, const uint16_t* alph
                    int out_features, bool out_packed, int epi, const DepKv* kv = nullptr) {
     const bool a8 = lm->act8 && g.wq == 1;
     const int wq = a8 ? 3 : g.wq;
-    const bool fuse = g.KSTEPS <= (wq ? 32 : 64) && !getenv("MMI_NO_NORM_FUSION");
+    const bool fuse = g.KSTEPS <= (wq ? 32 : 64) && !lm->knobs.no_norm_fusion;
     if (!fuse) {
         if (a8) {
             add_resid_rmsnorm(lm, x, Pending{}, alpha, xn_scratch, D, lm->dxnq, lm->sx_dxn, g.T);
@@ -747,9 +740,10 @@ void add_norm_gemm(mmi_lm* lm, const GemmW& g, uint16_t* x, const uint16_t* alph
     a.osplit = 1;
     const int T = g.T, mt = mmi_cdiv(lm->batch, g.T), NT = g.NT * (a.osplit > 1 ? a.osplit : 1);
     const long gbytes = (long)g.bytes;
+    const bool over_grid = !lm->knobs.q8_tiles_serial;
     lm->prog.add([=](hipStream_t s) {
         mmi_record_bytes(gbytes);
-        return launch_norm_fused(s, T, mt, wq, NT, a);
+        return launch_norm_fused(s, T, mt, wq, NT, over_grid, a);
     }, gbytes);
 }
 
@@ -772,7 +766,7 @@ void add_q8_gemm(mmi_lm* lm, const GemmW& g, const uint16_t* x, int in_features,
                  const uint16_t* resid) {
     const int T = g.T, mt = mmi_cdiv(lm->batch, g.T);
     const int kmax = q8_fused_kmax(g);
-    if (!kmax || getenv("MMI_NO_NORM_FUSION")) {
+    if (!kmax || lm->knobs.no_norm_fusion) {
         add_quant_rows(lm, x, lm->hbq, lm->sx_hb, in_features, g.T);
         Q8 q{3, lm->sx_hb};
         add_gemm(lm, g, reinterpret_cast<const uint16_t*>(lm->hbq), out, out_features, out_packed, epi, resid, nullptr, nullptr, 0, false, nullptr, &q);
@@ -789,12 +783,13 @@ void add_q8_gemm(mmi_lm* lm, const GemmW& g, const uint16_t* x, int in_features,
     a.wq = 3; a.xinv = g.xinv;
     // few n-tiles (the N = 1024 linears: 32 tiles for 256 CUs): share a tile's row octets out over several workgroups, as
     // plan_osplit does for the bf16 form of these GEMMs
-    a.osplit = q8_fused_osplit(g, epi, T);
+    a.osplit = q8_fused_osplit(lm->knobs, g, epi, T);
     const int NT = g.NT * a.osplit;
     const long gbytes = (long)g.bytes;
+    const bool over_grid = !lm->knobs.q8_tiles_serial;
     lm->prog.add([=](hipStream_t s) {
         mmi_record_bytes(gbytes);
-        return launch_q8_fused(s, T, mt, kmax, NT, a);
+        return launch_q8_fused(s, T, mt, kmax, NT, over_grid, a);
     }, gbytes);
 }
 
@@ -844,23 +839,17 @@ void add_sample(mmi_lm* lm, uint16_t* logits, int ld, int V, bool text, int site
     });
 }
 
-// MMI_ATTN: "wave" (default since round 4) = k_lm_attn_wave, one online softmax per wave, no barrier in the loop; "split" = the
-// chunked kernel of rounds 1-3 (same-box A/Bs)
-static bool attn_wave_kernel() {
-    const char* e = getenv("MMI_ATTN");
-    return !(e && e[0] == 's');
-}
+// the default since round 4: k_lm_attn_wave, one online softmax per wave, no barrier in the loop; knobs.attn_split = the chunked
+// kernel of rounds 1-3 (same-box A/Bs)
+static bool attn_wave_kernel(const MmiKnobs& k) { return !k.attn_split; }
 
 // workgroups per (session, head) of the decode attention.  k_lm_attn_wave: ONE from 128 pairs (4 sessions) on - one workgroup per
 // pair walking the whole ring beats ring split + merge launch at every depth there (4 / 8 / 16 sessions, 3000 rows: -0.03 / -0.16 /
 // -0.16 ms per step, profiles/r04_logs/call_v_summary.txt); below that the ring is split (and still walked by one workgroup while
 // it is short: attn_solo_rows).  The chunked kernel of rounds 1-3: 1 once B*H alone fills the chip.
-int attn_splits(const mmi_lm_cfg& c, int B) {
-    if (const char* e = getenv("MMI_ATTN_NS")) {          // test hook: the split + combine path on rings too short to need it
-        const int v = atoi(e);
-        if (v >= 1 && v <= 16) return v;
-    }
-    if (attn_wave_kernel() && B * c.num_heads >= 128) return 1;
+int attn_splits(const MmiKnobs& k, const mmi_lm_cfg& c, int B) {
+    if (k.attn_ns) return k.attn_ns;                      // test hook: the split + combine path on rings too short to need it
+    if (attn_wave_kernel(k) && B * c.num_heads >= 128) return 1;
     const int chunks = mmi_cdiv(c.context, MMI_ATTN_CHUNK);
     int want = 1024 / (B * c.num_heads);
     if (want < 1) want = 1;
@@ -869,9 +858,9 @@ int attn_splits(const mmi_lm_cfg& c, int B) {
 
 // k_lm_attn_wave, ring split over several workgroups: up to this many rows, workgroup 0 walks the ring alone and writes the output
 // itself.  Measured crossover against split + merge launch (profiles/r04_logs/call_u_summary.txt, call_v_summary.txt): one session
-// between 600 and 900 rows, two sessions between 600 and 1800.  MMI_ATTN_SOLO: test hook (0 = always the merge launch)
-static int attn_solo_rows(int pairs) {
-    if (const char* e = getenv("MMI_ATTN_SOLO")) return atoi(e);
+// between 600 and 900 rows, two sessions between 600 and 1800.  knobs.attn_solo: test hook (0 = always the merge launch)
+static int attn_solo_rows(const MmiKnobs& k, int pairs) {
+    if (k.attn_solo != MmiKnobs::UNSET) return k.attn_solo;
     return pairs <= 32 ? 768 : 1200;
 }
 
@@ -881,16 +870,15 @@ static int attn_solo_rows(int pairs) {
 //      4.7 ms single-session step.  (Should a ring be longer all the same, the kernel merges in its last-arriving workgroup:
 //      correct whatever the host believes, 8 us per layer slower than a launch - measured, profiles/r04_logs/call_j_summary.txt)
 //   1  deeper rings: partials from every workgroup + the k_lm_attn_combine launch, as in rounds 1-3.
-// MMI_ATTN_MERGE=kernel (test hook) stays on variant 0 whatever the depth.
+// knobs.attn_merge_kernel (test hook) stays on variant 0 whatever the depth.
 static int attn_variant(const mmi_lm* lm, int NS) {
-    if (NS <= 1 || !attn_wave_kernel()) return 0;
-    if (const char* e = getenv("MMI_ATTN_MERGE")) if (e[0] == 'k') return 0;
-    return lm->depth_bound + 1 > (long)attn_solo_rows(lm->batch * lm->cfg.num_heads) ? 1 : 0;
+    if (NS <= 1 || !attn_wave_kernel(lm->knobs) || lm->knobs.attn_merge_kernel) return 0;
+    return lm->depth_bound + 1 > (long)attn_solo_rows(lm->knobs, lm->batch * lm->cfg.num_heads) ? 1 : 0;
 }
 
-int launch_attn_split(hipStream_t s, const LmAttnArgs& a, bool kv8) {
+int launch_attn_split(hipStream_t s, const LmAttnArgs& a, bool kv8, bool wave) {
     dim3 grid(a.B * a.H, a.NS);
-    if (attn_wave_kernel()) {
+    if (wave) {
         if (kv8) {
             switch (a.Dh) {
                 case 128: MMI_LAUNCH((k_lm_attn_wave<128, true>), grid, 256, 0, s, a); break;
@@ -969,7 +957,7 @@ int build_program(mmi_lm* lm) {
         });
     }
     // ---- temporal transformer
-    const int NS = attn_splits(c, B);
+    const int NS = attn_splits(lm->knobs, c, B);
     lm->attn_ns = NS;
     const bool kv8 = c.kv_cache_dtype == MMI_F8E4M3;
     const size_t kv_layer = (size_t)B * H * c.context * Dh / (kv8 ? 2 : 1);     // in uint16 units: an fp8 ring is half as large
@@ -984,7 +972,7 @@ int build_program(mmi_lm* lm) {
         a.offsets = lm->offsets_m; a.opart = lm->opart; a.ml = lm->ml; a.out = lm->att;
         a.B = B; a.H = H; a.Dh = Dh; a.cap = c.context; a.context = c.context; a.NS = NS; a.max_period = c.max_period;
         a.T = lm->T; a.out_ksteps = packed_ksteps(lm, d);
-        a.done = lm->attn_done; a.solo_rows = attn_solo_rows(B * H);
+        a.done = lm->attn_done; a.solo_rows = attn_solo_rows(lm->knobs, B * H);
         P.site("L.in_proj");
         {   // in_proj with RoPE + ring-KV write in its epilogue
             GemmArgs ga;
@@ -997,11 +985,12 @@ int build_program(mmi_lm* lm) {
             P.add([lm, gw, ga](hipStream_t s) { return launch_gemm(lm, s, gw, ga, false); }, (long)gw.bytes);
         }
         P.site("L.attn");
+        const bool wave = attn_wave_kernel(lm->knobs);
         P.add([=](hipStream_t s) {
             LmAttnArgs aa = a;
-            const bool merge_launch = a.NS > 1 && (!attn_wave_kernel() || lm->prog.variant == 1);
+            const bool merge_launch = a.NS > 1 && (!wave || lm->prog.variant == 1);
             if (merge_launch) { aa.solo_rows = -1; aa.done = nullptr; }     // every workgroup leaves its partial (m, l, O)
-            int rc = launch_attn_split(s, aa, kv8);
+            int rc = launch_attn_split(s, aa, kv8, wave);
             if (rc) return rc;
             if (merge_launch) MMI_LAUNCH(k_lm_attn_combine, B * H, Dh < 64 ? 64 : Dh, 0, s, aa);
             MMI_CHECK_LAUNCH();
@@ -1110,8 +1099,8 @@ int build_program(mmi_lm* lm) {
             P.site("dep.in_proj");
             // micro-step 0 attends to one position: softmax over one score is 1 and the attention output is v itself, so in_proj's
             // epilogue writes k / v into the frame's cache and v as out_proj's operand, and the attention launch is dropped
-            // (bit-identical: 1 * v / 1; MMI_DEP_ATTN0_LAUNCH=1 keeps the launch)
-            const bool skip_attn0 = k == 0 && Dhd % 8 == 0 && !getenv("MMI_DEP_ATTN0_LAUNCH");
+            // (bit-identical: 1 * v / 1; knobs.dep_attn0_launch keeps the launch)
+            const bool skip_attn0 = k == 0 && Dhd % 8 == 0 && !lm->knobs.dep_attn0_launch;
             if (skip_attn0) {
                 DepKv kv{lm->dkc + l * dkv_layer, lm->dvc + l * dkv_layer, Hd, Dhd, c.dep_q};
                 add_norm_gemm(lm, L.in_proj[k], lm->dx, L.n1, lm->dxn, dd, lm->datt, dd, true, MMI_EPI_DEP_QKV0, &kv);
@@ -1256,6 +1245,7 @@ extern "C" int mmi_lm_create(const mmi_lm_cfg* cfg, const mmi_tensor_desc* weigh
 
 extern "C" int mmi_lm_create_ext(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ext, const mmi_tensor_desc* weights, int32_t n_weights,
                                  int32_t max_batch, mmi_lm** out) {
+    const MmiKnobs knobs = mmi_knobs_from_env();     // the handle's one reading of the environment
     if (!cfg || !weights || !out || max_batch <= 0) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_create: bad argument");
     if (max_batch > 64) return mmi_fail(MMI_ERR_UNSUPPORTED, "max_batch > 64 sessions per GPU is not supported yet");
     mmi_lm_cfg norm_cfg = *cfg;
@@ -1290,6 +1280,9 @@ extern "C" int mmi_lm_create_ext(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ex
     if (low_rank < 0 || low_rank % 8) return mmi_fail(MMI_ERR_INVALID, "depformer_low_rank_embeddings must be a multiple of 8");
     const bool demux = x.demux_second_text_stream != 0;
     mmi_lm* lm = new mmi_lm();
+    lm->knobs = knobs;
+    lm->wts.poison = lm->st.poison = knobs.debug_poison;
+    lm->prog.skip = knobs.skip_sites;
     lm->dep_sched = sched;
     lm->dep_nw = nw;
     lm->demux = demux;
@@ -1297,11 +1290,8 @@ extern "C" int mmi_lm_create_ext(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ex
     lm->cfg = norm_cfg;
     lm->max_batch = max_batch;
     lm->T = max_batch <= 16 ? 16 : 32;
-    if (const char* e = getenv("MMI_LM_TILE")) {      // A/B hook: the 32-row tile (and with it k_gemm_xlds / the octet sharing) at small batches
-        const int v = atoi(e);
-        if (v == 32 || (v == 16 && max_batch <= 16)) lm->T = v;
-    }
-    lm->use_graph = mmi_graphs_enabled();
+    if (knobs.lm_tile == 32 || (knobs.lm_tile == 16 && max_batch <= 16)) lm->T = knobs.lm_tile;     // A/B hook: the 32-row tile at small batches
+    lm->use_graph = !knobs.no_graph;
     const mmi_lm_cfg& c = lm->cfg;
     lm->NC = c.n_q + 1;
     lm->max_delay = 0;
@@ -1380,7 +1370,7 @@ extern "C" int mmi_lm_create_ext(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ex
     {
         // depformer_in[k] all read transformer_out, so they are packed back to back and run as ONE GEMM with
         // dep_q * depformer_dim output features ahead of the micro-step loop (build_program).  Needs whole n-tiles per step.
-        const bool group = c.dep_q > 0 && dd % lm->T == 0 && !getenv("MMI_NO_DEP_IN_GROUP");
+        const bool group = c.dep_q > 0 && dd % lm->T == 0 && !knobs.no_dep_in_group;
         uint8_t* wp_all = nullptr;
         float *scale_all = nullptr, *scb_all = nullptr;
         size_t per = 0;
@@ -1420,10 +1410,7 @@ extern "C" int mmi_lm_create_ext(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ex
     // (its row-major output is the boundary between the two tiles) and bf16 weights (the int8 / fp8 forms of the 16-row kernels
     // are instantiated for one batch tile only)
     lm->Td = lm->T;
-    {
-        const char* e = getenv("MMI_DEP_TILE");
-        if (lm->T == 32 && max_batch <= 32 && lm->q8 == 0 && lm->dep_in_grouped && dd % 16 == 0 && e && atoi(e) == 16) lm->Td = 16;
-    }
+    if (lm->T == 32 && max_batch <= 32 && lm->q8 == 0 && lm->dep_in_grouped && dd % 16 == 0 && knobs.dep_tile == 16) lm->Td = 16;
     const int Td = lm->Td;
     for (int k = 0; k < c.dep_q; ++k)
         if ((rc = load_linear(lm, W, "linears." + std::to_string(k) + ".weight", c.card, dd, 0, &lm->dep_lin[k], nullptr, nullptr, nullptr, Td))) return fail(rc);
@@ -1509,7 +1496,7 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
     lm->precapture_failed = false;
     const int G = batch;
     const int B = rows, d = c.dim, H = c.num_heads, Dh = d / H, dd = c.depformer_dim, Hd = c.depformer_num_heads, Dhd = dd / Hd;
-    const int NS = attn_splits(c, B);
+    const int NS = attn_splits(lm->knobs, c, B);
     auto fail = [&](int code) { lm->streaming = true; mmi_lm_streaming_stop(lm); return code; };
     MmiArena& A = lm->st;
     const size_t kvn = (size_t)c.num_layers * B * H * c.context * Dh / (c.kv_cache_dtype == MMI_F8E4M3 ? 2 : 1);   // uint16 units
@@ -1554,8 +1541,7 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
     lm->htap = nullptr;
     if (lm->hidden_taps) ok &= hipSuccess == A.alloc(&lm->htap, (size_t)2 * B * d);
     {   // int8 activations (see mmi_lm::act8)
-        const char* e8 = getenv("MMI_Q8_ACT");
-        lm->act8 = lm->q8 == 1 && !c.cross_attention && !(e8 && e8[0] == 'b');
+        lm->act8 = act8_of(lm);
         lm->xnq = lm->attq = lm->hbq = lm->toutq = lm->dxnq = nullptr;
         lm->sx_xn = lm->sx_tout = lm->sx_dxn = lm->sx_att = lm->sx_hb = nullptr;
         if (lm->act8) {
@@ -1632,9 +1618,9 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
     rc = build_program(lm);
     if (rc) return fail(rc);
     MMI_HIP_CHECK(hipStreamSynchronize(s));
-    if (const char* tp = getenv("MMI_DEBUG_TRACE")) {
+    if (lm->knobs.debug_trace) {
         static int session = 0;
-        lm->trace_name = std::string(tp) + "." + std::to_string(session++);
+        lm->trace_name = lm->knobs.debug_trace_prefix + "." + std::to_string(session++);
         lm->trace_file = fopen(lm->trace_name.c_str(), "w");
         lm->trace_prev.assign(lm->st.ptrs.size(), 0ull);
         lm->trace_step = 0;
@@ -1737,8 +1723,8 @@ extern "C" int mmi_lm_step(mmi_lm* lm, const int64_t* user_codes, int32_t n_user
                 if (now[a] != lm->trace_prev[a])
                     fprintf(lm->trace_file, "%ld %zu %s %zu %zu %016llx\n", lm->trace_step, i, lm->prog.sites[i].c_str(), a, lm->st.sizes[a], now[a]);
             lm->trace_prev = now;
-            // MMI_DEBUG_DUMP="step:op:alloc[,alloc...]": those allocations, as they are after that op, to <prefix>.<session>.a<alloc>
-            if (const char* dd = getenv("MMI_DEBUG_DUMP")) {
+            // knobs.debug_dump = "step:op:alloc[,alloc...]": those allocations, as they are after that op, to <prefix>.<session>.a<alloc>
+            if (const char* dd = lm->knobs.debug_dump.empty() ? nullptr : lm->knobs.debug_dump.c_str()) {
                 long ds = -1, dop = -1;
                 int used = 0;
                 if (sscanf(dd, "%ld:%ld:%n", &ds, &dop, &used) >= 2 && ds == lm->trace_step && dop == (long)i) {
@@ -1765,7 +1751,7 @@ extern "C" int mmi_lm_step(mmi_lm* lm, const int64_t* user_codes, int32_t n_user
         });
     } else rc = lm->prog.run(s, lm->use_graph && !lm->profiling, lm->cap_stream);
     if (rc) return rc;
-    if (lm->attn_ns > 1 && lm->use_graph && !lm->profiling && !hooked && attn_wave_kernel() && !getenv("MMI_NO_PRECAPTURE")) {
+    if (lm->attn_ns > 1 && lm->use_graph && !lm->profiling && !hooked && attn_wave_kernel(lm->knobs) && !lm->knobs.no_precapture) {
         // both attention programs exist from the stream's first step on: the switch at depth solo_rows is then a graph launch
         // like any other (without this the deep program was captured + instantiated ~61 s into a live single-session stream)
         // The step above is already committed: a failure to capture the OTHER program (out of memory at instantiate, ...) must not
@@ -1986,8 +1972,7 @@ extern "C" int mmi_lm_debug_linear(mmi_lm* lm, const char* weight_name, const ch
         if (ia == lm->vector_by_name.end()) return mmi_fail(MMI_ERR_MISSING_WEIGHT, "mmi_lm_debug_linear: the norm's alpha vector was not found");
         alpha = ia->second;
     }
-    const char* e8 = getenv("MMI_Q8_ACT");
-    const bool a8 = lm->q8 == 1 && !lm->cfg.cross_attention && !(e8 && e8[0] == 'b');
+    const bool a8 = act8_of(lm);
     if ((codes || absmax) && !(a8 && (path == MMI_DBG_PLAIN || path == MMI_DBG_SPLITK || path == MMI_DBG_NORM)))
         return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_linear: codes / absmax exist on the int8 x int8 paths that materialise the operand (plain, split-K, norm)");
     hipStream_t s = (hipStream_t)stream;
@@ -1995,6 +1980,7 @@ extern "C" int mmi_lm_debug_linear(mmi_lm* lm, const char* weight_name, const ch
     const int K = g.K, N = g.N, kin = packed_ksteps_t(lm, T, K), kout = packed_ksteps_t(lm, T, N);
     const int nthK = [&] { int n = mmi_cdiv(K / 8, 64) * 64; return n > 1024 ? 1024 : n; }();
     MmiArena A;
+    A.poison = lm->knobs.debug_poison;
     uint16_t *xp = nullptr, *yp = nullptr, *xres = nullptr, *zeros = nullptr, *outp = (uint16_t*)out_bf16;
     uint8_t* xq = nullptr;
     float *sx = nullptr, *partial = nullptr;
@@ -2039,7 +2025,7 @@ extern "C" int mmi_lm_debug_linear(mmi_lm* lm, const char* weight_name, const ch
         if (a8) { a.xp = reinterpret_cast<const u32x4*>(xq); a.sx = sx; a.wq = 3; }
         Pending pd;
         if (path == MMI_DBG_SPLITK) {
-            const GemmPlan p = plan_gemm(g, true);
+            const GemmPlan p = plan_gemm(lm->knobs, g, true);
             if (gated || p.ksplit <= 1) return done(mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_linear: the engine does not split this GEMM over K"));
             a.epi = MMI_EPI_PARTIAL; a.partial = partial; a.out = nullptr;
             pd.P = p.ksplit;
@@ -2063,8 +2049,8 @@ extern "C" int mmi_lm_debug_linear(mmi_lm* lm, const char* weight_name, const ch
         a.xp = reinterpret_cast<const u32x4*>(xp);
         a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT; a.wscale = g.scale; a.wscb = g.scb; a.gate_rows = gated ? g.N : 0;
         a.wq = 3; a.xinv = g.xinv;
-        a.osplit = q8_fused_osplit(g, a.epi, T);
-        rc = launch_q8_fused(s, T, mt, kmax, g.NT * a.osplit, a);
+        a.osplit = q8_fused_osplit(lm->knobs, g, a.epi, T);
+        rc = launch_q8_fused(s, T, mt, kmax, g.NT * a.osplit, !lm->knobs.q8_tiles_serial, a);
         if (rc) return done(rc);
     } else if (path == MMI_DBG_NORM_FUSED) {
         const int wq = (a8 && g.wq == 1) ? 3 : g.wq;
@@ -2073,7 +2059,7 @@ extern "C" int mmi_lm_debug_linear(mmi_lm* lm, const char* weight_name, const ch
         a.alpha = alpha; a.D = K; a.eps = 1e-8f;
         a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT; a.wscale = g.scale; a.wscb = g.scb; a.gate_rows = gated ? g.N : 0;
         a.wq = wq; a.xinv = g.xinv; a.osplit = 1;
-        rc = launch_norm_fused(s, T, mt, wq, g.NT, a);
+        rc = launch_norm_fused(s, T, mt, wq, g.NT, !lm->knobs.q8_tiles_serial, a);
         if (rc) return done(rc);
     } else {
         return done(mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_linear: unknown path"));

@@ -35,6 +35,7 @@ struct Buf {            // activation buffer [B][C][ld]; first H columns = causa
 }  // namespace
 
 struct mmi_mimi {
+    MmiKnobs knobs;                 // the MMI_* environment as it was when the handle was created (mmi_knobs.h)
     int device = -1;                // HIP device the handle lives on (current at create); see MmiDeviceGuard
     int* dec_k_dev = nullptr;       // number of codebooks of the current decode call (read by the captured decoder program)
     int dec_k_host = 0, dec_k_cur = 0;
@@ -322,7 +323,7 @@ int launch_conv_plan(hipStream_t s, const ConvGemmArgs& a, const ConvPlan& p) {
 
 // Decide the launch sequence of one conv and allocate its scratch (offset table / packed operand / partials) from
 // `arena`.  `a.x_packed`: the producer writes a.bp itself.  `a.out_mode` PACKED: the result feeds a linear directly.
-int plan_conv(MmiArena& arena, ConvGemmArgs& a, ConvPlan* p) {
+int plan_conv(const MmiKnobs& k, MmiArena& arena, ConvGemmArgs& a, ConvPlan* p) {
     const int N = a.Ntot;
     if (a.Cin * a.K >= (1 << 17) || N >= (1 << 17) || a.T_out >= (1 << 11) || a.K >= (1 << 11))
         return mmi_fail(MMI_ERR_UNSUPPORTED, "conv dimensions outside the range of the kernels' index arithmetic (sessions x samples per frame "
@@ -383,8 +384,8 @@ int plan_conv(MmiArena& arena, ConvGemmArgs& a, ConvPlan* p) {
                         break;
                     }
         }
-        if (const char* e = getenv("MMI_CONV_MTB")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) MTB = v; }   // test hooks
-        if (const char* e = getenv("MMI_CONV_W")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4 || v == 8) W = v; }
+        if (k.conv_mtb) MTB = k.conv_mtb;      // test hooks
+        if (k.conv_w) W = k.conv_w;
         while (W * MTB > 16) W >>= 1;          // split-K reduction buffer: W * MTB * 4 KiB of LDS, keep it within 64 KiB
         p->MTB = MTB; p->W = W;
         std::vector<int> tab((size_t)a.Q * 8);
@@ -428,10 +429,7 @@ int plan_conv(MmiArena& arena, ConvGemmArgs& a, ConvPlan* p) {
         // only the large strided convs (>= 2048-deep reductions, tens of MB of weights) are worth a finishing launch
         while (a.Q >= 256 && ks < 8 && a.Mt * ks * 2 <= 256 && a.Q / (ks * 2) >= 32) ks <<= 1;
     }
-    if (const char* e = getenv("MMI_CONV_KSPLIT")) {   // test hook
-        const int v = atoi(e);
-        if (a.out_mode == MMI_GOUT_NATURAL && v >= 1 && v <= 8 && a.Q >= v) ks = v;
-    }
+    if (k.conv_ksplit && a.out_mode == MMI_GOUT_NATURAL && a.Q >= k.conv_ksplit) ks = k.conv_ksplit;   // test hook
     p->ksplit = ks;
     if (ks > 1 && !a.partial) {
         float* part = nullptr;
@@ -473,10 +471,10 @@ ConvGemmArgs conv_args(const ConvW& w, const Buf& in, int x_off, int T_out, cons
 // `lead` floats so that the T NEW columns of every row start on a 128-byte line (the H history columns sit right in front of
 // them).  A 32-column tile of a conv's output is then exactly one cache line per row: consecutive workgroups run on different
 // XCDs (different L2s), and with rows starting at arbitrary 8-byte offsets every line was written in part by two of them.
-// MMI_MIMI_NO_ALIGN=1 keeps the dense layout (A/B).  Nothing else knows: every kernel takes (pointer, row stride, H).
+// knobs.mimi_no_align keeps the dense layout (A/B).  Nothing else knows: every kernel takes (pointer, row stride, H).
 int alloc_buf(mmi_mimi* m, int B, int C, int H, int T, Buf* b, hipStream_t s) {
     b->C = C; b->H = H; b->ld = H + T; b->lead = 0;
-    if (T >= 32 && !getenv("MMI_MIMI_NO_ALIGN")) {
+    if (T >= 32 && !m->knobs.mimi_no_align) {
         b->lead = (32 - H % 32) % 32;
         b->ld = ((b->lead + H + T + 31) / 32) * 32;
     }
@@ -506,9 +504,15 @@ HistDesc hist_of_src(const Buf& b, int T) {
     return hist_of(c, T);
 }
 
+// The producer of a k_gemm_f32 operand of <= 128 columns also stores it in the packed order the GEMM of `w` reads (`features` = its
+// reduction length, whole octets): no k_pack_b_f32 launch in front of that GEMM.  knobs.mimi_pack_launches keeps the launch
+bool producer_packs(const mmi_mimi* m, int columns, const ConvW& w, int features) {
+    return columns <= 128 && w.Q * 8 == features && !m->knobs.mimi_pack_launches;
+}
+
 int add_conv(mmi_mimi* m, MmiProgram& prog, ConvGemmArgs a, MmiArena* arena = nullptr) {
     ConvPlan p;
-    int rc = plan_conv(arena ? *arena : m->st, a, &p);
+    int rc = plan_conv(m->knobs, arena ? *arena : m->st, a, &p);
     if (rc) return rc;
     prog.add([a, p](hipStream_t s) { return launch_conv_plan(s, a, p); });
     return MMI_OK;
@@ -518,8 +522,8 @@ int add_conv(mmi_mimi* m, MmiProgram& prog, ConvGemmArgs a, MmiArena* arena = nu
 // has the shape the kernel is built for and enough columns to fill the chip with 32-column workgroups; else the two convs.
 int add_resblock(mmi_mimi* m, MmiProgram& prog, ConvGemmArgs a1, ConvGemmArgs a2, const ConvW& w2) {
     const int nblk = mmi_cdiv(a1.Ntot, 32);
-    long min_waves = 256;                        // below that the two-launch path (split-K over waves) fills the chip better
-    if (const char* e = getenv("MMI_MIMI_RES_FUSION_MIN")) min_waves = atol(e);      // test hook: the tiny shapes
+    // below 256 waves the two-launch path (split-K over waves) fills the chip better (knobs.res_fusion_min: test hook, the tiny shapes)
+    const long min_waves = m->knobs.res_fusion_min != MmiKnobs::UNSET ? m->knobs.res_fusion_min : 256;
     // Measured on MI355X (profiles/r02_logs/resblock_*): the 64-channel blocks (one hidden tile, 1920 one-wave workgroups) gain
     // 8-13 us each over two launches; the 128 / 256-channel blocks (480 / 96 workgroups of 2 / 4 waves: one wave per SIMD on part of
     // the chip) lost 2-15 us to the two-launch path's split-K over waves and are not instantiated.
@@ -579,7 +583,7 @@ int add_quantize_ops(mmi_mimi* m, MmiProgram& prog, const float* latent, int lat
     };
     int* codes = m->codes_i32; const int nq = c.q_n_q;
     // the semantic quantiser's single level and the first acoustic level share their two launches (independent, see RvqLevel)
-    const bool pair = c.q_n_q_semantic == 1 && K >= 2 && !getenv("MMI_RVQ_NO_PAIR");
+    const bool pair = c.q_n_q_semantic == 1 && K >= 2 && !m->knobs.rvq_no_pair;
     for (int k = 0; k < K; ++k) {
         const RvqLevel a0 = level(k, 0);
         const bool two = pair && k == 0;
@@ -603,7 +607,7 @@ int add_dequant_ops(mmi_mimi* m, MmiProgram& prog, int K, const Buf& out, int ou
     const mmi_mimi_cfg& c = m->cfg;
     const int D = c.q_dimension, bins = c.q_bins, nq = c.q_n_q, nsem = c.q_n_q_semantic;
     float* q2 = m->q2; const int* codes = m->dec_codes_i32; const float* E = m->E_all; const int* kdev = k_from_device ? m->dec_k_dev : nullptr;
-    const bool packed = B <= 128 && m->q_out.Q * 8 == 2 * D && !getenv("MMI_MIMI_PACK_LAUNCHES");
+    const bool packed = producer_packs(m, B, m->q_out, 2 * D);
     float* qp = packed ? m->qout_bp : nullptr; const int qQ = m->q_out.Q;
     prog.add([=](hipStream_t s) {
         MMI_LAUNCH(k_rvq_gather, mmi_cdiv(B * D, 256), 256, 0, s, codes, nq, K, E, bins, D, nsem, q2, B, kdev, qp, qQ);
@@ -682,7 +686,7 @@ int add_transformer(mmi_mimi* m, MmiProgram& prog, const std::vector<TrLayerW>& 
             aa.context = c.tr_context; aa.max_period = c.tr_max_period;
             aa.outp = attp; aa.outQ = Qd;
             // one memory round trip when a thread's 16 row slots cover the ring (the Mimi shape: 250 slots of 64 floats)
-            const bool one_pass = cap <= 16 * (256 / (Dh / 4)) && !getenv("MMI_MIMI_ATTN_TWO_PASS");
+            const bool one_pass = cap <= 16 * (256 / (Dh / 4)) && !m->knobs.mimi_attn_two_pass;
             prog.add([=](hipStream_t s) {
 #define MMI_ATT(D_, T_) do { if (one_pass) MMI_LAUNCH((k_mimi_attn_1pass<D_, T_>), B * H, 256, 0, s, aa); \
                              else MMI_LAUNCH((k_mimi_attn<D_, T_>), B * H, 256, attn_smem, s, aa); } while (0)
@@ -750,6 +754,30 @@ HistDesc hist_of(const Buf& b, int T) {
     HistDesc d;
     d.p = b.p; d.C = b.C; d.ld = b.ld; d.H = b.H; d.T = T; d.row_begin = 0;
     return d;
+}
+
+// the frame's last op: the histories of `hist` shifted by the frame's new columns and the transformer offsets `cnt` advanced by T_tr,
+// for the sessions of the exec mask (first: the encoder's replicate-padding flags, cleared) - one launch when the table fits by value
+int add_commit(mmi_mimi* m, MmiProgram& prog, std::vector<HistDesc>& hist, int B, int T_tr, HistDesc** dev, int* n, int* n_rows, long* cnt,
+               uint8_t* fi) {
+    HistTable tab;
+    int rc = upload_hist(m, hist, B, dev, n, n_rows, &tab);
+    if (rc) return rc;
+    HistDesc* hd = *dev; const int nh = *n, rows = *n_rows;
+    const uint8_t* ex = m->exec;
+    const bool one = tab.n >= 0 && !m->knobs.mimi_two_commits;
+    prog.add([=](hipStream_t s) {
+        if (one) {
+            MMI_LAUNCH(k_commit_all, mmi_cdiv(rows + B, 256), 256, 0, s, tab, rows, ex, cnt, 1, T_tr, fi, B);
+            MMI_CHECK_LAUNCH();
+            return (int)MMI_OK;
+        }
+        if (rows > 0) MMI_LAUNCH(k_commit_history, mmi_cdiv(rows, 256), 256, 0, s, (const HistDesc*)hd, nh, rows, ex);
+        MMI_LAUNCH(k_commit_counters, mmi_cdiv(B, 64), 64, 0, s, cnt, 1, T_tr, fi, ex, B);
+        MMI_CHECK_LAUNCH();
+        return (int)MMI_OK;
+    });
+    return MMI_OK;
 }
 
 int build_encoder(mmi_mimi* m, int B, hipStream_t s0) {
@@ -826,7 +854,7 @@ int build_encoder(mmi_mimi* m, int B, hipStream_t s0) {
     if (T % stride != 0 || T / stride != 1)
         return mmi_fail(MMI_ERR_UNSUPPORTED, "frame_size must map to exactly one latent column");
     if ((rc = alloc_buf(m, B, c.dimension, 0, 1, &m->latent, s0))) return rc;
-    const bool latent_packed = B <= 128 && m->q_in.Q * 8 == c.dimension && !getenv("MMI_MIMI_PACK_LAUNCHES");
+    const bool latent_packed = producer_packs(m, B, m->q_in, c.dimension);
     {
         ConvGemmArgs a = conv_args(m->downsample, dsin, 0, 1, m->latent, 0, B, false);
         a.first = m->first; a.exec = m->exec;
@@ -837,26 +865,7 @@ int build_encoder(mmi_mimi* m, int B, hipStream_t s0) {
     prog.site("enc.rvq");
     if ((rc = add_quantize_ops(m, prog, m->latent.p, 1, 0, B, latent_packed))) return rc;
     prog.site("enc.commit");
-    // commit
-    HistTable tab;
-    if ((rc = upload_hist(m, hist, B, &m->enc_hist, &m->enc_nhist, &m->enc_hist_rows, &tab))) return rc;
-    {
-        HistDesc* hd = m->enc_hist; int nh = m->enc_nhist, rows = m->enc_hist_rows;
-        const uint8_t* ex = m->exec; uint8_t* fi = m->first; long* cnt = m->counters;
-        const bool one = tab.n >= 0 && !getenv("MMI_MIMI_TWO_COMMITS");
-        prog.add([=](hipStream_t s) {
-            if (one) {
-                MMI_LAUNCH(k_commit_all, mmi_cdiv(rows + B, 256), 256, 0, s, tab, rows, ex, cnt, 1, T_tr, fi, B);
-                MMI_CHECK_LAUNCH();
-                return (int)MMI_OK;
-            }
-            if (rows > 0) MMI_LAUNCH(k_commit_history, mmi_cdiv(rows, 256), 256, 0, s, (const HistDesc*)hd, nh, rows, ex);
-            MMI_LAUNCH(k_commit_counters, mmi_cdiv(B, 64), 64, 0, s, cnt, 1, T_tr, fi, ex, B);
-            MMI_CHECK_LAUNCH();
-            return (int)MMI_OK;
-        });
-    }
-    return MMI_OK;
+    return add_commit(m, prog, hist, B, T_tr, &m->enc_hist, &m->enc_nhist, &m->enc_hist_rows, m->counters, m->first);
 }
 
 int build_decoder(mmi_mimi* m, int B, hipStream_t s0) {
@@ -910,7 +919,7 @@ int build_decoder(mmi_mimi* m, int B, hipStream_t s0) {
         ConvGemmArgs a0 = conv_args(m->dec_convs[ci++], din, 0, T, cur, 0, B, false);
         // its (ELU'd) output is read by the first transposed-conv GEMM only: stored as that GEMM's packed operand as well
         const ConvW& wtr0 = m->dec_convs[ci];
-        if (B * T <= 128 && wtr0.Q * 8 == mult * c.n_filters && !getenv("MMI_MIMI_PACK_LAUNCHES")) {
+        if (producer_packs(m, B * T, wtr0, mult * c.n_filters)) {
             MMI_HIP_CHECK(m->st.alloc(&conv0_bp, (size_t)mmi_cdiv(B * T, 32) * wtr0.Q * 256));
             MMI_HIP_CHECK(hipMemsetAsync(conv0_bp, 0, (size_t)mmi_cdiv(B * T, 32) * wtr0.Q * 256 * sizeof(float), s0));
             a0.outp = conv0_bp; a0.outQ = wtr0.Q;
@@ -972,25 +981,7 @@ int build_decoder(mmi_mimi* m, int B, hipStream_t s0) {
     prog.site("dec.final");
     if ((rc = add_conv(m, prog, conv_args(m->dec_convs[ci++], cur, 0, T, m->dec_out, 0, B, true)))) return rc;
     prog.site("dec.commit");
-    HistTable tab;
-    if ((rc = upload_hist(m, hist, B, &m->dec_hist, &m->dec_nhist, &m->dec_hist_rows, &tab))) return rc;
-    {
-        HistDesc* hd = m->dec_hist; int nh = m->dec_nhist, rows = m->dec_hist_rows;
-        const uint8_t* ex = m->exec; long* cnt = m->counters + B;
-        const bool one = tab.n >= 0 && !getenv("MMI_MIMI_TWO_COMMITS");
-        prog.add([=](hipStream_t s) {
-            if (one) {
-                MMI_LAUNCH(k_commit_all, mmi_cdiv(rows + B, 256), 256, 0, s, tab, rows, ex, cnt, 1, T_tr, (uint8_t*)nullptr, B);
-                MMI_CHECK_LAUNCH();
-                return (int)MMI_OK;
-            }
-            if (rows > 0) MMI_LAUNCH(k_commit_history, mmi_cdiv(rows, 256), 256, 0, s, (const HistDesc*)hd, nh, rows, ex);
-            MMI_LAUNCH(k_commit_counters, mmi_cdiv(B, 64), 64, 0, s, cnt, 1, T_tr, (uint8_t*)nullptr, ex, B);
-            MMI_CHECK_LAUNCH();
-            return (int)MMI_OK;
-        });
-    }
-    return MMI_OK;
+    return add_commit(m, prog, hist, B, T_tr, &m->dec_hist, &m->dec_nhist, &m->dec_hist_rows, m->counters + B, nullptr);
 }
 
 int check_cfg(const mmi_mimi_cfg& c) {
@@ -1024,15 +1015,19 @@ int frame_count_ok(const mmi_mimi* m, int batch, int n_frames) {
 // ===============================================================================================
 extern "C" int mmi_mimi_create(const mmi_mimi_cfg* cfg, const mmi_tensor_desc* weights, int32_t n_weights,
                                int32_t max_batch, mmi_mimi** out) {
+    const MmiKnobs knobs = mmi_knobs_from_env();     // the handle's one reading of the environment
     if (!cfg || !weights || !out || max_batch <= 0) return mmi_fail(MMI_ERR_INVALID, "mmi_mimi_create: bad argument");
     int rc = check_cfg(*cfg);
     if (rc) return rc;
     mmi_mimi* m = new mmi_mimi();
+    m->knobs = knobs;
+    m->wts.poison = m->st.poison = knobs.debug_poison;
+    m->enc_prog.skip = m->dec_prog.skip = knobs.skip_sites;
     if (hipGetDevice(&m->device) != hipSuccess) m->device = -1;
     m->cfg = *cfg;
     m->max_batch = max_batch;
     m->n_codebooks = cfg->q_n_q < 8 ? cfg->q_n_q : 8;
-    m->use_graph = mmi_graphs_enabled();
+    m->use_graph = !knobs.no_graph;
     MmiWeights W{weights, n_weights};
     const mmi_mimi_cfg& c = m->cfg;
     auto fail = [&](int code) { mmi_mimi_destroy(m); return code; };
@@ -1294,6 +1289,7 @@ extern "C" int mmi_mimi_quantize(mmi_mimi* m, const float* latent, int64_t* code
     const mmi_mimi_cfg& c = m->cfg;
     for (int f = 0; f < n_frames; ++f) {
         MmiProgram prog;
+        prog.skip = m->knobs.skip_sites;
         int rc = add_quantize_ops(m, prog, latent, n_frames, f, batch);
         if (rc) return rc;
         rc = prog.run_eager(s);
@@ -1318,6 +1314,7 @@ extern "C" int mmi_mimi_decode_latent(mmi_mimi* m, const int64_t* codes, float* 
         MMI_LAUNCH(k_codes_in, mmi_cdiv(batch * n_codebooks, 256), 256, 0, s, (const long*)codes, (long)n_codebooks * n_frames, m->dec_codes_i32,
                    c.q_n_q, batch, n_codebooks, n_frames, f);
         MmiProgram prog;
+        prog.skip = m->knobs.skip_sites;
         int rc = add_dequant_ops(m, prog, n_codebooks, out, f, batch);
         if (rc) return rc;
         rc = prog.run_eager(s);

@@ -2,6 +2,7 @@
 #pragma once
 #include <mmi_device.h>  // resolved through -I: csrc/ for the gfx950 build
 #include "../../include/moshi_mi.h"
+#include "mmi_knobs.h"
 
 #include <stdint.h>
 #include <stdlib.h>
@@ -80,6 +81,7 @@ struct MmiArena {
     std::vector<void*> ptrs;
     std::vector<size_t> sizes;
     size_t bytes = 0;
+    char poison = 0;            // MmiKnobs::debug_poison of the owning handle: '1' = every allocation starts as 0xFF bytes, '0' = as zeros
     template <class T>
     hipError_t alloc(T** p, size_t count) {
         void* q = nullptr;
@@ -87,13 +89,7 @@ struct MmiArena {
         if (nb == 0) nb = sizeof(T);
         hipError_t e = hipMalloc(&q, nb);
         if (e != hipSuccess) return e;
-        // MMI_DEBUG_POISON=1 (tests / scripts/gpu_check.sh): every allocation of a handle starts as 0xFF bytes (bf16 / fp32 NaNs,
-        // int -1) instead of whatever the allocator hands out, so that a read of state the engine never initialised shows up as
-        // a wrong result on every box, not only on the one whose memory happened to hold something else
-        // (MMI_DEBUG_POISON=0: zero-fill instead - two sessions then start from identical memory, which is what MMI_DEBUG_TRACE's
-        // per-op checksums need to be comparable line by line)
-        const char* pz = getenv("MMI_DEBUG_POISON");
-        if (pz && (pz[0] == '1' || pz[0] == '0') && (e = hipMemset(q, pz[0] == '1' ? 0xFF : 0x00, nb)) != hipSuccess) { hipFree(q); return e; }
+        if (poison && (e = hipMemset(q, poison == '1' ? 0xFF : 0x00, nb)) != hipSuccess) { hipFree(q); return e; }
         ptrs.push_back(q);
         sizes.push_back(nb);
         bytes += nb;

@@ -1,11 +1,10 @@
 // A frame step is a fixed list of kernel launches whose arguments never change between frames (every
 // varying quantity - offsets, masks, tokens - lives in device memory).  The list is captured once
 // into a hipGraph and replayed, which is what replaces the reference's CUDAGraphed wrappers
-// (utils/compile.py:190-280; compression.py:224-229; lm.py:630-632).  MMI_NO_GRAPH=1 runs the same
+// (utils/compile.py:190-280; compression.py:224-229; lm.py:630-632).  MmiKnobs::no_graph runs the same
 // list eagerly, mirroring the reference's NO_CUDA_GRAPH switch (utils/compile.py:169-175).
 #pragma once
 #include "mmi_common.h"
-#include <stdlib.h>
 
 // Launch-list recorder: while a program runs for the first time (eagerly, or under stream capture) every MMI_LAUNCH is
 // logged as "site<TAB>kernel", where the site is the label of the op that issued it ("L.ffn_in", "dep.out_proj", ...).
@@ -38,32 +37,26 @@ struct MmiProgram {
     hipGraphExec_t exec_a[NV] = {nullptr, nullptr}, exec_b[NV] = {nullptr, nullptr};
     size_t cut_[NV] = {0, 0};
 
+    std::vector<std::string> skip;              // MmiKnobs::skip_sites of the owning handle: ops under these site prefixes are not added.  How
+                                                // round 6 found which part of the codec stretches the depth-transformer phase under the
+                                                // duplex pipeline (profiles/r06_logs/pipeline_skip_sites.txt)
+
     void site(const std::string& label) { site_ = label; }
     void add(std::function<int(hipStream_t)> f, long bytes = 0) {
-        // MMI_SKIP_SITES="enc.tr,dec.res" (timing experiments ONLY - the outputs are then garbage): ops whose site label starts with
-        // one of the prefixes are left out of the list.  How round 6 found which part of the codec stretches the depth-transformer
-        // phase under the duplex pipeline (profiles/r06_logs/pipeline_skip_sites.txt)
-        if (const char* e = getenv("MMI_SKIP_SITES")) {
-            std::string all(e);
-            size_t i = 0;
-            while (i <= all.size()) {
-                const size_t j = all.find(',', i);
-                const std::string pre = all.substr(i, j == std::string::npos ? std::string::npos : j - i);
-                if (!pre.empty() && site_.compare(0, pre.size(), pre) == 0) return;
-                if (j == std::string::npos) break;
-                i = j + 1;
-            }
-        }
+        for (const std::string& pre : skip)
+            if (site_.compare(0, pre.size(), pre) == 0) return;
         ops.push_back(std::move(f)); sites.push_back(site_); op_bytes.push_back(bytes);
     }
     bool logged() const { return logged_[variant]; }
     const std::vector<std::string>& launch_log() const { return launch_logs[variant]; }
 
-    int run_eager(hipStream_t s) {
+    // every op launched eagerly; the variant's first run records its launch list.  between: enqueued on s in front of op `cut`
+    int run_eager(hipStream_t s, size_t cut = 0, const std::function<int(hipStream_t)>* between = nullptr) {
         const bool rec = !logged_[variant];
         if (rec) mmi_record_begin(&launch_logs[variant]);
         int rc = MMI_OK;
         for (size_t i = 0; i < ops.size() && !rc; ++i) {
+            if (between && i == cut && (rc = (*between)(s))) break;
             if (rec) mmi_record_site(sites[i].c_str());
             if (tap) tap(i, true, s);
             rc = ops[i](s);
@@ -80,62 +73,11 @@ struct MmiProgram {
         return rc;
     }
 
-    // the CURRENT variant's whole list captured into graph[v] / exec[v] (nothing executes; the first capture also records the launch list)
-    int capture_full(hipStream_t capture_stream) {
-        const int v = variant;
-        if (exec[v]) return MMI_OK;
+    // ops [i0, i1) of the CURRENT variant captured into *g / *e (nothing executes).  record: the whole list through run_eager,
+    // whose first capture also records the launch list
+    int capture_range(hipStream_t capture_stream, size_t i0, size_t i1, hipGraph_t* g, hipGraphExec_t* e, bool record = false) {
         MMI_HIP_CHECK(hipStreamBeginCapture(capture_stream, hipStreamCaptureModeThreadLocal));
-        int rc = run_eager(capture_stream);
-        hipError_t e = hipStreamEndCapture(capture_stream, &graph[v]);
-        if (rc || e != hipSuccess) {
-            if (e == hipSuccess && graph[v]) hipGraphDestroy(graph[v]);
-            graph[v] = nullptr;
-            if (rc) return rc;
-            return mmi_fail(MMI_ERR_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(e));
-        }
-        e = hipGraphInstantiate(&exec[v], graph[v], nullptr, nullptr, 0);
-        if (e != hipSuccess) {
-            hipGraphDestroy(graph[v]);
-            graph[v] = nullptr;
-            exec[v] = nullptr;
-            return mmi_fail(MMI_ERR_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
-        }
-        return MMI_OK;
-    }
-
-    int run(hipStream_t s, bool use_graph, hipStream_t capture_stream) {
-        if (!use_graph) return run_eager(s);
-        const int v = variant;
-        if (!exec[v]) {
-            int rc = capture_full(capture_stream);
-            if (rc) return rc;
-        }
-        MMI_HIP_CHECK(hipGraphLaunch(exec[v], s));
-        return MMI_OK;
-    }
-
-    // Variant v made ready AHEAD of the step that first needs it (ADVICE r4: a stream whose rings grow past the short-ring program
-    // would otherwise capture and instantiate the other program in the middle of a live session - a one-off latency spike in a
-    // real-time stream): its graph(s) captured and instantiated now, nothing launched.  split: the two-graph form run_split uses.
-    int precapture(int v, hipStream_t capture_stream, bool split, size_t cut) {
-        const int keep = variant;
-        variant = v;
-        int rc = MMI_OK;
-        if (!split || !logged_[v]) rc = capture_full(capture_stream);       // (also records the variant's launch list)
-        if (!rc && split && (!exec_a[v] || cut_[v] != cut)) {
-            drop_split(v);
-            if (!(rc = capture_range(capture_stream, 0, cut, &graph_a[v], &exec_a[v])) &&
-                !(rc = capture_range(capture_stream, cut, ops.size(), &graph_b[v], &exec_b[v])))
-                cut_[v] = cut;
-        }
-        variant = keep;
-        return rc;
-    }
-    bool ready(int v, bool split) const { return split ? (exec_a[v] && exec_b[v]) : exec[v] != nullptr; }
-
-    int capture_range(hipStream_t capture_stream, size_t i0, size_t i1, hipGraph_t* g, hipGraphExec_t* e) {
-        MMI_HIP_CHECK(hipStreamBeginCapture(capture_stream, hipStreamCaptureModeThreadLocal));
-        int rc = run_range(capture_stream, i0, i1);
+        int rc = record ? run_eager(capture_stream) : run_range(capture_stream, i0, i1);
         hipError_t err = hipStreamEndCapture(capture_stream, g);
         if (rc || err != hipSuccess) {          // an op failed while capturing: the half-built graph is not kept
             if (err == hipSuccess && *g) hipGraphDestroy(*g);
@@ -152,31 +94,52 @@ struct MmiProgram {
         }
         return MMI_OK;
     }
+    // the CURRENT variant's whole list captured into graph[v] / exec[v]
+    int capture_full(hipStream_t capture_stream) {
+        const int v = variant;
+        return exec[v] ? (int)MMI_OK : capture_range(capture_stream, 0, ops.size(), &graph[v], &exec[v], /*record=*/true);
+    }
+    // the two-graph form of the CURRENT variant: ops [0, cut) and [cut, end)
+    int capture_split(hipStream_t capture_stream, size_t cut) {
+        const int v = variant;
+        if (exec_a[v] && cut_[v] == cut) return MMI_OK;
+        drop_split(v);
+        int rc;
+        if ((rc = capture_range(capture_stream, 0, cut, &graph_a[v], &exec_a[v]))) return rc;
+        if ((rc = capture_range(capture_stream, cut, ops.size(), &graph_b[v], &exec_b[v]))) return rc;
+        cut_[v] = cut;
+        return MMI_OK;
+    }
+
+    int run(hipStream_t s, bool use_graph, hipStream_t capture_stream) {
+        if (!use_graph) return run_eager(s);
+        const int v = variant;
+        int rc = capture_full(capture_stream);
+        if (rc) return rc;
+        MMI_HIP_CHECK(hipGraphLaunch(exec[v], s));
+        return MMI_OK;
+    }
+
+    // Variant v made ready AHEAD of the step that first needs it (ADVICE r4: a stream whose rings grow past the short-ring program
+    // would otherwise capture and instantiate the other program in the middle of a live session - a one-off latency spike in a
+    // real-time stream): its graph(s) captured and instantiated now, nothing launched.  split: the two-graph form run_split uses.
+    int precapture(int v, hipStream_t capture_stream, bool split, size_t cut) {
+        const int keep = variant;
+        variant = v;
+        int rc = MMI_OK;
+        if (!split || !logged_[v]) rc = capture_full(capture_stream);       // (also records the variant's launch list)
+        if (!rc && split) rc = capture_split(capture_stream, cut);
+        variant = keep;
+        return rc;
+    }
+    bool ready(int v, bool split) const { return split ? (exec_a[v] && exec_b[v]) : exec[v] != nullptr; }
 
     // ops [0, cut) - between(s) - ops [cut, end): as two graph launches (or eagerly), `between` enqueued on s in the middle
     int run_split(hipStream_t s, bool use_graph, hipStream_t capture_stream, size_t cut, const std::function<int(hipStream_t)>& between) {
         int rc;
         const int v = variant;
-        if (!use_graph || !logged_[v]) {        // the first run of a variant is the eager one that records the launch list
-            const bool rec = !logged_[v];
-            if (rec) mmi_record_begin(&launch_logs[v]);
-            rc = MMI_OK;
-            for (size_t i = 0; i < ops.size() && !rc; ++i) {
-                if (i == cut && (rc = between(s))) break;
-                    if (rec) mmi_record_site(sites[i].c_str());
-                if (tap) tap(i, true, s);
-                rc = ops[i](s);
-                if (tap) tap(i, false, s);
-            }
-            if (rec) { mmi_record_end(); logged_[v] = true; }
-            return rc;
-        }
-        if (!exec_a[v] || cut_[v] != cut) {
-            drop_split(v);
-            if ((rc = capture_range(capture_stream, 0, cut, &graph_a[v], &exec_a[v]))) return rc;
-            if ((rc = capture_range(capture_stream, cut, ops.size(), &graph_b[v], &exec_b[v]))) return rc;
-            cut_[v] = cut;
-        }
+        if (!use_graph || !logged_[v]) return run_eager(s, cut, &between);   // the first run of a variant is the eager one that records the launch list
+        if ((rc = capture_split(capture_stream, cut))) return rc;
         MMI_HIP_CHECK(hipGraphLaunch(exec_a[v], s));
         if ((rc = between(s))) return rc;
         MMI_HIP_CHECK(hipGraphLaunch(exec_b[v], s));
@@ -208,8 +171,3 @@ struct MmiProgram {
         site_ = "-";
     }
 };
-
-static inline bool mmi_graphs_enabled() {
-    const char* e = getenv("MMI_NO_GRAPH");
-    return !(e && e[0] && e[0] != '0');
-}

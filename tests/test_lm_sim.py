@@ -525,3 +525,66 @@ def test_debug_trace_of_two_sessions_is_identical(sim_lib, monkeypatch, tmp_path
     assert len(traces) == 2 and traces[0].read_text() == traces[1].read_text() and len(traces[0].read_text().splitlines()) > 100
     dumps = sorted(tmp_path.glob("trace.*.a10"))
     assert len(dumps) == 2 and dumps[0].read_bytes() == dumps[1].read_bytes() and any(dumps[0].read_bytes())
+
+
+def _launches_of_two_steps(gen, cfg, B):
+    rng = np.random.default_rng(0)
+    with gen.streaming(B):
+        for _ in range(2):
+            gen.step(torch.from_numpy(rng.integers(0, cfg.card, (B, cfg.n_q - cfg.dep_q, 1))))
+        rows = gen.launch_list(with_bytes=True)
+    # the recorder hands a weight-byte count left behind by the thread's last unrecorded GEMM (an earlier handle's) to the first
+    # launch it sees, k_lm_prepare: not this handle's doing
+    assert rows[0][:2] == ("prepare", "k_lm_prepare")
+    return [rows[0][:2] + (0,)] + rows[1:]
+
+
+def _knob_snapshot_case(sim_lib, monkeypatch, B):
+    """One session (the depth transformer's attention inside out_proj unless MMI_NO_DEP_ATTN_FUSION) or 18 (k_gemm_xlds unless
+    MMI_GEMM_LDS=0; MMI_GEMM_LDS_GRID, set throughout, is what lets the tiny shapes take that kernel at all): the launch list of
+    a handle that never saw the two variables, and a factory of fresh handles."""
+    monkeypatch.delenv("MMI_GEMM_LDS", raising=False)
+    monkeypatch.delenv("MMI_NO_DEP_ATTN_FUSION", raising=False)
+    monkeypatch.setenv("MMI_GEMM_LDS_GRID", "8")
+    cfg = tiny_lm_config()
+    sd = random_lm_state_dict(cfg, seed=5)
+
+    def make():
+        return lm_cases.make_engine(cfg, sd, "cpu", sim_lib, B, use_sampling=False, support_out_of_sync=True)
+    never = _launches_of_two_steps(make(), cfg, B)
+    assert len(never) > 50
+    if B == 1:
+        assert not any(site == "dep.attn" for site, _, _ in never)
+    else:
+        assert any("k_gemm_xlds" in kernel for _, kernel, _ in never)
+    return cfg, make, never
+
+
+def test_a_handle_keeps_the_environment_it_was_created_in(sim_lib, monkeypatch):
+    """Every MMI_* variable is read once, when a handle is created (mmi_knobs.h): MMI_GEMM_LDS (decided per launch) and
+    MMI_NO_DEP_ATTN_FUSION (decided when streaming_start builds the launch list) changed between create and streaming_start do
+    not reach the handle - its launch list, weight bytes included, is that of a handle that never saw them."""
+    for B in (1, 18):
+        cfg, make, never = _knob_snapshot_case(sim_lib, monkeypatch, B)
+        gen = make()
+        monkeypatch.setenv("MMI_GEMM_LDS", "0")
+        monkeypatch.setenv("MMI_NO_DEP_ATTN_FUSION", "1")
+        assert _launches_of_two_steps(gen, cfg, B) == never
+        assert _launches_of_two_steps(gen, cfg, B) == never        # nor a later stream of the same handle
+
+
+def test_a_handle_created_after_the_environment_changed_obeys_it(sim_lib, monkeypatch):
+    """The snapshot is per handle, not per process: the next handle of the same process takes the new values."""
+    for B in (1, 18):
+        cfg, make, never = _knob_snapshot_case(sim_lib, monkeypatch, B)
+        monkeypatch.setenv("MMI_GEMM_LDS", "0")
+        monkeypatch.setenv("MMI_NO_DEP_ATTN_FUSION", "1")
+        changed = _launches_of_two_steps(make(), cfg, B)
+        assert changed != never
+        if B == 1:
+            assert sum(site == "dep.attn" for site, _, _ in changed) == 7 * 2
+        else:
+            assert not any("k_gemm_xlds" in kernel for _, kernel, _ in changed)
+        monkeypatch.delenv("MMI_GEMM_LDS")
+        monkeypatch.delenv("MMI_NO_DEP_ATTN_FUSION")
+        assert _launches_of_two_steps(make(), cfg, B) == never
