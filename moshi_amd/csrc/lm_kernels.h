@@ -2367,7 +2367,9 @@ __device__ __forceinline__ float mmi_exp_noise(unsigned long long seed, unsigned
         k0 += 0x9E3779B9u;
         k1 += 0xBB67AE85u;
     }
-    float u = ((float)(c0 >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0,1)
+    // (0, 1): 24 bits + 0.5 is rounded to fp32 above 2^23 (to even) and all-ones would arrive at 1.0f - a draw of -log(u) = 0 - without
+    // the clamp to the largest float under 1; every other word keeps the value it always had
+    float u = fminf(((float)(c0 >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
     return -logf(u);
 }
 
@@ -2743,7 +2745,7 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
                     if (!tk[e]) continue;
                     const int e_ = 4 * h + e, i = i0 + v_ * 8 + e_;
                     const uint16_t bits = (uint16_t)((e_ & 1) ? (r4_[e_ >> 1] >> 16) : (r4_[e_ >> 1] & 0xffffu));
-                    const float u = ((float)(r[e] >> 8) + 0.5f) * (1.0f / 16777216.0f);   // (0, 1)
+                    const float u = fminf(((float)(r[e] >> 8) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);   // (0, 1): see mmi_exp_noise
                     const float sc_ = mmi_bf16_to_f32(bits) * inv_t - mmi_fast_logf(-mmi_fast_logf(u));
                     if (sc_ > best || (sc_ == best && i < bi)) { best = sc_; bi = i; }
                 }

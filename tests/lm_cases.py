@@ -990,7 +990,7 @@ def philox_exp_noise(seed: int, step: int, a: int, idx: np.ndarray) -> np.ndarra
         p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2
         c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ k0) & M, p1 & M, ((p0 >> np.uint64(32)) ^ c3 ^ k1) & M, p0 & M
         k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M, (k1 + np.uint64(0xBB67AE85)) & M
-    u = ((c0 >> np.uint64(8)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0)
+    u = np.minimum(((c0 >> np.uint64(8)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0), np.float32(1.0 - 2.0 ** -24))   # < 1
     return (-np.log(u)).astype(np.float32)
 
 
@@ -1059,7 +1059,7 @@ def check_topk_device_rng(device, lib, cfg=None, top_k=20, top_k_text=10, steps=
             V = len(key)
             order = np.lexsort((np.arange(V), -key))[:min(k, V)]
             words = philox4_words(seed, step, site * B + b, order >> 2)[np.arange(len(order)), order & 3]
-            u = ((words >> np.uint64(8)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0)
+            u = np.minimum(((words >> np.uint64(8)).astype(np.float32) + np.float32(0.5)) * np.float32(1.0 / 16777216.0), np.float32(1.0 - 2.0 ** -24))
             sc = (logits[b][order].astype(np.float32) * (np.float32(1.0) / np.float32(t))).astype(np.float32) - np.log(-np.log(u)).astype(np.float32)
             best = order[np.lexsort((order, -sc))]
             if int(got[b]) != int(best[0]):
