@@ -284,6 +284,52 @@ int mmi_lm_streaming_stop(mmi_lm* lm);
 int mmi_lm_set_exec_mask(mmi_lm* lm, const uint8_t* mask, mmi_stream stream);        /* lm.py:544-547 */
 int mmi_lm_reset(mmi_lm* lm, const uint8_t* mask_or_null, mmi_stream stream);        /* lm.py:537-542 */
 
+/* Per-session sampling settings (no counterpart in the reference's Python LMGen; its Rust server takes them from each
+ * connection's query string, rust/moshi-backend/src/stream_both.rs:95-105, and applies them to that session alone,
+ * rust/moshi-core/src/lm_generate_multistream.rs:142-183, 247-255).  A session that has an entry samples every site with its own
+ * values and its own Philox stream: key = seed, counter (the session's stream offset, site, entry) - so its draws do not depend
+ * on its slot, on the batch size or on how many steps the handle has run, and on a fresh stream they are the draws of a
+ * one-session stream started with the same mmi_sampling.  The text site of such a session also gets, in this order:
+ *   repetition penalty  every distinct token among the newest repetition_context entries of the session's ring of its last 64
+ *                       committed text tokens (the token the step stores, after forcing and hooks; the padding id, the
+ *                       end-of-padding id (0 unless mmi_lm_set_text_end_padding_id moved it) and the text start id are never
+ *                       recorded; masked steps record nothing) has its logit changed: l >= 0 ? l / penalty : l * penalty - fp32 from the bf16 logit, correctly rounded division,
+ *                       rounded back to bf16 (nearest even).  Ids outside the vocabulary are ignored.
+ *   pad bias            sampling sessions only (greedy ones ignore it, like the reference's ArgMax): the logit of
+ *                       existing_text_padding_id becomes bf16(l + pad_mult * temp_text), an fp32 product then an fp32 sum - the
+ *                       reference's prs[pad] *= exp(pad_mult) after the temperature softmax, in logit space.  Its resolution is
+ *                       one bf16 ulp of the pad logit: a bias smaller than half an ulp leaves the row unchanged.
+ * Both come after the guidance mix and after an on_text_logits hook.  Sessions without an entry sample exactly as before. */
+struct mmi_row_sampling {
+    int32_t use_sampling;        /* 0 = greedy argmax                                  */
+    float temp;                  /* audio temperature                                  */
+    float temp_text;
+    int32_t top_k;               /* 0 (or >= the vocabulary) = the full multinomial    */
+    int32_t top_k_text;
+    uint64_t seed;               /* one seed per session: text and audio sites share it */
+    float pad_mult;              /* 0 = off                                            */
+    float repetition_penalty;    /* 1 = off; must be > 0                               */
+    int32_t repetition_context;  /* 0 = off; at most 64                                */
+};
+typedef struct mmi_row_sampling mmi_row_sampling;
+/* MMI_OK, or what mmi_lm_set_row_sampling would refuse the entry with: top_k / top_k_text > 256 MMI_ERR_UNSUPPORTED, < 0
+ * MMI_ERR_INVALID (as for mmi_sampling); repetition_context outside [0, 64], repetition_penalty <= 0 or any non-finite value
+ * MMI_ERR_INVALID. */
+int mmi_row_sampling_check(const mmi_row_sampling* r);
+/* The sessions b with mask[b] != 0 (mask: HOST uint8 [batch], NULL = all) take rows[b] (HOST [batch]; entries of unmasked
+ * sessions are not read), their ring of text tokens is emptied and they sample with their own settings from the next step on.
+ * Stream-ordered on `stream`, no host synchronisation (the entries travel as kernel arguments), legal between any two steps;
+ * neither the launch list nor a captured graph changes.  Under guidance it addresses sessions, not model rows.  A refused call
+ * changes nothing.  mmi_lm_reset keeps a session's settings and empties its ring; streaming_start begins with no entries; a state
+ * snapshot carries entries and rings.  While any session has an entry, mmi_lm_step refuses opt_noise (MMI_ERR_UNSUPPORTED). */
+int mmi_lm_set_row_sampling(mmi_lm* lm, const uint8_t* mask_or_null, const mmi_row_sampling* rows, mmi_stream stream);
+/* The masked sessions (HOST uint8 [batch], NULL = all) return to the handle's mmi_sampling and the handle's counter. */
+int mmi_lm_clear_row_sampling(mmi_lm* lm, const uint8_t* mask_or_null, mmi_stream stream);
+/* The end-of-padding id the text history skips (the reference's text_eop_token; LMModel.end_of_text_padding_id, which a
+ * checkpoint's existing_text_end_padding_id may move).  0 after create.  Not while streaming (MMI_ERR_STATE): the id is an
+ * argument of the commit kernel in the launch list.  An id outside [0, text_card] is MMI_ERR_INVALID. */
+int mmi_lm_set_text_end_padding_id(mmi_lm* lm, int32_t id);
+
 /* LMGen.step (lm.py:785-791, 668-783).
  *   user_codes  i64 [batch, n_user(>= n_q - dep_q), 1]; extra rows are ignored (lm.py:688-689)
  *   out_tokens  i64 [batch, dep_q + 1, 1]; rows not yet valid hold -2 (lm.py:781-782)
@@ -490,6 +536,10 @@ void mmi_batcher_destroy(mmi_batcher* b);
 /* Claim a free slot (py_module.rs:443-470); MMI_ERR_BUSY when all are taken.  The row's streaming state is reset at
  * the next step (handle_chat: mimi.reset_streaming(); lm_gen.reset_streaming(), server.py:163-164). */
 int mmi_batcher_open(mmi_batcher* b, int64_t* channel_id);
+/* The same with the channel's own sampling settings (stream_both.rs:95-105): the slot's row gets them, with its reset, before
+ * its first step.  NULL = mmi_batcher_open: the batcher's cfg.sampling (also for a slot whose last owner had settings).
+ * Settings mmi_row_sampling_check refuses are refused here, and no slot is claimed. */
+int mmi_batcher_open_with(mmi_batcher* b, const mmi_row_sampling* settings_or_null, int64_t* channel_id);
 int mmi_batcher_close(mmi_batcher* b, int64_t channel_id);
 /* Append 24 kHz mono PCM (host f32) to the channel's FIFO (batched_asr.rs:77-90 extend_data). */
 int mmi_batcher_push_pcm(mmi_batcher* b, int64_t channel_id, const float* pcm, int32_t n_samples);

@@ -62,6 +62,13 @@ class Sampling(C.Structure):
                 ("top_k_text", C.c_int32), ("seed", C.c_uint64)]
 
 
+class RowSampling(C.Structure):
+    """struct mmi_row_sampling: one session's own sampling settings (mmi_lm_set_row_sampling, mmi_batcher_open_with)."""
+    _fields_ = [("use_sampling", C.c_int32), ("temp", C.c_float), ("temp_text", C.c_float), ("top_k", C.c_int32),
+                ("top_k_text", C.c_int32), ("seed", C.c_uint64), ("pad_mult", C.c_float), ("repetition_penalty", C.c_float),
+                ("repetition_context", C.c_int32)]
+
+
 class Guidance(C.Structure):
     _fields_ = [("cfg_coef", C.c_float), ("cfg_is_no_text", C.c_int32), ("cfg_is_masked_until", C.c_void_p),
                 ("condition_sum", C.c_void_p), ("condition_cross", C.c_void_p), ("cross_len", C.c_int32)]
@@ -136,6 +143,10 @@ SIGNATURES = {
     "mmi_lm_streaming_stop": (C.c_int, [_P]),
     "mmi_lm_set_exec_mask": (C.c_int, [_P, _P, _P]),
     "mmi_lm_reset": (C.c_int, [_P, _P, _P]),
+    "mmi_row_sampling_check": (C.c_int, [C.POINTER(RowSampling)]),
+    "mmi_lm_set_row_sampling": (C.c_int, [_P, _P, C.POINTER(RowSampling), _P]),
+    "mmi_lm_clear_row_sampling": (C.c_int, [_P, _P, _P]),
+    "mmi_lm_set_text_end_padding_id": (C.c_int, [_P, C.c_int32]),
     "mmi_lm_step": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32), _P]),
     "mmi_lm_force_next_tokens": (C.c_int, [_P, _P, _P]),
     "mmi_lm_set_phase_callback": (C.c_int, [_P, _P, _P]),
@@ -146,6 +157,7 @@ SIGNATURES = {
     "mmi_batcher_create": (C.c_int, [_P, _P, C.POINTER(BatcherCfg), C.POINTER(_P)]),
     "mmi_batcher_destroy": (None, [_P]),
     "mmi_batcher_open": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "mmi_batcher_open_with": (C.c_int, [_P, C.POINTER(RowSampling), C.POINTER(C.c_int64)]),
     "mmi_batcher_close": (C.c_int, [_P, C.c_int64]),
     "mmi_batcher_push_pcm": (C.c_int, [_P, C.c_int64, _P, C.c_int32]),
     "mmi_batcher_step": (C.c_int, [_P, C.POINTER(C.c_int32)]),
@@ -162,6 +174,16 @@ SIGNATURES = {
 }
 
 
+_SINCE_ROW_SAMPLING = ("mmi_row_sampling_check", "mmi_lm_set_row_sampling", "mmi_lm_clear_row_sampling", "mmi_batcher_open_with",
+                       "mmi_lm_set_text_end_padding_id")
+
+
+def _missing(name, path):
+    def refuse(*_a):
+        raise RuntimeError(f"{path} does not export {name}: it was built before per-session sampling existed")
+    return refuse
+
+
 class Lib:
     """A loaded engine library with typed entry points and the reference's error conventions."""
 
@@ -169,6 +191,10 @@ class Lib:
         self.path = Path(path)
         self.cdll = C.CDLL(str(self.path))
         for name, (res, args) in SIGNATURES.items():
+            if name in _SINCE_ROW_SAMPLING and not hasattr(self.cdll, name):
+                # an older build of the engine (MMI_LIB_PATH, A/B runs against a parent build): everything else works, these refuse
+                setattr(self, name, _missing(name, self.path))
+                continue
             fn = getattr(self.cdll, name)  # AttributeError if the library does not export the ABI
             fn.restype = res
             fn.argtypes = args

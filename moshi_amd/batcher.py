@@ -103,9 +103,15 @@ class SessionBatcher:
         self.close_all()
 
     # ---- channels ------------------------------------------------------------------------------------
-    def open(self) -> int:
+    def open(self, sampling=None) -> int:
+        """Claim a slot.  `sampling`: a `moshi_amd.SessionSampling` - the channel samples with its own settings and its own seeded
+        draw stream (the same tokens whichever slot it lands in); None = the batcher's settings.  Settings the engine refuses
+        raise here (ValueError / NotImplementedError) and claim no slot."""
         ch = C.c_int64(0)
-        self._lib.check(self._lib.mmi_batcher_open(self._handle, C.byref(ch)))
+        if sampling is None:
+            self._lib.check(self._lib.mmi_batcher_open(self._handle, C.byref(ch)))
+        else:
+            self._lib.check(self._lib.mmi_batcher_open_with(self._handle, C.byref(sampling.to_c()), C.byref(ch)))
         return int(ch.value)
 
     def close(self, channel: int) -> None:

@@ -12,6 +12,18 @@ int mmi_fail(int code, const std::string& msg) {
 extern "C" int mmi_version(void) { return MMI_ABI_VERSION; }
 extern "C" const char* mmi_last_error(void) { return g_last_error.c_str(); }
 
+// mmi_row_sampling as mmi_lm_set_row_sampling and mmi_batcher_open_with accept it (validated like mmi_sampling)
+extern "C" int mmi_row_sampling_check(const mmi_row_sampling* r) {
+    if (!r) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (r->top_k > 256 || r->top_k_text > 256) return mmi_fail(MMI_ERR_UNSUPPORTED, "top_k > 256");
+    if (r->top_k < 0 || r->top_k_text < 0) return mmi_fail(MMI_ERR_INVALID, "top_k must be >= 0 (0 = no top-k)");
+    if (r->repetition_context < 0 || r->repetition_context > 64) return mmi_fail(MMI_ERR_INVALID, "repetition_context must be in [0, 64]");
+    for (float v : {r->temp, r->temp_text, r->pad_mult, r->repetition_penalty})
+        if (!(v - v == 0.f)) return mmi_fail(MMI_ERR_INVALID, "per-session sampling settings must be finite");
+    if (!(r->repetition_penalty > 0.f)) return mmi_fail(MMI_ERR_INVALID, "repetition_penalty must be > 0 (1 = off)");
+    return MMI_OK;
+}
+
 // ---- launch-list recorder (mmi_graph.h) ------------------------------------------------------------------------------
 static thread_local std::vector<std::string>* g_rec_log = nullptr;
 static thread_local const char* g_rec_site = "-";

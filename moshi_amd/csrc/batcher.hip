@@ -25,6 +25,8 @@ struct Channel {                 // batched_asr.rs:61-69
     int64_t id = 0;
     bool live = false;
     bool pending_reset = false;  // opened since the last step: the row's streaming state is reset before it runs
+    bool own_sampling = false;   // mmi_batcher_open_with: the row samples with `sampling` instead of the batcher's settings
+    mmi_row_sampling sampling{};
     long frames = 0;             // input frames consumed
     std::deque<float> in;        // PCM FIFO
     std::deque<OutFrame> out;
@@ -99,6 +101,8 @@ struct mmi_batcher {
     std::mutex mu;                // guards channels / stats (batched_asr.rs:438 Channels = Arc<Mutex<..>>)
     std::vector<Channel> channels;
     std::vector<int64_t> row_owner;   // channel id that owned each row when the current step started
+    std::vector<uint8_t> m_set, m_clear;      // rows opened since the last step: with / without settings of their own
+    std::vector<mmi_row_sampling> row_set;
     int64_t next_id = 1;
     mmi_batcher_stats stats;
 };
@@ -175,6 +179,9 @@ int create_impl(mmi_batcher* b) {
     if ((rc = mmi_lm_streaming_start_guided(b->lm, B, &b->cfg.sampling, guide, b->stream))) return rc;
     b->channels.resize(B);
     b->row_owner.assign(B, 0);
+    b->m_set.assign(B, 0);
+    b->m_clear.assign(B, 0);
+    b->row_set.assign(B, mmi_row_sampling{});
     memset(&b->stats, 0, sizeof(b->stats));
     b->stats.total_slots = B;
     return MMI_OK;
@@ -206,15 +213,20 @@ extern "C" void mmi_batcher_destroy(mmi_batcher* b) {
     if (b) release(b);
 }
 
-extern "C" int mmi_batcher_open(mmi_batcher* b, int64_t* channel_id) {
+extern "C" int mmi_batcher_open(mmi_batcher* b, int64_t* channel_id) { return mmi_batcher_open_with(b, nullptr, channel_id); }
+
+extern "C" int mmi_batcher_open_with(mmi_batcher* b, const mmi_row_sampling* settings, int64_t* channel_id) {
     MmiDeviceGuard dev_guard_(b ? mmi_lm_device(b->lm) : -1);
     if (!b || !channel_id) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    int rc;
+    if (settings && (rc = mmi_row_sampling_check(settings))) return rc;
     std::lock_guard<std::mutex> g(b->mu);
     for (auto& c : b->channels) {
         if (c.live) continue;
         c = Channel();
         c.live = true;
         c.pending_reset = true;
+        if (settings) { c.own_sampling = true; c.sampling = *settings; }
         c.id = b->next_id++;
         *channel_id = c.id;
         b->stats.used_slots += 1;
@@ -252,7 +264,7 @@ extern "C" int mmi_batcher_step(mmi_batcher* b, int32_t* n_active) {
     const int B = b->B, F = b->F;
     Staging& h = b->host;
     Staging& d = b->dev;
-    int active = 0, resets = 0, firsts = 0;
+    int active = 0, resets = 0, firsts = 0, sets = 0;
     {   // ---- pre_process (batched_asr.rs:279-374)
         std::lock_guard<std::mutex> g(b->mu);
         for (int r = 0; r < B; ++r) {
@@ -264,7 +276,10 @@ extern "C" int mmi_batcher_step(mmi_batcher* b, int32_t* n_active) {
                 h.reset[r] = 1;
                 c.pending_reset = false;
                 ++resets;
-            }
+                b->m_set[r] = c.own_sampling ? 1 : 0;
+                b->m_clear[r] = c.own_sampling ? 0 : 1;
+                if (c.own_sampling) { b->row_set[r] = c.sampling; ++sets; }
+            } else b->m_set[r] = b->m_clear[r] = 0;
             if (c.live && c.in.size() >= (size_t)F) {
                 std::copy(c.in.begin(), c.in.begin() + F, dst);
                 c.in.erase(c.in.begin(), c.in.begin() + F);
@@ -289,6 +304,9 @@ extern "C" int mmi_batcher_step(mmi_batcher* b, int32_t* n_active) {
     if (resets) {   // handle_chat: mimi.reset_streaming(); lm_gen.reset_streaming() (server.py:163-164), for the new rows only
         if ((rc = mmi_mimi_reset(b->mimi, d.reset, s))) return rc;
         if ((rc = mmi_lm_reset(b->lm, d.reset, s))) return rc;
+        // the new owner's sampling settings: its own (open_with), or the batcher's again whatever the slot's last owner had
+        if (resets > sets && (rc = mmi_lm_clear_row_sampling(b->lm, b->m_clear.data(), s))) return rc;
+        if (sets && (rc = mmi_lm_set_row_sampling(b->lm, b->m_set.data(), b->row_set.data(), s))) return rc;
     }
     if (active == 0) {
         MMI_HIP_CHECK(hipStreamSynchronize(s));

@@ -133,6 +133,12 @@ struct mmi_lm {
     bool forced_armed = false;
     bool noise_on = false;                          // host mirror of *use_noise
     unsigned long long* rng = nullptr;
+    // per-session sampling (mmi_lm_set_row_sampling): the device table k_sample reads, the rings of committed text tokens, and
+    // the host's mirror of `active` (supplied noise is refused while any row is active)
+    RowSamp* rowtab = nullptr;                      // [gen_batch]
+    int* thist = nullptr;                           // [gen_batch][MMI_TEXT_HIST]
+    std::vector<uint8_t> row_active;
+    int text_eop = 0;                               // LMModel.end_of_text_padding_id (mmi_lm_set_text_end_padding_id)
     // per-step host hooks (mmi_lm_set_hooks): the step is cut at these ops of the launch list
     mmi_lm_hooks hooks{nullptr, nullptr, nullptr, nullptr};
     bool in_hook = false;
@@ -824,6 +830,8 @@ void add_sample(mmi_lm* lm, uint16_t* logits, int ld, int V, bool text, int site
     sa.use_noise = lm->use_noise; sa.rng = lm->rng; sa.site = site; sa.out = out; sa.out_stride = out_stride;
     sa.B = lm->gen_batch;
     sa.forced = lm->forced + site; sa.forced_stride = 1 + lm->cfg.dep_q; sa.use_forced = lm->use_forced;
+    sa.rows = lm->rowtab; sa.offsets = lm->offsets; sa.thist = text ? lm->thist : nullptr; sa.text = text ? 1 : 0;
+    sa.pad_id = lm->cfg.existing_text_padding_id;
     const int B = lm->gen_batch;
     if (text) {                     // hook boundaries: the guided logits are final here, the sampler is the next op
         lm->op_text_sample = lm->prog.ops.size();
@@ -922,6 +930,8 @@ TokArgs tok_args(mmi_lm* lm) {
     t.cache = lm->cache; t.offsets = lm->offsets; t.exec = lm->exec; t.delays = lm->delays_dev;
     t.B = lm->gen_batch; t.NC = lm->NC; t.CT = lm->CT; t.dep_q = lm->cfg.dep_q; t.max_delay = lm->max_delay;
     t.card = lm->cfg.card; t.text_card = lm->cfg.text_card;
+    t.rows = lm->rowtab; t.thist = lm->thist;
+    t.text_pad = lm->cfg.existing_text_padding_id; t.text_eop = lm->text_eop;      // LMModel.end_of_text_padding_id (lm.py:261); gen.rs:79
     return t;
 }
 
@@ -1574,6 +1584,8 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
     ok &= hipSuccess == A.alloc(&lm->forced, (size_t)G * (1 + c.dep_q));
     ok &= hipSuccess == A.alloc(&lm->use_forced, (size_t)1);
     ok &= hipSuccess == A.alloc(&lm->rng, (size_t)2);
+    ok &= hipSuccess == A.alloc(&lm->rowtab, (size_t)G);
+    ok &= hipSuccess == A.alloc(&lm->thist, (size_t)G * MMI_TEXT_HIST);
     if (!ok) return fail(mmi_fail(MMI_ERR_HIP, "out of device memory (LM streaming state)"));
     MMI_HIP_CHECK(hipMemsetAsync(lm->exec, 1, G, s));
     MMI_HIP_CHECK(hipMemsetAsync(lm->offsets, 0, G * sizeof(long), s));
@@ -1594,6 +1606,9 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
     lm->noise_on = false;
     MMI_HIP_CHECK(hipMemsetAsync(lm->use_forced, 0, sizeof(int), s));
     lm->forced_armed = false;
+    MMI_HIP_CHECK(hipMemsetAsync(lm->rowtab, 0, (size_t)G * sizeof(RowSamp), s));          // every row inactive
+    MMI_HIP_CHECK(hipMemsetAsync(lm->thist, 0, (size_t)G * MMI_TEXT_HIST * sizeof(int), s));
+    lm->row_active.assign(G, 0);
     {   // packed activations: the padding rows / columns of a fragment are never written and must read as zero
         struct { uint16_t* p; int f; int T; } pk[] = {{lm->x, d, lm->T}, {lm->xn, d, lm->T}, {lm->att, d, lm->T}, {lm->hb, c.ffn_hidden, lm->T},
                                                       {lm->tout, d, lm->T}, {lm->dx, dd, lm->Td}, {lm->dxn, dd, lm->Td}, {lm->datt, dd, lm->Td},
@@ -1668,6 +1683,59 @@ extern "C" int mmi_lm_reset(mmi_lm* lm, const uint8_t* mask, mmi_stream stream) 
     return MMI_OK;
 }
 
+// ---- per-session sampling ---------------------------------------------------------------------------------------------------
+static int write_rows(mmi_lm* lm, const uint8_t* mask, const mmi_row_sampling* rows, hipStream_t s) {
+    const int G = lm->gen_batch;
+    RowSampSet set;
+    memset(&set, 0, sizeof(set));
+    auto flush = [&]() -> int {
+        if (!set.n) return MMI_OK;
+        MMI_LAUNCH(k_lm_set_rows, 1, 64, 0, s, lm->rowtab, set, G);
+        MMI_CHECK_LAUNCH();
+        set.n = 0;
+        return MMI_OK;
+    };
+    for (int b = 0; b < G; ++b) {
+        if (mask && !mask[b]) continue;
+        RowSamp e;
+        memset(&e, 0, sizeof(e));                       // active = 0, hist_n = 0: the handle's settings, an empty ring
+        if (rows) {
+            const mmi_row_sampling& r = rows[b];
+            e.active = 1; e.use_sampling = r.use_sampling ? 1 : 0; e.top_k = r.top_k; e.top_k_text = r.top_k_text;
+            e.temp = r.temp; e.temp_text = r.temp_text; e.pad_mult = r.pad_mult; e.rep_penalty = r.repetition_penalty;
+            e.seed = r.seed; e.rep_context = r.repetition_context;
+        }
+        set.e[set.n] = e; set.row[set.n] = b;
+        if (++set.n == 16) { int rc = flush(); if (rc) return rc; }
+        lm->row_active[b] = rows ? 1 : 0;
+    }
+    return flush();
+}
+
+extern "C" int mmi_lm_set_row_sampling(mmi_lm* lm, const uint8_t* mask, const mmi_row_sampling* rows, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm || !rows) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (!lm->streaming) return mmi_fail(MMI_ERR_STATE, "not streaming");
+    for (int b = 0; b < lm->gen_batch; ++b)            // all or nothing: a refused call changes no row
+        if (!mask || mask[b]) { int rc = mmi_row_sampling_check(&rows[b]); if (rc) return rc; }
+    return write_rows(lm, mask, rows, (hipStream_t)stream);
+}
+
+extern "C" int mmi_lm_set_text_end_padding_id(mmi_lm* lm, int32_t id) {
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (lm->streaming) return mmi_fail(MMI_ERR_STATE, "the end-of-padding id is part of the step's launch list: set it before streaming_start");
+    if (id < 0 || id > lm->cfg.text_card) return mmi_fail(MMI_ERR_INVALID, "end-of-padding id outside the text vocabulary");
+    lm->text_eop = id;
+    return MMI_OK;
+}
+
+extern "C" int mmi_lm_clear_row_sampling(mmi_lm* lm, const uint8_t* mask, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (!lm->streaming) return mmi_fail(MMI_ERR_STATE, "not streaming");
+    return write_rows(lm, mask, nullptr, (hipStream_t)stream);
+}
+
 extern "C" int mmi_lm_step(mmi_lm* lm, const int64_t* user_codes, int32_t n_user, int64_t* out_tokens, float* opt_text_logits,
                            float* opt_audio_logits, const float* opt_noise, int32_t batch, int32_t* valid, mmi_stream stream) {
     MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
@@ -1681,10 +1749,14 @@ extern "C" int mmi_lm_step(mmi_lm* lm, const int64_t* user_codes, int32_t n_user
     if (n_user < need_user) return mmi_fail(MMI_ERR_SHAPE, "not enough user tokens");   // lm.py:683-686
     hipStream_t s = (hipStream_t)stream;
     const int B = batch;
-    if (need_user > 0)
-        MMI_LAUNCH(k_i64_to_i32, mmi_cdiv(B * need_user, 256), 256, 0, s, (const long*)user_codes, (long)n_user, lm->user_i32, B, need_user);
+    // refusals first: a refused step enqueues nothing
+    if (opt_noise)
+        for (uint8_t on : lm->row_active)
+            if (on) return mmi_fail(MMI_ERR_UNSUPPORTED, "supplied noise is a parity aid of the handle's own sampling settings: not available while a session has settings of its own (mmi_lm_set_row_sampling)");
     if (opt_noise && lm->samp.use_sampling && (lm->samp.top_k == 0 || lm->samp.top_k_text == 0))
         return mmi_fail(MMI_ERR_UNSUPPORTED, "supplied noise is indexed by rank in the top-k: not available with top_k = 0");
+    if (need_user > 0)
+        MMI_LAUNCH(k_i64_to_i32, mmi_cdiv(B * need_user, 256), 256, 0, s, (const long*)user_codes, (long)n_user, lm->user_i32, B, need_user);
     if (opt_noise) {
         MMI_HIP_CHECK(hipMemcpyAsync(lm->noise, opt_noise, (size_t)B * (1 + c.dep_q) * lm->kmax * sizeof(float), hipMemcpyDeviceToDevice, s));
         MMI_HIP_CHECK(hipMemsetAsync(lm->use_noise, 1, 1, s));
@@ -1891,6 +1963,9 @@ extern "C" int mmi_lm_state_load(mmi_lm* lm, const void* src, int64_t bytes, int
         long mx = 0;
         for (long o : off) mx = o > mx ? o : mx;
         lm->depth_bound = mx;
+        std::vector<RowSamp> tab(lm->gen_batch);         // and the restored table says which rows have settings of their own
+        MMI_HIP_CHECK(hipMemcpy(tab.data(), lm->rowtab, tab.size() * sizeof(RowSamp), hipMemcpyDeviceToHost));
+        for (int b = 0; b < lm->gen_batch; ++b) lm->row_active[b] = tab[b].active ? 1 : 0;
     }
     lm->forced_armed = false;
     lm->noise_on = true;               // the snapshot carries its own use_noise word: the next step rewrites it

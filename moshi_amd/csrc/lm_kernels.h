@@ -2243,6 +2243,24 @@ __global__ __launch_bounds__(WAVES * 64) void k_dep_attn_out_proj(GemmArgs a, De
 // ------------------------------------------------------------------------------------------------
 // sampling (sampling.py:86-106): softmax(logits/temp) -> top-k -> argmax(p / Exp(1)); greedy when disabled
 // ------------------------------------------------------------------------------------------------
+// One entry per streaming session (mmi_row_sampling + the engine's own words), 48 bytes = three 16-byte loads that k_sample
+// requests with its other control words.  active == 0: the row samples with the handle's settings and the handle's counter.
+// Active rows: Philox key = seed, counter (the row's stream offset, site, entry) - nothing of the slot, the batch size or the
+// handle's age enters the draws.  The text site of an active row first patches its logits (bf16 in, fp32 arithmetic, bf16 out):
+//   repetition penalty: every distinct in-vocabulary token among the newest rep_context entries of the row's ring of committed
+//                       text tokens: l >= 0 ? l / penalty : l * penalty (correctly rounded fp32 division)
+//   pad bias (sampling rows only, after the penalty): l_pad + pad_mult * temp_text, fp32 product then fp32 sum (no fma) - the
+//                       reference multiplies the pad probability by exp(pad_mult) after the temperature softmax.  The sum is
+//                       rounded to bf16 like every logit, so the bias resolves to one bf16 ulp of the pad logit.
+#define MMI_TEXT_HIST 64
+struct __attribute__((aligned(16))) RowSamp {
+    int active, use_sampling, top_k, top_k_text;
+    float temp, temp_text, pad_mult, rep_penalty;
+    unsigned long long seed;
+    int rep_context;          // 0 = off, <= MMI_TEXT_HIST
+    unsigned hist_n;          // text tokens appended to the row's ring since it was emptied (k_lm_commit); slot = hist_n % 64
+};
+
 struct SampleArgs {
     const uint16_t* logits;   // [B][ld] bf16
     int ld, V, k;
@@ -2268,6 +2286,12 @@ struct SampleArgs {
     int nx_D, nx_T, nx_ksteps;
     int nx_dup;               // classifier-free guidance: the unconditioned twin of session b is model row b + nx_dup and
                               // opens the micro-step with the same token (lm.py:823-826 `input_.repeat(2, 1, 1)`); 0 = none
+    // per-session sampling (mmi_lm_set_row_sampling): the table is read at run time, so a change never touches the launch list
+    const RowSamp* rows;      // [B], never null
+    const long* offsets;      // [B] the sessions' stream offsets: the Philox step counter of an active row
+    const int* thist;         // [B][MMI_TEXT_HIST] ring of committed text tokens; non-null at the text site only
+    int text;                 // 1 = the text site (temp_text / top_k_text of the row's entry)
+    int pad_id;               // existing_text_padding_id: the entry RowSamp::pad_mult lifts
 };
 
 __device__ __forceinline__ void mmi_sample_next_input(const SampleArgs& a, int b0, int tok) {
@@ -2407,6 +2431,24 @@ __device__ __forceinline__ unsigned mmi_bf16_key(uint16_t h) {       // order-pr
     return (h & 0x8000u) ? (unsigned)(uint16_t)~h : (unsigned)(h | 0x8000u);
 }
 
+// One of the thread's E cached logits (entry `off` of its NV vectors) replaced in place: every (vector, word) is compared against
+// `off` with compile-time indices, so the cache stays in registers (no dynamic register indexing, no scratch).
+//   mode 0: repetition penalty p: l >= 0 ? l / p : l * p      mode 1: l + p (the pad bias, p = pad_mult * temp_text)
+template <int NV>
+__device__ __forceinline__ void mmi_sample_patch(u32x4 (&cache)[NV], int off, int mode, float p) {
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+            if ((off >> 1) == v * 4 + w) {
+                const unsigned word = cache[v][w];
+                const float l = mmi_bf16_to_f32((uint16_t)((off & 1) ? (word >> 16) : (word & 0xffffu)));
+                const float r = mode == 0 ? (l >= 0.f ? l / p : l * p) : l + p;
+                const unsigned nb = (unsigned)mmi_f32_to_bf16(r);
+                cache[v][w] = (off & 1) ? ((word & 0x0000ffffu) | (nb << 16)) : ((word & 0xffff0000u) | nb);
+            }
+}
+
 #ifndef MMI_SAMPLE_STAMP
 #define MMI_SAMPLE_STAMP(i)          // scripts/sample_microbench.hip defines it: device-clock stamps at the kernel's stages
 #endif
@@ -2428,14 +2470,18 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
     MMI_SHARED int s_want;
     MMI_SHARED unsigned redk[NT / 64];
     MMI_SHARED unsigned wcnt[NT / 64][4];
+    MMI_SHARED int s_rep[MMI_TEXT_HIST];     // the newest text tokens of an active row (repetition penalty)
     const int lane = tid & 63, wave = tid >> 6;
     const int i0 = tid * E;
     constexpr int NV = E / 8;
     // the step's control words, requested together with the logits: each is a memory round trip of its own where it is first
     // read otherwise (the RNG words in the middle of the scoring, the forcing words behind the last barrier: ~2 us of an 8 us kernel)
-    const int c_use_noise = *a.use_noise;
-    const unsigned long long c_seed = a.rng[0], c_step = a.rng[1];
+    const int g_use_noise = *a.use_noise;
+    const unsigned long long g_seed = a.rng[0], g_step = a.rng[1];
     const int c_forced = *a.use_forced ? a.forced[(long)b * a.forced_stride] : -1;
+    // the session's entry of the per-row table and its stream offset ride with them (workgroup-uniform: one row, one entry)
+    const RowSamp c_row = a.rows[b];
+    const long c_off = a.offsets[b];
 
     u32x4 cache[CACHE ? NV : 1];
     if constexpr (CACHE) {
@@ -2479,7 +2525,40 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
         }                                                                                          \
     }
 
-    if (!a.use_sampling || !(a.temp > 0.f)) {
+    // ---- the row's settings: its own entry when active, else the handle's (today's bits: global seed, counter (rng[1], site * B + b))
+    const bool act = c_row.active != 0;
+    const int s_use_sampling = act ? c_row.use_sampling : a.use_sampling;
+    const float s_temp = act ? (a.text ? c_row.temp_text : c_row.temp) : a.temp;
+    int s_k = act ? (a.text ? c_row.top_k_text : c_row.top_k) : a.k;
+    if (s_k >= V || s_k > 256) s_k = 0;              // top_k == 0 (or the whole vocabulary): the full multinomial
+    const int c_use_noise = act ? 0 : g_use_noise;   // supplied noise is a parity aid of the handle's settings (mmi_lm_step refuses it)
+    const unsigned long long c_seed = act ? c_row.seed : g_seed, c_step = act ? (unsigned long long)c_off : g_step;
+    const unsigned c_pa = act ? (unsigned)a.site : (unsigned)(a.site * a.B + b);
+    const bool s_greedy = !s_use_sampling || !(s_temp > 0.f);
+
+    if constexpr (CACHE) {
+        if (act && a.thist) {             // text site of an active row (block-uniform)
+            const int have = c_row.hist_n < (unsigned)MMI_TEXT_HIST ? (int)c_row.hist_n : MMI_TEXT_HIST;
+            int ctx = c_row.rep_context < have ? c_row.rep_context : have;
+            if (ctx > MMI_TEXT_HIST) ctx = MMI_TEXT_HIST;
+            if (ctx > 0 && c_row.rep_penalty != 1.f) {
+                // newest first: slot (hist_n - 1 - j) % 64
+                if (tid < ctx) s_rep[tid] = a.thist[(long)b * MMI_TEXT_HIST + (int)((c_row.hist_n - 1u - (unsigned)tid) & (unsigned)(MMI_TEXT_HIST - 1))];
+                __syncthreads();
+                for (int j = 0; j < ctx; ++j) {
+                    const int t = s_rep[j];
+                    if (t < 0 || t >= V || (unsigned)(t - i0) >= (unsigned)E) continue;      // not this thread's entry (or outside the vocabulary)
+                    bool seen = false;
+                    for (int jj = 0; jj < j; ++jj) seen = seen || s_rep[jj] == t;            // a token seen twice is penalised once
+                    if (!seen) mmi_sample_patch<NV>(cache, t - i0, 0, c_row.rep_penalty);
+                }
+            }
+            if (!s_greedy && c_row.pad_mult != 0.f && a.pad_id >= 0 && a.pad_id < V && (unsigned)(a.pad_id - i0) < (unsigned)E)
+                mmi_sample_patch<NV>(cache, a.pad_id - i0, 1, c_row.pad_mult * s_temp);      // the fp32 product; the sum is the patch
+        }
+    }
+
+    if (s_greedy) {
         // torch.argmax(logits): first maximum
         float best = -INFINITY;
         int bi = 0x7fffffff;
@@ -2516,11 +2595,11 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
     // removes the two softmax passes, the ordered compaction and the rank computation from the critical path of every
     // sampling site; what stays is the radix select of the k-th largest logit.  Supplied noise (the parity taps) keeps the
     // reference's rank-indexed form below.
-    const bool fast = a.k > 0 && c_use_noise == 0;
+    const bool fast = s_k > 0 && c_use_noise == 0;
     float mx = -INFINITY, sum = 1.f;
     if (!fast) {
     // ---- softmax statistics of logits / temp (fp32)
-    MMI_S_FOREACH({ mx = fmaxf(mx, mmi_bf16_to_f32(bits) / a.temp); })
+    MMI_S_FOREACH({ mx = fmaxf(mx, mmi_bf16_to_f32(bits) / s_temp); })
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, mmi_shfl_xor(mx, m));
     if (lane == 0) redf[wave] = mx;
@@ -2529,7 +2608,7 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
     for (int w = 1; w < NT / 64; ++w) mx = fmaxf(mx, redf[w]);
     __syncthreads();
     sum = 0.f;
-    MMI_S_FOREACH({ sum += expf(mmi_bf16_to_f32(bits) / a.temp - mx); })
+    MMI_S_FOREACH({ sum += expf(mmi_bf16_to_f32(bits) / s_temp - mx); })
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) sum += mmi_shfl_xor(sum, m);
     if (lane == 0) redf[wave] = sum;
@@ -2539,15 +2618,15 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
     __syncthreads();
     }
 
-    if (a.k <= 0) {
+    if (s_k <= 0) {
         // top_k = 0: `multinomial(probs)` over the whole vocabulary (sampling.py:98-106 without top-k/top-p): the reference
         // draws one Exp(1) per VOCABULARY ENTRY and takes argmax(p / q) (sampling.py:40-47); here the draw of entry i is the
         // counter RNG at (site, session, i).  Supplied noise (the parity taps) only exists for the top-k form.
         float score = -INFINITY;
         int tok = 0x7fffffff;
         MMI_S_FOREACH({
-            const float pr = expf(mmi_bf16_to_f32(bits) / a.temp - mx) / sum;
-            const float sc_ = pr / mmi_exp_noise(a.rng[0], a.rng[1], (unsigned)(a.site * a.B + b), (unsigned)i);
+            const float pr = expf(mmi_bf16_to_f32(bits) / s_temp - mx) / sum;
+            const float sc_ = pr / mmi_exp_noise(c_seed, c_step, c_pa, (unsigned)i);
             if (sc_ > score || (sc_ == score && i < tok)) { score = sc_; tok = i; }
         })
 #pragma unroll
@@ -2572,7 +2651,7 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
         return;
     }
 
-    const int k = a.k < V ? a.k : V;
+    const int k = s_k < V ? s_k : V;
     int want = k;
     unsigned Tkey = 0u;
     // ---- production path (round 6): the k-th largest key WITHOUT the two 256-bin LDS histograms over every entry.  The logits of
@@ -2714,7 +2793,7 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
         float best = -INFINITY;
         int bi = 0x7fffffff;
         int eq_seen_f = 0;
-        const float inv_t = 1.0f / a.temp;
+        const float inv_t = 1.0f / s_temp;
         const unsigned long long seed = c_seed, step = c_step;
 #pragma unroll
         for (int v_ = 0; v_ < NV; ++v_) {
@@ -2739,7 +2818,7 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
                 }
                 if (!any) continue;
                 unsigned r[4];
-                mmi_philox4(seed, step, (unsigned)(a.site * a.B + b), (unsigned)((i0 + v_ * 8 + 4 * h) >> 2), r);
+                mmi_philox4(seed, step, c_pa, (unsigned)((i0 + v_ * 8 + 4 * h) >> 2), r);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     if (!tk[e]) continue;
@@ -2782,7 +2861,7 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
         if (ky == Tkey) { take = eq_seen < eq_take; ++eq_seen; }
         if (take) {
             if (pos < 256) {
-                sel_val[pos] = expf(mmi_bf16_to_f32(bits) / a.temp - mx) / sum;
+                sel_val[pos] = expf(mmi_bf16_to_f32(bits) / s_temp - mx) / sum;
                 sel_cmp[pos] = (ky << 16) | (unsigned)(0xffff - i);
                 sel_idx[pos] = i;
             }
@@ -2807,8 +2886,8 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
             r += (o[0] > mine ? 1 : 0) + (o[1] > mine ? 1 : 0) + (o[2] > mine ? 1 : 0) + (o[3] > mine ? 1 : 0);
         }
         float q;
-        if (*a.use_noise) q = a.noise[(long)b * a.noise_ld + r];
-        else q = mmi_exp_noise(a.rng[0], a.rng[1], (unsigned)(a.site * a.B + b), (unsigned)r);
+        if (c_use_noise) q = a.noise[(long)b * a.noise_ld + r];
+        else q = mmi_exp_noise(c_seed, c_step, c_pa, (unsigned)r);
         score = v / q;
         rank = r;
         tok = id;
@@ -2843,6 +2922,9 @@ struct TokArgs {
     const uint8_t* exec;   // [B]
     const int* delays;     // [NC]
     int B, NC, CT, dep_q, max_delay, card, text_card;
+    RowSamp* rows;         // [B] per-session sampling table (mmi_lm_set_row_sampling)
+    int* thist;            // [B][MMI_TEXT_HIST] ring of committed text tokens of the active rows
+    int text_pad, text_eop;   // with text_card (the start token): the ids the ring skips (lm_generate_multistream.rs:151-157)
 };
 
 // 1. write the user's codes at (offset+delay)%CT, 2. gather the model input at offset%CT with init-token substitution
@@ -2886,8 +2968,15 @@ __global__ void k_lm_commit(TokArgs t, const int* __restrict__ text_tok, const i
     const int pos = (int)(off_new % t.CT);
     int* rows = t.cache + (long)b * t.NC * t.CT;
     if (ex) {
-        rows[pos] = text_tok[b];
+        const int tt = text_tok[b];
+        rows[pos] = tt;
         for (int k = 0; k < t.dep_q; ++k) rows[(1 + k) * t.CT + pos] = audio_tok[(long)b * t.dep_q + k];
+        // the text history of an active row: the token the step stores (after forcing and after an on_text_hook)
+        if (t.rows[b].active && tt != t.text_pad && tt != t.text_eop && tt != t.text_card) {
+            const unsigned n = t.rows[b].hist_n;
+            t.thist[(long)b * MMI_TEXT_HIST + (int)(n & (unsigned)(MMI_TEXT_HIST - 1))] = tt;
+            t.rows[b].hist_n = n + 1u;
+        }
     }
     const bool hide = off_new <= (long)t.max_delay || !ex;
     for (int c = 0; c <= t.dep_q; ++c) {
@@ -2922,6 +3011,21 @@ __global__ void k_lm_reset(TokArgs t, const uint8_t* __restrict__ mask, uint8_t*
     if (mask && !mask[idx]) return;
     t.offsets[idx] = 0;           // lm.py:537-542; transformer.py:329-334 (KV end_offset, MHA offset)
     exec[idx] = 1;                // streaming.py:43-44
+    t.rows[idx].hist_n = 0u;      // the row keeps its sampling settings; its text history starts over
+}
+
+// mmi_lm_set_row_sampling / mmi_lm_clear_row_sampling: up to 16 entries ride in the kernel arguments, so the call is
+// stream-ordered without a host copy to wait for.  An entry with active == 0 returns the row to the handle's settings.
+struct RowSampSet {
+    RowSamp e[16];
+    int row[16];
+    int n;
+};
+__global__ void k_lm_set_rows(RowSamp* __restrict__ rows, RowSampSet set, int B) {
+    const int i = (int)threadIdx.x;
+    if (i >= set.n) return;
+    const int r = set.row[i];
+    if (r >= 0 && r < B) rows[r] = set.e[i];
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 from contextlib import contextmanager
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -166,6 +167,8 @@ class LMModel:
             else:
                 lib.check(lib.mmi_lm_create_ext(C.byref(cfg), C.byref(ext), descs, len(sd), max_batch, C.byref(self._handle)))
         del keep, sd
+        if self.config.existing_text_end_padding_id != 0:     # the one id of the text history's skip list that the cfg struct does not carry
+            lib.check(lib.mmi_lm_set_text_end_padding_id(self._handle, int(self.config.existing_text_end_padding_id)))
         self.max_batch = max_batch
         self.training = False
 
@@ -323,6 +326,48 @@ class LMModel:
     @property
     def ungenerated_token_id(self) -> int:
         return -2
+
+
+@dataclass
+class SessionSampling:
+    """One session's own sampling settings (the reference's Rust server reads them from each connection's query string,
+    rust/moshi-backend/src/stream_both.rs:95-105).  `seed` keys the session's own draw stream: its tokens do not depend on the
+    slot it runs in.  `pad_mult` biases the text padding token (0 = off), `repetition_penalty` (1 = off) applies to the distinct
+    tokens among the session's last `repetition_context` (<= 64, 0 = off) text tokens; both act on the text logits only."""
+    use_sampling: bool = True
+    temp: float = 0.8
+    temp_text: float = 0.7
+    top_k: int = 250
+    top_k_text: int = 25
+    seed: int = 0
+    pad_mult: float = 0.0
+    repetition_penalty: float = 1.0
+    repetition_context: int = 0
+
+    def to_c(self) -> "_capi.RowSampling":
+        r = _capi.RowSampling()
+        r.use_sampling = 1 if self.use_sampling else 0
+        r.temp, r.temp_text = float(self.temp), float(self.temp_text)
+        r.top_k, r.top_k_text = int(self.top_k), int(self.top_k_text)
+        r.seed = int(self.seed) & 0xFFFFFFFFFFFFFFFF
+        r.pad_mult, r.repetition_penalty = float(self.pad_mult), float(self.repetition_penalty)
+        r.repetition_context = int(self.repetition_context)
+        return r
+
+    def validate(self) -> None:
+        """The engine's own rules (mmi_row_sampling_check), restated so that a caller without a handle - the server, while it
+        parses a connection's query string - can refuse early with the same exception types."""
+        import math
+        if self.top_k > 256 or self.top_k_text > 256:
+            raise NotImplementedError("top_k > 256")
+        if self.top_k < 0 or self.top_k_text < 0:
+            raise ValueError("top_k must be >= 0 (0 = no top-k)")
+        if not 0 <= self.repetition_context <= 64:
+            raise ValueError("repetition_context must be in [0, 64]")
+        if not all(math.isfinite(float(v)) for v in (self.temp, self.temp_text, self.pad_mult, self.repetition_penalty)):
+            raise ValueError("per-session sampling settings must be finite")
+        if not self.repetition_penalty > 0:
+            raise ValueError("repetition_penalty must be > 0 (1 = off)")
 
 
 class LMGen:
@@ -486,6 +531,33 @@ class LMGen:
         assert self.is_streaming
         keep, ptr = self._mask_ptr(reset_mask)
         self._lib.check(self._lib.mmi_lm_reset(self.lm_model._handle, ptr, self._stream()))
+
+    # ---- per-session sampling (mmi_lm_set_row_sampling) --------------------------------------------
+    def _host_mask(self, mask):
+        if mask is None:
+            return None, None
+        m = [1 if bool(v) else 0 for v in (mask.tolist() if isinstance(mask, torch.Tensor) else mask)]
+        assert len(m) == self._batch
+        arr = (C.c_uint8 * len(m))(*m)
+        return arr, C.cast(arr, C.c_void_p)
+
+    def set_session_sampling(self, settings, mask=None) -> None:
+        """The masked sessions (all without a mask) sample with their own `SessionSampling` from the next step on: `settings` is
+        one for all of them or a sequence with one per session.  Their text history (repetition penalty) starts empty.  Stream
+        ordered; the launch list and a captured step graph stay as they are."""
+        assert self.is_streaming
+        if isinstance(settings, SessionSampling):
+            settings = [settings] * self._batch
+        assert len(settings) == self._batch, "one SessionSampling, or one per session"
+        rows = (_capi.RowSampling * self._batch)(*[x.to_c() for x in settings])
+        keep, ptr = self._host_mask(mask)
+        self._lib.check(self._lib.mmi_lm_set_row_sampling(self.lm_model._handle, ptr, rows, self._stream()))
+
+    def clear_session_sampling(self, mask=None) -> None:
+        """The masked sessions (all without a mask) sample with this LMGen's own settings and counter again."""
+        assert self.is_streaming
+        keep, ptr = self._host_mask(mask)
+        self._lib.check(self._lib.mmi_lm_clear_row_sampling(self.lm_model._handle, ptr, self._stream()))
 
     def get_streaming_state(self) -> dict:
         """streaming.py:158-166: the complete streaming state (a copy: one opaque device tensor + the host step counter)."""

@@ -139,6 +139,38 @@ class _Session:
     pending: np.ndarray = field(default_factory=lambda: np.zeros(0, np.float32))
 
 
+# The reference's per-connection query parameters (rust/moshi-backend/src/stream_both.rs:95-105) -> SessionSampling fields.  The
+# engine has ONE seed per session: `seed` (`text_seed` is accepted as a synonym, `audio_seed` is read and ignored).
+_QUERY_FIELDS = {"text_temperature": ("temp_text", float), "text_topk": ("top_k_text", int), "audio_temperature": ("temp", float),
+                 "audio_topk": ("top_k", int), "pad_mult": ("pad_mult", float), "repetition_penalty": ("repetition_penalty", float),
+                 "repetition_penalty_context": ("repetition_context", int), "seed": ("seed", int), "text_seed": ("seed", int)}
+
+
+def parse_session_query(query):
+    """A connection's query mapping -> `SessionSampling`, or None when it names none of the parameters (the connection then
+    samples with the batcher's settings, exactly as before).  ValueError / NotImplementedError for a value that does not parse
+    or that the engine would refuse."""
+    from .lm import SessionSampling
+    if not query:
+        return None
+    found = {}
+    for name, (attr, conv) in _QUERY_FIELDS.items():
+        if name in query:
+            if name == "text_seed" and "seed" in query:
+                continue
+            try:
+                found[attr] = conv(query[name])
+            except (TypeError, ValueError):
+                raise ValueError(f"query parameter {name}={query[name]!r} is not a valid {conv.__name__}") from None
+    if not found:
+        return None
+    if "seed" in found and not 0 <= found["seed"] < 2 ** 64:
+        raise ValueError("seed must fit 64 unsigned bits")
+    s = SessionSampling(**found)
+    s.validate()
+    return s
+
+
 class BatchedServer:
     """`SessionBatcher` behind the websocket protocol.  `text_piece(token_id) -> str | None` turns a text token into what the
     reference sends (sentencepiece `id_to_piece` with "▁" -> " ", tokens 0 and 3 dropped, server.py:92-99); the default sends the
@@ -213,20 +245,34 @@ class BatchedServer:
         from aiohttp import web
         ws = web.WebSocketResponse()
         await ws.prepare(request)
-        await self.serve_websocket(ws)
+        await self.serve_websocket(ws, request.query)
         return ws
 
-    async def serve_websocket(self, ws) -> None:
+    async def serve_websocket(self, ws, query=None) -> None:
         """Handshake, then audio in -> frames to the session's slot, frames out -> audio (+ text pieces).  A connection that
         finds every slot taken gets an Error message (MT=5) and is closed - the Rust server's behaviour; the reference's Python
-        server would make it wait on the lock."""
+        server would make it wait on the lock.  `query`: the connection URL's query mapping - text_temperature, text_topk,
+        audio_temperature, audio_topk, pad_mult, repetition_penalty, repetition_penalty_context, seed (stream_both.rs:95-105;
+        one seed per session: text_seed is a synonym, audio_seed is ignored) give the session its own sampling settings; a value
+        the engine would refuse closes the connection with an Error message before a slot is claimed."""
         import aiohttp
         if self.errors:                               # the model loop is gone: a new connection would get a slot and no frames
             await ws.send_bytes(encode_error(f"model loop failed: {self.errors[0]!r}"))
             await ws.close()
             return
         try:
-            channel = self.batcher.open()
+            sampling = parse_session_query(query)
+        except (ValueError, NotImplementedError) as e:
+            await ws.send_bytes(encode_error(f"bad sampling parameters: {e}"))
+            await ws.close()
+            return
+        open_channel = self.batcher.open if sampling is None else (lambda: self.batcher.open(sampling=sampling))
+        try:
+            channel = open_channel()
+        except (ValueError, NotImplementedError) as e:
+            await ws.send_bytes(encode_error(f"bad sampling parameters: {e}"))
+            await ws.close()
+            return
         except BufferError as e:
             await ws.send_bytes(encode_error(f"no free slot: {e}"))
             await ws.close()
@@ -281,7 +327,7 @@ class BatchedServer:
                         self._sessions.pop(channel, None)
                     self.batcher.close(channel)
                     try:
-                        channel = self.batcher.open()
+                        channel = open_channel()      # the connection's settings hold for its next dialogue too
                     except BufferError as e:          # another connection took the slot in between
                         await ws.send_bytes(encode_error(f"no free slot: {e}"))
                         await ws.close()

@@ -51,9 +51,12 @@ int main() {
     for (int V : {2048, 32000}) {
         const int k = V == 2048 ? 250 : 25;
         uint16_t *logits, *pre, *emb, *xo; int *out, *use_noise, *forced, *use_forced; float* noise; unsigned long long* rng;
+        RowSamp* rows; long* offsets;                  // the per-session table the engine always passes: all rows inactive, offsets 0
         CK(hipMalloc(&logits, (size_t)B * V * 2)); CK(hipMalloc(&pre, (size_t)B * 8 * 1024 * 2)); CK(hipMalloc(&emb, (size_t)(V + 1) * 1024 * 2));
         CK(hipMalloc(&xo, (size_t)64 * 1024 * 2)); CK(hipMalloc(&out, B * 4)); CK(hipMalloc(&use_noise, 4)); CK(hipMalloc(&forced, B * 4));
         CK(hipMalloc(&use_forced, 4)); CK(hipMalloc(&noise, (size_t)B * 256 * 4)); CK(hipMalloc(&rng, 16));
+        CK(hipMalloc(&rows, B * sizeof(RowSamp))); CK(hipMalloc(&offsets, B * sizeof(long)));
+        CK(hipMemset(rows, 0, B * sizeof(RowSamp))); CK(hipMemset(offsets, 0, B * sizeof(long)));
         CK(hipMemset(use_forced, 0, 4)); CK(hipMemset(forced, 0, B * 4)); CK(hipMemset(pre, 0, (size_t)B * 8 * 1024 * 2));
         CK(hipMemset(emb, 0, (size_t)(V + 1) * 1024 * 2)); CK(hipMemset(rng, 0, 16));
         std::vector<float> hn((size_t)B * 256, 1.0f); CK(hipMemcpy(noise, hn.data(), hn.size() * 4, hipMemcpyHostToDevice));
@@ -64,7 +67,7 @@ int main() {
                 SampleArgs a; memset(&a, 0, sizeof(a));
                 a.logits = logits; a.ld = V; a.V = V; a.k = k; a.temp = 0.8f; a.use_sampling = mode != 0;
                 a.noise = noise; a.noise_ld = 256; a.use_noise = use_noise; a.rng = rng; a.site = 1; a.out = out; a.out_stride = 1; a.B = B;
-                a.forced = forced; a.forced_stride = 1; a.use_forced = use_forced;
+                a.forced = forced; a.forced_stride = 1; a.use_forced = use_forced; a.rows = rows; a.offsets = offsets;
                 if (nx) { a.nx_pre = pre; a.nx_ld = 8 * 1024; a.nx_emb = emb; a.nx_out = xo; a.nx_D = 1024; a.nx_T = 32; a.nx_ksteps = 64; }
                 int un = mode == 2; CK(hipMemcpy(use_noise, &un, 4, hipMemcpyHostToDevice));
                 const double t = chain_us(s, n, [&](int) {
@@ -81,7 +84,7 @@ int main() {
             SampleArgs a; memset(&a, 0, sizeof(a));
             a.logits = logits; a.ld = V; a.V = V; a.k = k; a.temp = 0.8f; a.use_sampling = 1;
             a.noise = noise; a.noise_ld = 256; a.use_noise = use_noise; a.rng = rng; a.site = 1; a.out = out; a.out_stride = 1; a.B = B;
-            a.forced = forced; a.forced_stride = 1; a.use_forced = use_forced;
+            a.forced = forced; a.forced_stride = 1; a.use_forced = use_forced; a.rows = rows; a.offsets = offsets;
             a.nx_pre = pre; a.nx_ld = 8 * 1024; a.nx_emb = emb; a.nx_out = xo; a.nx_D = 1024; a.nx_T = 32; a.nx_ksteps = 64;
             int un = 0; CK(hipMemcpy(use_noise, &un, 4, hipMemcpyHostToDevice));
             for (int r = 0; r < 3; ++r) {
