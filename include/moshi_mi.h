@@ -330,6 +330,42 @@ int mmi_lm_clear_row_sampling(mmi_lm* lm, const uint8_t* mask_or_null, mmi_strea
  * argument of the commit kernel in the launch list.  An id outside [0, text_card] is MMI_ERR_INVALID. */
 int mmi_lm_set_text_end_padding_id(mmi_lm* lm, int32_t id);
 
+/* Per-session conditions and guidance strength (no counterpart in the reference's Python LMGen, which fixes them for the whole
+ * stream, lm.py:612-651; its Rust TTS server takes the voice's cross-attention source and the guidance strength from each
+ * request's query: rust/moshi-server/src/tts.rs:342-357).  A session of a live stream gets its own `sum` condition row, its own cross-attention source with its own length
+ * and its own guidance coefficient; under guidance a session is two model rows (b and batch + b) and the call fans out to the
+ * twin itself.
+ *   cfg_coef         1 = this session's sampling sites keep the conditioned logits untouched (the reference does not mix at 1,
+ *                    lm.py:727); != 1 only on a stream that was started with guidance (it has the twin rows)
+ *   condition_sum    device bf16 [R, dim] or NULL = keep; R = 1, or 2 on a guided stream (conditioned row first); only on a
+ *                    stream started with a condition_sum (it has the buffer)
+ *   condition_cross  device bf16 [R, cross_len, dim] or NULL = keep: projected through every temporal layer's key / value rows
+ *                    into the session's own slots, the same bits mmi_lm_streaming_start_guided gives the same positions
+ *   cross_len        1 .. capacity; read only with condition_cross.  Positions beyond a row's length are never read. */
+struct mmi_row_condition {
+    float cfg_coef;
+    const void* condition_sum;
+    const void* condition_cross;
+    int32_t cross_len;
+};
+typedef struct mmi_row_condition mmi_row_condition;
+/* Positions a row's cross-attention source may hold in the streams started after this call (the keys / values buffer of the
+ * streaming state is [layers][model rows][capacity][2 dim], so mmi_lm_state_bytes grows with it).  0 (the default) = the
+ * cross_len given at streaming_start, as before.  Not while streaming (MMI_ERR_STATE).  A streaming_start whose cross_len
+ * exceeds a capacity set here is refused with MMI_ERR_SHAPE.  mmi_lm_cross_capacity: the capacity of the live stream, or the
+ * value set here when not streaming (a negative status for a NULL handle). */
+int mmi_lm_set_cross_capacity(mmi_lm* lm, int32_t positions);
+int mmi_lm_cross_capacity(const mmi_lm* lm);
+/* Session `session` takes the condition *c from its next step on.  Stream-ordered on `stream`, no host synchronisation (the
+ * scalars travel as kernel arguments, the projection is enqueued), legal between any two steps; neither the launch list nor a
+ * captured graph changes.  The device buffers c names must stay valid until `stream` has passed the call.  streaming_start sets
+ * every session from mmi_guidance; mmi_lm_reset keeps a session's condition; a state snapshot carries conditions, lengths and
+ * coefficients.  Hooks, supplied noise and forced tokens are unaffected.  A refused call changes nothing: not streaming
+ * MMI_ERR_STATE; session outside [0, batch) or a non-finite cfg_coef MMI_ERR_INVALID; cfg_coef != 1 on a stream started without
+ * guidance, or condition_sum on a stream started without one, MMI_ERR_STATE; condition_cross on a model without
+ * cross-attention layers MMI_ERR_INVALID; cross_len outside [1, capacity] MMI_ERR_SHAPE. */
+int mmi_lm_set_row_condition(mmi_lm* lm, int32_t session, const mmi_row_condition* c, mmi_stream stream);
+
 /* LMGen.step (lm.py:785-791, 668-783).
  *   user_codes  i64 [batch, n_user(>= n_q - dep_q), 1]; extra rows are ignored (lm.py:688-689)
  *   out_tokens  i64 [batch, dep_q + 1, 1]; rows not yet valid hold -2 (lm.py:781-782)
@@ -514,9 +550,9 @@ typedef struct mmi_batcher_cfg {
     int32_t reset_codec_after_first_frame;  /* server.py:135-141: the first input frame's encoder state is dropped  */
     int32_t max_buffered_frames;            /* per-channel cap on queued input frames and on un-popped output frames */
     mmi_sampling sampling;                  /* LMGen constructor arguments (lm.py:557-574)                          */
-    mmi_guidance guidance;                  /* cfg_coef = 0 or 1: none.  Otherwise as mmi_lm_streaming_start_guided, shared by
-                                               every channel (server.py:53-54: one condition for the model type); the LM
-                                               handle then needs max_batch >= 2 * slots                               */
+    mmi_guidance guidance;                  /* cfg_coef = 0 or 1: none.  Otherwise as mmi_lm_streaming_start_guided: what every
+                                               channel gets that does not bring its own (mmi_batcher_open_cond; server.py:53-54:
+                                               one condition for the model type); the LM handle then needs max_batch >= 2 * slots */
 } mmi_batcher_cfg;
 
 typedef struct mmi_batcher_stats {
@@ -540,6 +576,23 @@ int mmi_batcher_open(mmi_batcher* b, int64_t* channel_id);
  * its first step.  NULL = mmi_batcher_open: the batcher's cfg.sampling (also for a slot whose last owner had settings).
  * Settings mmi_row_sampling_check refuses are refused here, and no slot is claimed. */
 int mmi_batcher_open_with(mmi_batcher* b, const mmi_row_sampling* settings_or_null, int64_t* channel_id);
+/* A channel's own condition (tts.rs:342-357: voice and guidance strength per request).  HOST memory, like everything else at
+ * this boundary; the fields are those of mmi_row_condition. */
+struct mmi_batcher_condition {
+    float cfg_coef;
+    const void* condition_sum;           /* host bf16 [R, dim] or NULL; R = 1, or 2 when the batcher runs guided */
+    const void* condition_cross;         /* host bf16 [R, cross_len, dim] or NULL */
+    int32_t cross_len;
+};
+typedef struct mmi_batcher_condition mmi_batcher_condition;
+/* mmi_batcher_open_with plus the channel's own condition.  The arrays are copied at once (the caller's may go away); at the next
+ * step the slot's rows get them (one host-to-device copy, then mmi_lm_set_row_condition on the batcher's stream) with the slot's
+ * reset, before the row's first step.  cond_or_null == NULL: the batcher's own cfg.guidance rows of that slot, also for a slot
+ * whose last owner had a condition (the batcher keeps a copy of them).  Room for sources longer than cfg.guidance.cross_len
+ * is a property of the LM handle: mmi_lm_set_cross_capacity before mmi_batcher_create.  A condition mmi_lm_set_row_condition
+ * would refuse is refused here with the same status, and no slot is claimed. */
+int mmi_batcher_open_cond(mmi_batcher* b, const mmi_row_sampling* settings_or_null, const mmi_batcher_condition* cond_or_null,
+                          int64_t* channel_id);
 int mmi_batcher_close(mmi_batcher* b, int64_t channel_id);
 /* Append 24 kHz mono PCM (host f32) to the channel's FIFO (batched_asr.rs:77-90 extend_data). */
 int mmi_batcher_push_pcm(mmi_batcher* b, int64_t channel_id, const float* pcm, int32_t n_samples);

@@ -69,6 +69,16 @@ class RowSampling(C.Structure):
                 ("repetition_context", C.c_int32)]
 
 
+class RowCondition(C.Structure):
+    """struct mmi_row_condition: one session's own condition and guidance coefficient (mmi_lm_set_row_condition); device pointers."""
+    _fields_ = [("cfg_coef", C.c_float), ("condition_sum", C.c_void_p), ("condition_cross", C.c_void_p), ("cross_len", C.c_int32)]
+
+
+class BatcherCondition(C.Structure):
+    """struct mmi_batcher_condition: the same for a batcher channel (mmi_batcher_open_cond); host pointers."""
+    _fields_ = [("cfg_coef", C.c_float), ("condition_sum", C.c_void_p), ("condition_cross", C.c_void_p), ("cross_len", C.c_int32)]
+
+
 class Guidance(C.Structure):
     _fields_ = [("cfg_coef", C.c_float), ("cfg_is_no_text", C.c_int32), ("cfg_is_masked_until", C.c_void_p),
                 ("condition_sum", C.c_void_p), ("condition_cross", C.c_void_p), ("cross_len", C.c_int32)]
@@ -147,6 +157,9 @@ SIGNATURES = {
     "mmi_lm_set_row_sampling": (C.c_int, [_P, _P, C.POINTER(RowSampling), _P]),
     "mmi_lm_clear_row_sampling": (C.c_int, [_P, _P, _P]),
     "mmi_lm_set_text_end_padding_id": (C.c_int, [_P, C.c_int32]),
+    "mmi_lm_set_cross_capacity": (C.c_int, [_P, C.c_int32]),
+    "mmi_lm_cross_capacity": (C.c_int, [_P]),
+    "mmi_lm_set_row_condition": (C.c_int, [_P, C.c_int32, C.POINTER(RowCondition), _P]),
     "mmi_lm_step": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32), _P]),
     "mmi_lm_force_next_tokens": (C.c_int, [_P, _P, _P]),
     "mmi_lm_set_phase_callback": (C.c_int, [_P, _P, _P]),
@@ -158,6 +171,7 @@ SIGNATURES = {
     "mmi_batcher_destroy": (None, [_P]),
     "mmi_batcher_open": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "mmi_batcher_open_with": (C.c_int, [_P, C.POINTER(RowSampling), C.POINTER(C.c_int64)]),
+    "mmi_batcher_open_cond": (C.c_int, [_P, C.POINTER(RowSampling), C.POINTER(BatcherCondition), C.POINTER(C.c_int64)]),
     "mmi_batcher_close": (C.c_int, [_P, C.c_int64]),
     "mmi_batcher_push_pcm": (C.c_int, [_P, C.c_int64, _P, C.c_int32]),
     "mmi_batcher_step": (C.c_int, [_P, C.POINTER(C.c_int32)]),
@@ -176,11 +190,14 @@ SIGNATURES = {
 
 _SINCE_ROW_SAMPLING = ("mmi_row_sampling_check", "mmi_lm_set_row_sampling", "mmi_lm_clear_row_sampling", "mmi_batcher_open_with",
                        "mmi_lm_set_text_end_padding_id")
+_SINCE_ROW_CONDITION = ("mmi_lm_set_cross_capacity", "mmi_lm_cross_capacity", "mmi_lm_set_row_condition", "mmi_batcher_open_cond")
 
 
 def _missing(name, path):
+    what = "per-session conditions" if name in _SINCE_ROW_CONDITION else "per-session sampling"
+
     def refuse(*_a):
-        raise RuntimeError(f"{path} does not export {name}: it was built before per-session sampling existed")
+        raise RuntimeError(f"{path} does not export {name}: it was built before {what} existed")
     return refuse
 
 
@@ -191,7 +208,7 @@ class Lib:
         self.path = Path(path)
         self.cdll = C.CDLL(str(self.path))
         for name, (res, args) in SIGNATURES.items():
-            if name in _SINCE_ROW_SAMPLING and not hasattr(self.cdll, name):
+            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION and not hasattr(self.cdll, name):
                 # an older build of the engine (MMI_LIB_PATH, A/B runs against a parent build): everything else works, these refuse
                 setattr(self, name, _missing(name, self.path))
                 continue

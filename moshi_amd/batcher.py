@@ -56,6 +56,7 @@ class SessionBatcher:
         # guidance / conditioning shared by every channel (server.py:53-54 builds ONE set of condition tensors per model type)
         keep = []
         rows = int(slots) * (2 if cfg_coef != 1.0 else 1)
+        self._rows = 2 if cfg_coef != 1.0 else 1            # model rows per session
         cfg.guidance.cfg_coef = float(cfg_coef)
         cfg.guidance.cfg_is_no_text = 1 if cfg_is_no_text else 0
         if cfg_is_masked_until is not None and cfg_coef != 1.0:
@@ -103,15 +104,41 @@ class SessionBatcher:
         self.close_all()
 
     # ---- channels ------------------------------------------------------------------------------------
-    def open(self, sampling=None) -> int:
+    def open(self, sampling=None, condition=None) -> int:
         """Claim a slot.  `sampling`: a `moshi_amd.SessionSampling` - the channel samples with its own settings and its own seeded
-        draw stream (the same tokens whichever slot it lands in); None = the batcher's settings.  Settings the engine refuses
-        raise here (ValueError / NotImplementedError) and claim no slot."""
+        draw stream (the same tokens whichever slot it lands in); None = the batcher's settings.  `condition`: a
+        `moshi_amd.SessionCondition` - the channel's own condition tensors (fused like the batcher's; two rows when the batcher
+        runs guided; a `cross` source of up to the model's `cross_capacity` positions) and guidance coefficient; None = the
+        batcher's own condition for that slot.  What the engine refuses raises here and claims no slot."""
         ch = C.c_int64(0)
-        if sampling is None:
+        if sampling is None and condition is None:
             self._lib.check(self._lib.mmi_batcher_open(self._handle, C.byref(ch)))
-        else:
+        elif condition is None:
             self._lib.check(self._lib.mmi_batcher_open_with(self._handle, C.byref(sampling.to_c()), C.byref(ch)))
+        else:
+            import torch
+            bc = _capi.BatcherCondition()
+            bc.cfg_coef = float(condition.cfg_coef)
+            keep = []
+            if condition.condition_tensors is not None:
+                fuser = self.lm_model.fuser
+                assert fuser is not None, "Model has no fuser"
+
+                def host(t):            # bf16 bits in host memory: the batcher copies them before the call returns
+                    t = t.detach().to(device="cpu", dtype=torch.bfloat16).contiguous()
+                    keep.append(t)
+                    return t.data_ptr()
+                cs = fuser.get_sum(condition.condition_tensors)
+                if cs is not None:
+                    assert cs.shape[0] == self._rows, "one condition row per model row of a session (2 when guided)"
+                    bc.condition_sum = host(cs.reshape(self._rows, self.lm_model.dim))
+                cx = fuser.get_cross(condition.condition_tensors)
+                if cx is not None:
+                    assert cx.shape[0] == self._rows and cx.dim() == 3 and cx.shape[2] == self.lm_model.dim, cx.shape
+                    bc.condition_cross = host(cx)
+                    bc.cross_len = int(cx.shape[1])
+            sp = C.byref(sampling.to_c()) if sampling is not None else None
+            self._lib.check(self._lib.mmi_batcher_open_cond(self._handle, sp, C.byref(bc), C.byref(ch)))
         return int(ch.value)
 
     def close(self, channel: int) -> None:

@@ -11,6 +11,7 @@
 // (this file uses nothing of the engines but include/moshi_mi.h), so it is also the worked example of driving the ABI.
 #include "mmi_common.h"
 
+#include <math.h>
 #include <deque>
 #include <mutex>
 
@@ -27,6 +28,10 @@ struct Channel {                 // batched_asr.rs:61-69
     bool pending_reset = false;  // opened since the last step: the row's streaming state is reset before it runs
     bool own_sampling = false;   // mmi_batcher_open_with: the row samples with `sampling` instead of the batcher's settings
     mmi_row_sampling sampling{};
+    bool own_cond = false;       // mmi_batcher_open_cond: the row gets this condition instead of the batcher's cfg.guidance
+    float coef = 1.f;
+    int cross_len = 0;
+    std::vector<uint16_t> cond_sum, cond_cross;   // bf16 [R][dim] / [R][cross_len][dim], copied at open; empty = keep
     long frames = 0;             // input frames consumed
     std::deque<float> in;        // PCM FIFO
     std::deque<OutFrame> out;
@@ -103,6 +108,18 @@ struct mmi_batcher {
     std::vector<int64_t> row_owner;   // channel id that owned each row when the current step started
     std::vector<uint8_t> m_set, m_clear;      // rows opened since the last step: with / without settings of their own
     std::vector<mmi_row_sampling> row_set;
+    // per-channel conditions (mmi_batcher_open_cond).  A slot's region of the three blocks below is [R][dim] sum rows, then
+    // [R][cross_cap][dim] source positions (packed at the channel's own length); R = model rows per session.
+    bool guided = false, has_sum = false, has_cross = false;
+    int R = 1, dim = 0, cross_cap = 0, cross_len0 = 0;
+    float coef0 = 1.f;
+    size_t cond_slot = 0;             // bf16 elements per slot region
+    uint16_t* h_cond = nullptr;       // pinned staging [B] regions
+    uint16_t* d_cond = nullptr;       // their device mirror
+    uint16_t* d_def = nullptr;        // cfg.guidance's own rows per slot, kept to give a slot back to a channel without a condition
+    struct CondPlan { int what; float coef; bool sum, cross; int len; bool prev; };   // prev: the slot's last owner had one too   // what: 0 nothing, 1 the channel's own, 2 cfg.guidance's again
+    std::vector<CondPlan> cond_plan;
+    std::vector<uint8_t> row_has_cond;   // the slot's rows currently hold a channel's own condition
     int64_t next_id = 1;
     mmi_batcher_stats stats;
 };
@@ -127,6 +144,9 @@ void release(mmi_batcher* b) {
     if (b->dev.down) hipFree(b->dev.down);
     if (b->d_codes) hipFree(b->d_codes);
     if (b->d_dec_codes) hipFree(b->d_dec_codes);
+    if (b->h_cond) hipHostFree(b->h_cond);
+    if (b->d_cond) hipFree(b->d_cond);
+    if (b->d_def) hipFree(b->d_def);
     if (b->ev_begin) hipEventDestroy(b->ev_begin);
     if (b->ev_end) hipEventDestroy(b->ev_end);
     if (b->stream) hipStreamDestroy(b->stream);
@@ -182,6 +202,36 @@ int create_impl(mmi_batcher* b) {
     b->m_set.assign(B, 0);
     b->m_clear.assign(B, 0);
     b->row_set.assign(B, mmi_row_sampling{});
+    // what a channel's own condition may be, and cfg.guidance's rows regrouped per slot (the caller's buffers may go away)
+    b->guided = guide && guide->cfg_coef != 1.f;
+    b->R = b->guided ? 2 : 1;
+    b->dim = lc.dim;
+    b->coef0 = guide ? guide->cfg_coef : 1.f;
+    b->has_sum = guide && guide->condition_sum;
+    b->has_cross = lc.cross_attention != 0;
+    b->cross_len0 = b->has_cross ? guide->cross_len : 0;
+    b->cross_cap = b->has_cross ? mmi_lm_cross_capacity(b->lm) : 0;
+    b->cond_slot = (size_t)b->R * b->dim * (1 + (size_t)b->cross_cap);
+    b->cond_plan.assign(B, mmi_batcher::CondPlan{0, 1.f, false, false, 0, false});
+    b->row_has_cond.assign(B, 0);
+    if (b->has_sum || b->has_cross) {
+        const size_t bytes = (size_t)B * b->cond_slot * sizeof(uint16_t), D = (size_t)b->dim;
+        MMI_HIP_CHECK(hipHostMalloc((void**)&b->h_cond, bytes, 0));
+        MMI_HIP_CHECK(hipMalloc((void**)&b->d_cond, bytes));
+        MMI_HIP_CHECK(hipMalloc((void**)&b->d_def, bytes));
+        const uint16_t* gs = reinterpret_cast<const uint16_t*>(guide->condition_sum);
+        const uint16_t* gx = reinterpret_cast<const uint16_t*>(guide->condition_cross);
+        for (int r = 0; r < B; ++r)
+            for (int t = 0; t < b->R; ++t) {     // model row t * B + r
+                uint16_t* reg = b->d_def + (size_t)r * b->cond_slot;
+                if (b->has_sum)
+                    MMI_HIP_CHECK(hipMemcpyAsync(reg + t * D, gs + ((size_t)t * B + r) * D, D * sizeof(uint16_t), hipMemcpyDeviceToDevice, b->stream));
+                if (b->has_cross)
+                    MMI_HIP_CHECK(hipMemcpyAsync(reg + b->R * D + (size_t)t * b->cross_len0 * D, gx + ((size_t)t * B + r) * b->cross_len0 * D,
+                                                 (size_t)b->cross_len0 * D * sizeof(uint16_t), hipMemcpyDeviceToDevice, b->stream));
+            }
+        MMI_HIP_CHECK(hipStreamSynchronize(b->stream));
+    }
     memset(&b->stats, 0, sizeof(b->stats));
     b->stats.total_slots = B;
     return MMI_OK;
@@ -216,10 +266,23 @@ extern "C" void mmi_batcher_destroy(mmi_batcher* b) {
 extern "C" int mmi_batcher_open(mmi_batcher* b, int64_t* channel_id) { return mmi_batcher_open_with(b, nullptr, channel_id); }
 
 extern "C" int mmi_batcher_open_with(mmi_batcher* b, const mmi_row_sampling* settings, int64_t* channel_id) {
+    return mmi_batcher_open_cond(b, settings, nullptr, channel_id);
+}
+
+extern "C" int mmi_batcher_open_cond(mmi_batcher* b, const mmi_row_sampling* settings, const mmi_batcher_condition* cond, int64_t* channel_id) {
     MmiDeviceGuard dev_guard_(b ? mmi_lm_device(b->lm) : -1);
     if (!b || !channel_id) return mmi_fail(MMI_ERR_INVALID, "null argument");
     int rc;
     if (settings && (rc = mmi_row_sampling_check(settings))) return rc;
+    if (cond) {     // what mmi_lm_set_row_condition would refuse at the step, refused now: no slot is claimed
+        if (!std::isfinite(cond->cfg_coef)) return mmi_fail(MMI_ERR_INVALID, "cfg_coef must be finite");
+        if (cond->cfg_coef != 1.f && !b->guided) return mmi_fail(MMI_ERR_STATE, "cfg_coef != 1 needs a batcher created with guidance");
+        if (cond->condition_sum && !b->has_sum) return mmi_fail(MMI_ERR_STATE, "the batcher was created without a sum condition");
+        if (cond->condition_cross && !b->has_cross)
+            return mmi_fail(MMI_ERR_INVALID, "a cross-attention condition was given to a model without cross-attention layers");
+        if (cond->condition_cross && (cond->cross_len < 1 || cond->cross_len > b->cross_cap))
+            return mmi_fail(MMI_ERR_SHAPE, "cross_len outside [1, capacity] (mmi_lm_set_cross_capacity before mmi_batcher_create)");
+    }
     std::lock_guard<std::mutex> g(b->mu);
     for (auto& c : b->channels) {
         if (c.live) continue;
@@ -227,6 +290,20 @@ extern "C" int mmi_batcher_open_with(mmi_batcher* b, const mmi_row_sampling* set
         c.live = true;
         c.pending_reset = true;
         if (settings) { c.own_sampling = true; c.sampling = *settings; }
+        if (cond) {
+            c.own_cond = true;
+            c.coef = cond->cfg_coef;
+            const size_t D = (size_t)b->dim;
+            if (cond->condition_sum) {
+                const uint16_t* p = reinterpret_cast<const uint16_t*>(cond->condition_sum);
+                c.cond_sum.assign(p, p + b->R * D);
+            }
+            if (cond->condition_cross) {
+                const uint16_t* p = reinterpret_cast<const uint16_t*>(cond->condition_cross);
+                c.cross_len = cond->cross_len;
+                c.cond_cross.assign(p, p + (size_t)b->R * c.cross_len * D);
+            }
+        }
         c.id = b->next_id++;
         *channel_id = c.id;
         b->stats.used_slots += 1;
@@ -279,7 +356,19 @@ extern "C" int mmi_batcher_step(mmi_batcher* b, int32_t* n_active) {
                 b->m_set[r] = c.own_sampling ? 1 : 0;
                 b->m_clear[r] = c.own_sampling ? 0 : 1;
                 if (c.own_sampling) { b->row_set[r] = c.sampling; ++sets; }
-            } else b->m_set[r] = b->m_clear[r] = 0;
+                mmi_batcher::CondPlan& cp = b->cond_plan[r];
+                cp.what = c.own_cond ? 1 : (b->row_has_cond[r] ? 2 : 0);
+                cp.prev = b->row_has_cond[r] != 0;
+                if (c.own_cond) {       // into the slot's pinned region (the last step's copy out of it has completed)
+                    uint16_t* reg = b->h_cond ? b->h_cond + (size_t)r * b->cond_slot : nullptr;
+                    cp.coef = c.coef; cp.sum = !c.cond_sum.empty(); cp.cross = !c.cond_cross.empty(); cp.len = c.cross_len;
+                    if (cp.sum) std::copy(c.cond_sum.begin(), c.cond_sum.end(), reg);
+                    if (cp.cross) std::copy(c.cond_cross.begin(), c.cond_cross.end(), reg + (size_t)b->R * b->dim);
+                    c.cond_sum = std::vector<uint16_t>();
+                    c.cond_cross = std::vector<uint16_t>();
+                }
+                b->row_has_cond[r] = c.own_cond ? 1 : 0;
+            } else { b->m_set[r] = b->m_clear[r] = 0; b->cond_plan[r].what = 0; }
             if (c.live && c.in.size() >= (size_t)F) {
                 std::copy(c.in.begin(), c.in.begin() + F, dst);
                 c.in.erase(c.in.begin(), c.in.begin() + F);
@@ -307,6 +396,28 @@ extern "C" int mmi_batcher_step(mmi_batcher* b, int32_t* n_active) {
         // the new owner's sampling settings: its own (open_with), or the batcher's again whatever the slot's last owner had
         if (resets > sets && (rc = mmi_lm_clear_row_sampling(b->lm, b->m_clear.data(), s))) return rc;
         if (sets && (rc = mmi_lm_set_row_sampling(b->lm, b->m_set.data(), b->row_set.data(), s))) return rc;
+        // the new owner's condition: its own (open_cond), or cfg.guidance's again if the slot's last owner had one
+        for (int r = 0; r < B; ++r) {
+            const mmi_batcher::CondPlan& cp = b->cond_plan[r];
+            if (!cp.what) continue;
+            const size_t off = (size_t)r * b->cond_slot, sum_n = (size_t)b->R * b->dim;
+            mmi_row_condition rc_;
+            if (cp.what == 1) {
+                const size_t n = cp.cross ? sum_n + (size_t)b->R * cp.len * b->dim : (cp.sum ? sum_n : 0);
+                if (n) MMI_HIP_CHECK(hipMemcpyAsync(b->d_cond + off, b->h_cond + off, n * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+                rc_.cfg_coef = cp.coef;
+                // a part the channel does not bring is cfg.guidance's: kept, or given back if the slot's last owner had replaced it
+                rc_.condition_sum = cp.sum ? b->d_cond + off : (cp.prev && b->has_sum ? b->d_def + off : nullptr);
+                rc_.condition_cross = cp.cross ? b->d_cond + off + sum_n : (cp.prev && b->has_cross ? b->d_def + off + sum_n : nullptr);
+                rc_.cross_len = cp.cross ? cp.len : b->cross_len0;
+            } else {
+                rc_.cfg_coef = b->coef0;
+                rc_.condition_sum = b->has_sum ? b->d_def + off : nullptr;
+                rc_.condition_cross = b->has_cross ? b->d_def + off + sum_n : nullptr;
+                rc_.cross_len = b->cross_len0;
+            }
+            if ((rc = mmi_lm_set_row_condition(b->lm, r, &rc_, s))) return rc;
+        }
     }
     if (active == 0) {
         MMI_HIP_CHECK(hipStreamSynchronize(s));

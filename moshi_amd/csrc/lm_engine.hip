@@ -87,8 +87,12 @@ struct mmi_lm {
     int cfg_no_text = 0;
     int* masked_until = nullptr;    // [gen_batch] or null
     uint16_t* cond = nullptr;       // [batch][dim] summed `sum` conditions (lm.py:621-628) or null
-    uint16_t* xkv = nullptr;        // [layers][batch * cross_len][2 * dim] keys | values of the cross-attention source
-    int cross_len = 0;
+    uint16_t* xkv = nullptr;        // [layers][batch][cross_cap][2 * dim] keys | values of every model row's cross-attention source
+    int cross_len = 0;              // mmi_guidance.cross_len of the stream's start
+    int cross_cap = 0;              // positions a row's source may hold for this stream (cross_cap_set, or cross_len)
+    int cross_cap_set = 0;          // mmi_lm_set_cross_capacity; 0 = the start's cross_len
+    int* xlen = nullptr;            // [batch] live positions per model row (k_lm_cross_attn), null without cross-attention
+    float* coefs = nullptr;         // [gen_batch] guidance coefficient per session (k_cfg_mix)
     long* offsets_m = nullptr;      // [batch] offsets per model row (== offsets without guidance)
     std::vector<uint16_t*> extra_heads;   // nn.Linear(dim, extra_heads_dim) weights, row-major
     uint16_t* extra_heads_all = nullptr;
@@ -804,9 +808,9 @@ void add_sample(mmi_lm* lm, uint16_t* logits, int ld, int V, bool text, int site
     const bool guided = lm->cfg_coef != 1.f;
     if (guided && !(text && lm->cfg_no_text)) {     // lm.py:727-733 (text; `cfg_is_no_text` keeps the conditioned logits), 828-832
         const int G = lm->gen_batch;
-        const float coef = lm->cfg_coef;
+        const float* coefs = lm->coefs;
         lm->prog.add([=](hipStream_t s) {
-            MMI_LAUNCH(k_cfg_mix, dim3(mmi_cdiv(V, 256), G), 256, 0, s, logits, ld, V, G, coef);
+            MMI_LAUNCH(k_cfg_mix, dim3(mmi_cdiv(V, 256), G), 256, 0, s, logits, ld, V, G, coefs);
             MMI_CHECK_LAUNCH();
             return (int)MMI_OK;
         });
@@ -1032,8 +1036,8 @@ int build_program(mmi_lm* lm) {
             P.site("L.cross_attn");
             {
                 CrossAttnArgs ca;
-                ca.q = lm->qrot; ca.kv = lm->xkv + (size_t)l * B * lm->cross_len * 2 * d; ca.out = lm->att;
-                ca.B = B; ca.H = H; ca.Dh = Dh; ca.Tc = lm->cross_len; ca.T = lm->T; ca.out_ksteps = packed_ksteps(lm, d);
+                ca.q = lm->qrot; ca.kv = lm->xkv + (size_t)l * B * lm->cross_cap * 2 * d; ca.out = lm->att;
+                ca.len = lm->xlen; ca.B = B; ca.H = H; ca.Dh = Dh; ca.cap = lm->cross_cap; ca.T = lm->T; ca.out_ksteps = packed_ksteps(lm, d);
                 P.add([=](hipStream_t s) {
                     MMI_LAUNCH(k_lm_cross_attn, B * H, 64, 0, s, ca);
                     MMI_CHECK_LAUNCH();
@@ -1166,10 +1170,14 @@ int build_program(mmi_lm* lm) {
 }
 
 // keys | values of the cross-attention source for every temporal layer (transformer.py:495-505: `linear(src, in_proj.weight[dim:])`,
-// bf16), once per stream: the source's rows*T_c positions go through the weight-streaming GEMM as batches of T "sessions"
-int project_cross_source(mmi_lm* lm, const uint16_t* src, hipStream_t s) {
+// bf16): the `ncol` source positions src [ncol][dim] land in slots [slot0, slot0 + ncol) of every layer's [batch * cross_cap]
+// slots, through the weight-streaming GEMM as batches of T "sessions".  At streaming_start with cap == cross_len that is every
+// row at once; otherwise, and for mmi_lm_set_row_condition, one model row's positions into that row's slots.  A position's
+// keys / values do not depend on its column in the tile nor on the tile's fill (every launch has mt = 1), so both give the same bits.
+int project_cross_source(mmi_lm* lm, const uint16_t* src, size_t slot0, int ncol, hipStream_t s) {
     const mmi_lm_cfg& c = lm->cfg;
-    const int d = c.dim, T = lm->T, ncol = lm->batch * lm->cross_len, ksteps = packed_ksteps(lm, d);
+    const int d = c.dim, T = lm->T, ksteps = packed_ksteps(lm, d);
+    const size_t slots = (size_t)lm->batch * lm->cross_cap;
     uint16_t* xp = lm->xn;                                        // packed scratch of >= one batch tile
     for (int col0 = 0; col0 < ncol; col0 += T) {
         const int n = ncol - col0 < T ? ncol - col0 : T;
@@ -1180,7 +1188,7 @@ int project_cross_source(mmi_lm* lm, const uint16_t* src, hipStream_t s) {
             GemmArgs a;
             memset(&a, 0, sizeof(a));
             a.xp = reinterpret_cast<const u32x4*>(xp);
-            a.out = lm->xkv + ((size_t)l * ncol + col0) * 2 * d;
+            a.out = lm->xkv + ((size_t)l * slots + slot0 + col0) * 2 * d;
             a.epi = MMI_EPI_STORE; a.B = n; a.out_mode = MMI_OUT_ROWMAJOR; a.out_ld = 2 * d; a.out_ksteps = ksteps;
             a.tok_rows = n;
             int rc = launch_gemm(lm, s, lm->layers[l].x_kv, a, false);
@@ -1518,13 +1526,19 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
     if (guided) ok &= hipSuccess == A.alloc(&lm->offsets_m, (size_t)B);
     if (guided && guide->cfg_is_masked_until) ok &= hipSuccess == A.alloc(&lm->masked_until, (size_t)G);
     if (guide && guide->condition_sum) ok &= hipSuccess == A.alloc(&lm->cond, (size_t)B * d);
+    ok &= hipSuccess == A.alloc(&lm->coefs, (size_t)G);
     lm->xkv = nullptr;
-    lm->cross_len = 0;
+    lm->xlen = nullptr;
+    lm->cross_len = lm->cross_cap = 0;
     if (c.cross_attention) {
         if (!guide || !guide->condition_cross || guide->cross_len <= 0)
             return fail(mmi_fail(MMI_ERR_INVALID, "the model has cross-attention layers: mmi_guidance.condition_cross is required"));   // transformer.py:793-795
+        if (lm->cross_cap_set && lm->cross_cap_set < guide->cross_len)
+            return fail(mmi_fail(MMI_ERR_SHAPE, "mmi_guidance.cross_len exceeds the capacity set with mmi_lm_set_cross_capacity"));
         lm->cross_len = guide->cross_len;
-        ok &= hipSuccess == A.alloc(&lm->xkv, (size_t)c.num_layers * B * lm->cross_len * 2 * d);
+        lm->cross_cap = lm->cross_cap_set ? lm->cross_cap_set : lm->cross_len;
+        ok &= hipSuccess == A.alloc(&lm->xkv, (size_t)c.num_layers * B * lm->cross_cap * 2 * d);
+        ok &= hipSuccess == A.alloc(&lm->xlen, (size_t)B);
     } else if (guide && guide->condition_cross) {
         return fail(mmi_fail(MMI_ERR_INVALID, "a cross-attention condition was given to a model without cross-attention layers"));
     }
@@ -1627,9 +1641,23 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
     MMI_HIP_CHECK(hipMemsetAsync(lm->audio_tok, 0, (size_t)G * c.dep_q * sizeof(int), s));
     unsigned long long r0[2] = {sampling->seed, 0ull};
     MMI_HIP_CHECK(hipMemcpyAsync(lm->rng, r0, sizeof(r0), hipMemcpyHostToDevice, s));
+    {   // every session starts with the stream's coefficient and, on a cross-attention model, the start's length
+        std::vector<float> cf(G, lm->cfg_coef);
+        MMI_HIP_CHECK(hipMemcpy(lm->coefs, cf.data(), G * sizeof(float), hipMemcpyHostToDevice));
+    }
+    if (lm->xlen) MMI_LAUNCH(k_fill_i32, mmi_cdiv(B, 256), 256, 0, s, lm->xlen, lm->cross_len, (long)B);
     MMI_CHECK_LAUNCH();
     int rc = 0;
-    if (lm->xkv && (rc = project_cross_source(lm, reinterpret_cast<const uint16_t*>(guide->condition_cross), s))) return fail(rc);
+    if (lm->xkv) {
+        const uint16_t* src = reinterpret_cast<const uint16_t*>(guide->condition_cross);
+        if (lm->cross_cap == lm->cross_len) rc = project_cross_source(lm, src, 0, B * lm->cross_len, s);
+        else {      // slots [cross_len, cap) of a row are never read before mmi_lm_set_row_condition fills them: zero for the snapshot's sake
+            MMI_HIP_CHECK(hipMemsetAsync(lm->xkv, 0, (size_t)c.num_layers * B * lm->cross_cap * 2 * d * sizeof(uint16_t), s));
+            for (int r = 0; r < B && !rc; ++r)
+                rc = project_cross_source(lm, src + (size_t)r * lm->cross_len * d, (size_t)r * lm->cross_cap, lm->cross_len, s);
+        }
+        if (rc) return fail(rc);
+    }
     rc = build_program(lm);
     if (rc) return fail(rc);
     MMI_HIP_CHECK(hipStreamSynchronize(s));
@@ -1719,6 +1747,55 @@ extern "C" int mmi_lm_set_row_sampling(mmi_lm* lm, const uint8_t* mask, const mm
     for (int b = 0; b < lm->gen_batch; ++b)            // all or nothing: a refused call changes no row
         if (!mask || mask[b]) { int rc = mmi_row_sampling_check(&rows[b]); if (rc) return rc; }
     return write_rows(lm, mask, rows, (hipStream_t)stream);
+}
+
+// ---- per-session conditions ---------------------------------------------------------------------------------------------------
+extern "C" int mmi_lm_set_cross_capacity(mmi_lm* lm, int32_t positions) {
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (lm->streaming) return mmi_fail(MMI_ERR_STATE, "the capacity sizes the stream's keys / values buffer: set it before streaming_start");
+    if (positions < 0) return mmi_fail(MMI_ERR_INVALID, "capacity must be >= 0 (0 = the start's cross_len)");
+    lm->cross_cap_set = positions;
+    return MMI_OK;
+}
+
+extern "C" int mmi_lm_cross_capacity(const mmi_lm* lm) {
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    return lm->streaming ? lm->cross_cap : lm->cross_cap_set;
+}
+
+extern "C" int mmi_lm_set_row_condition(mmi_lm* lm, int32_t session, const mmi_row_condition* c, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm || !c) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (!lm->streaming) return mmi_fail(MMI_ERR_STATE, "not streaming");
+    if (session < 0 || session >= lm->gen_batch) return mmi_fail(MMI_ERR_INVALID, "session outside [0, batch)");
+    if (!std::isfinite(c->cfg_coef)) return mmi_fail(MMI_ERR_INVALID, "cfg_coef must be finite");
+    const bool guided = lm->batch > lm->gen_batch;
+    if (c->cfg_coef != 1.f && !guided)
+        return mmi_fail(MMI_ERR_STATE, "cfg_coef != 1 needs a stream started with guidance (two model rows per session)");
+    if (c->condition_sum && !lm->cond)
+        return mmi_fail(MMI_ERR_STATE, "the stream was started without a sum condition: it has no buffer for one");
+    if (c->condition_cross && !lm->cfg.cross_attention)
+        return mmi_fail(MMI_ERR_INVALID, "a cross-attention condition was given to a model without cross-attention layers");
+    if (c->condition_cross && (c->cross_len < 1 || c->cross_len > lm->cross_cap))
+        return mmi_fail(MMI_ERR_SHAPE, "cross_len outside [1, capacity] (mmi_lm_set_cross_capacity)");
+    hipStream_t s = (hipStream_t)stream;
+    const int G = lm->gen_batch, d = lm->cfg.dim, R = guided ? 2 : 1;
+    if (c->condition_cross) {       // the session's row(s): positions [0, cross_len) of their own slots; nothing else is touched
+        const uint16_t* src = reinterpret_cast<const uint16_t*>(c->condition_cross);
+        const long counted = lm->xlds_launches;       // mmi_lm_stat(lm, 0) counts the step's launches, not these
+        for (int r = 0; r < R; ++r) {
+            int rc = project_cross_source(lm, src + (size_t)r * c->cross_len * d, (size_t)(r * G + session) * lm->cross_cap, c->cross_len, s);
+            if (rc) return rc;
+        }
+        lm->xlds_launches = counted;
+    }
+    RowCondSet set;
+    memset(&set, 0, sizeof(set));
+    set.session = session; set.G = G; set.rows = R; set.len = c->condition_cross ? c->cross_len : 0; set.coef = c->cfg_coef;
+    set.sum = reinterpret_cast<const uint16_t*>(c->condition_sum); set.D = d;
+    MMI_LAUNCH(k_lm_set_row_cond, mmi_cdiv(c->condition_sum ? d : 1, 256), 256, 0, s, lm->xlen, lm->coefs, lm->cond, set);
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
 }
 
 extern "C" int mmi_lm_set_text_end_padding_id(mmi_lm* lm, int32_t id) {

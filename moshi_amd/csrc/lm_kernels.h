@@ -1450,15 +1450,18 @@ __global__ void k_unpack_rows(const uint16_t* __restrict__ xp, int B, int D, uin
     dst[idx] = xp[mmi_xp_index(T, r, k, ksteps)];
 }
 
-// Cross-attention of the one new query per (model row, head) over the T_c projected condition positions (transformer.py:
-// 544-552, 584: no mask, no rope, keys / values fixed for the stream).  kv: [rows][T_c][2 * H * Dh] bf16 (keys, then values, as
-// the in_proj's rows dim.. produce them); q: [rows][H * Dh] bf16.  One wave per (row, head); lane (r, c) = position slot r x
-// 16-byte chunk c of the head; online softmax per slot, slots merged at the end.
+// Cross-attention of the one new query per (model row, head) over the row's own len[b] projected condition positions
+// (transformer.py:544-552, 584: no mask, no rope; keys / values change only with mmi_lm_set_row_condition).  kv: [rows][cap][2 * H *
+// Dh] bf16 (keys, then values, as the in_proj's rows dim.. produce them), cap = the stream's capacity in positions; q: [rows][H *
+// Dh] bf16.  One wave per (row, head); lane (r, c) = position slot r x 16-byte chunk c of the head; online softmax per slot,
+// slots merged at the end.  len[b] is the same for the whole wave (one scalar load, no divergence on it); positions >= len[b]
+// are never read, so what an earlier owner of the row left there does not matter.  1 <= len[b] <= cap.
 struct CrossAttnArgs {
     const uint16_t* q;
     const uint16_t* kv;
     uint16_t* out;          // packed (T, out_ksteps) operand of the cross out_proj, feature = h*Dh + d
-    int B, H, Dh, Tc;
+    const int* len;         // [B] live positions per model row
+    int B, H, Dh, cap;
     int T, out_ksteps;
 };
 
@@ -1476,10 +1479,11 @@ __global__ __launch_bounds__(64) void k_lm_cross_attn(CrossAttnArgs a) {
     float m_run = -INFINITY, l_run = 0.f, acc[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) acc[e] = 0.f;
-    for (int t0 = 0; t0 < a.Tc; t0 += RP) {
+    const int L = a.len[b];
+    for (int t0 = 0; t0 < L; t0 += RP) {
         const int t = t0 + r;
-        const bool live = t < a.Tc;
-        const uint16_t* row = a.kv + ((long)b * a.Tc + (live ? t : a.Tc - 1)) * 2 * HD + h * Dh + 8 * c;
+        const bool live = t < L;
+        const uint16_t* row = a.kv + ((long)b * a.cap + (live ? t : L - 1)) * 2 * HD + h * Dh + 8 * c;
         const u32x4 kv = *reinterpret_cast<const u32x4*>(row), vv = *reinterpret_cast<const u32x4*>(row + HD);
         float d = 0.f;
 #pragma unroll
@@ -3028,6 +3032,27 @@ __global__ void k_lm_set_rows(RowSamp* __restrict__ rows, RowSampSet set, int B)
     if (r >= 0 && r < B) rows[r] = set.e[i];
 }
 
+// mmi_lm_set_row_condition: one session's cross-attention length, guidance coefficient and `sum` condition row(s); like
+// k_lm_set_rows the scalars ride in the kernel arguments.  Under guidance (rows == 2) the session's twin G + b follows it.
+// len / sum null: keep.  One workgroup per 256 features; the first thread of the first also writes the scalars.
+struct RowCondSet {
+    int session, G, rows;       // rows: model rows of a session (1, or 2 on a guided stream)
+    int len;                    // 0 = keep
+    float coef;
+    const uint16_t* sum;        // [rows][D] or null = keep
+    int D;
+};
+__global__ void k_lm_set_row_cond(int* __restrict__ len, float* __restrict__ coefs, uint16_t* __restrict__ cond, RowCondSet set) {
+    const int d = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (d == 0) {
+        coefs[set.session] = set.coef;
+        if (len && set.len > 0)
+            for (int r = 0; r < set.rows; ++r) len[r * set.G + set.session] = set.len;
+    }
+    if (cond && set.sum && d < set.D)
+        for (int r = 0; r < set.rows; ++r) cond[(long)(r * set.G + set.session) * set.D + d] = set.sum[(long)r * set.D + d];
+}
+
 // ------------------------------------------------------------------------------------------------
 // classifier-free guidance (lm.py:646-665, 712-733, 823-832) and extra heads (lm.py:793-807)
 // ------------------------------------------------------------------------------------------------
@@ -3062,12 +3087,15 @@ __global__ void k_lm_cfg_twins(TokArgs t, int* __restrict__ tokens, const int* _
     }
 }
 
-// logits[b] <- logits_null + (logits - logits_null) * coef, each operation on bf16 tensors (lm.py:733, 830-832);
-// logits rows [0,G) conditioned, [G,2G) unconditioned; the mix lands in row b, which the sampler and the taps then read
-__global__ void k_cfg_mix(uint16_t* __restrict__ logits, int ld, int V, int G, float coef) {
+// logits[b] <- logits_null + (logits - logits_null) * coef[b], each operation on bf16 tensors (lm.py:733, 830-832);
+// logits rows [0,G) conditioned, [G,2G) unconditioned; the mix lands in row b, which the sampler and the taps then read.
+// coefs [G]: one coefficient per session (mmi_lm_set_row_condition).  A session at coefficient 1 keeps its conditioned logits
+// as they are - the reference does not mix there (lm.py:727), and n + bf16(bf16(l - n) * 1) is not l.
+__global__ void k_cfg_mix(uint16_t* __restrict__ logits, int ld, int V, int G, const float* __restrict__ coefs) {
     const int b = blockIdx.y;
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (i >= V) return;
+    const float coef = coefs[b];
+    if (i >= V || coef == 1.f) return;
     uint16_t* c = logits + (long)b * ld + i;
     const float l = mmi_bf16_to_f32(*c), n = mmi_bf16_to_f32(logits[(long)(G + b) * ld + i]);
     const float d = mmi_round_bf16(l - n);

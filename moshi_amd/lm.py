@@ -120,7 +120,8 @@ class LMModel:
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], config: Optional[LMConfig] = None,
                  device: torch.device | str = "cuda", max_batch: int = 32, lib: Optional[_capi.Lib] = None,
-                 quantize: bool | str = False, fuser: Optional[ConditionFuser] = None, kv_cache: Optional[str] = None):
+                 quantize: bool | str = False, fuser: Optional[ConditionFuser] = None, kv_cache: Optional[str] = None,
+                 cross_capacity: Optional[int] = None):
         self.config = config or LMConfig()
         if kv_cache is not None:         # "fp8": e4m3 KV ring (half the attention stream); default: the config's (bf16)
             from dataclasses import replace
@@ -171,6 +172,8 @@ class LMModel:
             lib.check(lib.mmi_lm_set_text_end_padding_id(self._handle, int(self.config.existing_text_end_padding_id)))
         self.max_batch = max_batch
         self.training = False
+        if cross_capacity is not None:
+            self.set_cross_capacity(cross_capacity)
 
     def __del__(self):
         try:
@@ -181,6 +184,12 @@ class LMModel:
                 self._handle = C.c_void_p()
         except Exception:
             pass
+
+    def set_cross_capacity(self, positions: Optional[int]) -> None:
+        """Positions a session's cross-attention source may hold in the streams started from now on (`LMModel(cross_capacity=)`):
+        room for `LMGen.set_session_condition` / `SessionBatcher.open(condition=)` to bring a longer source than the one the
+        stream starts with.  None or 0 = the length of the start's source.  Not while streaming."""
+        self._lib.check(self._lib.mmi_lm_set_cross_capacity(self._handle, int(positions or 0)))
 
     def enable_hidden_taps(self, on: bool = True) -> None:
         """Parity tap (tests): every step of the NEXT `LMGen.streaming()` also keeps the residual stream after the first and
@@ -370,6 +379,17 @@ class SessionSampling:
             raise ValueError("repetition_penalty must be > 0 (1 = off)")
 
 
+@dataclass
+class SessionCondition:
+    """One session's own condition and guidance strength (the reference's Rust TTS server takes the voice source and `cfg_alpha`
+    from each request, rust/moshi-server/src/tts.rs:342-357).  `condition_tensors`: as for `LMGen`, fused through the model's
+    fuser - one row, or two (conditioned, then unconditioned) on a stream under guidance; None keeps what the session has.  A
+    `cross` source may have any length up to the model's `cross_capacity`.  `cfg_coef` 1 = the session's sampling sites keep the
+    conditioned logits untouched; another value needs a stream that was started with guidance."""
+    cfg_coef: float = 1.0
+    condition_tensors: Optional[dict] = None
+
+
 class LMGen:
     """Streaming generation (reference: lm.py:556-850), including classifier-free guidance (`cfg_coef`,
     `cfg_is_masked_until`, `cfg_is_no_text`), `sum` condition tensors through `lm_model.fuser` and the per-step hooks
@@ -471,6 +491,7 @@ class LMGen:
         self._lib.check(self._lib.mmi_lm_streaming_start_guided(lm._handle, int(batch_size), C.byref(s), C.byref(g), self._stream()))
         del keep
         self._batch = int(batch_size)
+        self._cond_keep = []
         self._install_hooks()
 
     def _install_hooks(self) -> None:
@@ -517,6 +538,7 @@ class LMGen:
         self._lib.mmi_lm_set_hooks(self.lm_model._handle, None)
         self._hooks_keep = None
         self._lib.check(self._lib.mmi_lm_streaming_stop(self.lm_model._handle))
+        self._cond_keep = []
         self._batch = None
 
     @contextmanager
@@ -558,6 +580,37 @@ class LMGen:
         assert self.is_streaming
         keep, ptr = self._host_mask(mask)
         self._lib.check(self._lib.mmi_lm_clear_row_sampling(self.lm_model._handle, ptr, self._stream()))
+
+    # ---- per-session conditions (mmi_lm_set_row_condition) ---------------------------------------
+    def set_session_condition(self, session: int, cond: SessionCondition) -> None:
+        """Session `session` runs with its own condition (sum row, cross-attention source of its own length) and guidance
+        coefficient from the next step on.  Stream-ordered; the launch list and a captured step graph stay as they are, and no other
+        session changes.  `reset_streaming` keeps it.  With a `DuplexStream` call it after `join()`: the LM's own stream must have
+        passed the last submitted frame."""
+        assert self.is_streaming
+        lm = self.lm_model
+        rows = 2 if self.cfg_coef != 1. else 1
+        rc = _capi.RowCondition()
+        rc.cfg_coef = float(cond.cfg_coef)
+        keep = []
+        if cond.condition_tensors is not None:
+            assert lm.fuser is not None, "Model has no fuser"
+            cs = lm.fuser.get_sum(cond.condition_tensors)
+            if cs is not None:
+                assert cs.shape[0] == rows, "cfg requires 2x more conditions." if rows == 2 else "one condition row per session"
+                cs = cs.to(device=self.device, dtype=torch.bfloat16).contiguous().view(rows, lm.dim)
+                keep.append(cs)
+                rc.condition_sum = cs.data_ptr()
+            cx = lm.fuser.get_cross(cond.condition_tensors)
+            if cx is not None:
+                assert cx.shape[0] == rows, "cfg requires 2x more conditions." if rows == 2 else "one condition row per session"
+                cx = cx.to(device=self.device, dtype=torch.bfloat16).contiguous()
+                assert cx.dim() == 3 and cx.shape[2] == lm.dim, cx.shape
+                keep.append(cx)
+                rc.condition_cross = cx.data_ptr()
+                rc.cross_len = int(cx.shape[1])
+        self._lib.check(self._lib.mmi_lm_set_row_condition(lm._handle, int(session), C.byref(rc), self._stream()))
+        self._cond_keep.append(keep)         # alive until the next step has been enqueued behind the call
 
     def get_streaming_state(self) -> dict:
         """streaming.py:158-166: the complete streaming state (a copy: one opaque device tensor + the host step counter)."""
@@ -654,6 +707,7 @@ class LMGen:
             err, self._hook_error = self._hook_error, None
             raise err
         self._lib.check(rc)
+        self._cond_keep = []
         if not self.support_out_of_sync and not valid.value:
             return None, tl, al
         return out, tl, al
