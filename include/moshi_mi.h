@@ -366,6 +366,63 @@ int mmi_lm_cross_capacity(const mmi_lm* lm);
  * cross-attention layers MMI_ERR_INVALID; cross_len outside [1, capacity] MMI_ERR_SHAPE. */
 int mmi_lm_set_row_condition(mmi_lm* lm, int32_t session, const mmi_row_condition* c, mmi_stream stream);
 
+/* The TTS script machine on the device: what TTSModel.generate's three host hooks do on every frame
+ * (models/tts.py:553-583) - StateMachine.process per row (tts.py:160-252), the zeroed / prefixed audio codebooks, the padding
+ * bonus - as part of the launch list, so that a TTS step stays one captured graph.  The fields are StateMachine's and
+ * TTSModel's: text_card = TokenIds.card (the mux base of a demuxed text stream: the model's text_card + 1), new_word, pad, zero
+ * (tts.py:37-57; zero must be -1), second_stream_ahead, max_padding, initial_padding (tts.py:146-149), delay_steps and
+ * padding_bonus (tts.py:563, 555). */
+struct mmi_tts_params {
+    int32_t text_card, new_word, pad, zero;
+    int32_t second_stream_ahead, max_padding, initial_padding, delay_steps;
+    float padding_bonus;
+};
+typedef struct mmi_tts_params mmi_tts_params;
+/* Replaces LMGen(on_text_logits_hook, on_text_hook, on_audio_hook) of tts.py:588-593 for the streams started after the call, in
+ * the manner of mmi_lm_set_cross_capacity: a property of the handle, not while streaming (MMI_ERR_STATE).  Capacities per
+ * session: script entries, script tokens, prefix columns (they size the machine's rows in the streaming state, which
+ * mmi_lm_state_save / _load carry).  The step then runs k_tts_machine behind the text sampler (on a demuxed model in place of the
+ * launch that wrote the depth transformer's first input row, else as one added launch), applies the audio rule in the ring
+ * commit and the padding bonus in the text sampler.  NULL params: off again - the launch list of a handle that never enabled it.
+ * Refused: dep_q == 0, or second_stream_ahead > 0 on a model without a demuxed text stream, MMI_ERR_UNSUPPORTED; negative
+ * values, ids outside the text vocabulary, zero != -1, a mux base that is not text_card + 1 MMI_ERR_INVALID. */
+int mmi_lm_enable_tts_machine(mmi_lm* lm, const mmi_tts_params* params, int32_t max_entries, int32_t max_tokens, int32_t max_prefix);
+/* One session's script: HOST arrays, copied by the call.  Entry e (tts.py:60-74 Entry) owns tokens[entry_first[e] ..
+ * entry_first[e + 1]) - none = a break - and entry_padding[e]; entry_first has n_entries + 1 values, the first 0.
+ * text_prefix [text_prefix_len] and audio_prefix [dep_q][audio_prefix_len] are row 0 and rows audio_offset.. of
+ * generate(prefixes=...) (tts.py:536-551), un-delayed: the engine delays each codebook by its delay + delay_steps as `_delayed`
+ * does; -2 (ungenerated) entries leave the sampled token. */
+struct mmi_tts_script {
+    const int32_t* tokens;
+    const int32_t* entry_first;
+    const int32_t* entry_padding;
+    int32_t n_entries;
+    const int32_t* text_prefix;
+    int32_t text_prefix_len;
+    const int32_t* audio_prefix;
+    int32_t audio_prefix_len;
+};
+typedef struct mmi_tts_script mmi_tts_script;
+/* Session `session` runs `script` from `new_state` (tts.py:151-158, 530) from its next step on; NULL: no script, its sampled text
+ * token passes through.  Stream-ordered like k_lm_set_rows: the row is composed in pinned memory and copied on `stream`, no host
+ * synchronisation; neither the launch list nor a captured graph changes and no other session is touched.  The machine's step
+ * index is the session's own stream offset (mmi_lm_seek / reset), so a session that starts later in a live batch behaves like a
+ * fresh stream; with all rows in step it is the loop index of tts.py:602.  mmi_lm_reset of the row rewinds its machine to
+ * new_state of the same script (as it keeps the row's condition and sampling settings).  Appending entries to a running script is
+ * not built: a call replaces the script.  A refused call changes nothing: machine not enabled or not streaming MMI_ERR_STATE;
+ * session outside [0, batch), a token outside the text vocabulary, a negative padding MMI_ERR_INVALID; more entries, tokens or
+ * prefix columns than the capacities MMI_ERR_SHAPE. */
+int mmi_lm_set_row_script(mmi_lm* lm, int32_t session, const mmi_tts_script* script, mmi_stream stream);
+/* TTSResult's end_steps / all_consumption_times of one session (tts.py:624-628; end_step -1 = None).  consumption_times: HOST
+ * [capacity] or NULL; the first min(n_consumed, capacity) values are written.  Waits for `stream`. */
+struct mmi_tts_status {
+    int32_t has_script, end_step, n_consumed;
+    int32_t* consumption_times;
+    int32_t capacity;
+};
+typedef struct mmi_tts_status mmi_tts_status;
+int mmi_lm_row_script_status(mmi_lm* lm, int32_t session, mmi_tts_status* out, mmi_stream stream);
+
 /* LMGen.step (lm.py:785-791, 668-783).
  *   user_codes  i64 [batch, n_user(>= n_q - dep_q), 1]; extra rows are ignored (lm.py:688-689)
  *   out_tokens  i64 [batch, dep_q + 1, 1]; rows not yet valid hold -2 (lm.py:781-782)

@@ -74,6 +74,26 @@ class RowCondition(C.Structure):
     _fields_ = [("cfg_coef", C.c_float), ("condition_sum", C.c_void_p), ("condition_cross", C.c_void_p), ("cross_len", C.c_int32)]
 
 
+class TTSParams(C.Structure):
+    """struct mmi_tts_params: StateMachine's and TTSModel's settings (mmi_lm_enable_tts_machine)."""
+    _fields_ = [("text_card", C.c_int32), ("new_word", C.c_int32), ("pad", C.c_int32), ("zero", C.c_int32),
+                ("second_stream_ahead", C.c_int32), ("max_padding", C.c_int32), ("initial_padding", C.c_int32),
+                ("delay_steps", C.c_int32), ("padding_bonus", C.c_float)]
+
+
+class TTSScriptC(C.Structure):
+    """struct mmi_tts_script: one session's script and prefixes (mmi_lm_set_row_script); host pointers."""
+    _fields_ = [("tokens", C.POINTER(C.c_int32)), ("entry_first", C.POINTER(C.c_int32)), ("entry_padding", C.POINTER(C.c_int32)),
+                ("n_entries", C.c_int32), ("text_prefix", C.POINTER(C.c_int32)), ("text_prefix_len", C.c_int32),
+                ("audio_prefix", C.POINTER(C.c_int32)), ("audio_prefix_len", C.c_int32)]
+
+
+class TTSStatus(C.Structure):
+    """struct mmi_tts_status (mmi_lm_row_script_status)."""
+    _fields_ = [("has_script", C.c_int32), ("end_step", C.c_int32), ("n_consumed", C.c_int32),
+                ("consumption_times", C.POINTER(C.c_int32)), ("capacity", C.c_int32)]
+
+
 class BatcherCondition(C.Structure):
     """struct mmi_batcher_condition: the same for a batcher channel (mmi_batcher_open_cond); host pointers."""
     _fields_ = [("cfg_coef", C.c_float), ("condition_sum", C.c_void_p), ("condition_cross", C.c_void_p), ("cross_len", C.c_int32)]
@@ -160,6 +180,9 @@ SIGNATURES = {
     "mmi_lm_set_cross_capacity": (C.c_int, [_P, C.c_int32]),
     "mmi_lm_cross_capacity": (C.c_int, [_P]),
     "mmi_lm_set_row_condition": (C.c_int, [_P, C.c_int32, C.POINTER(RowCondition), _P]),
+    "mmi_lm_enable_tts_machine": (C.c_int, [_P, C.POINTER(TTSParams), C.c_int32, C.c_int32, C.c_int32]),
+    "mmi_lm_set_row_script": (C.c_int, [_P, C.c_int32, C.POINTER(TTSScriptC), _P]),
+    "mmi_lm_row_script_status": (C.c_int, [_P, C.c_int32, C.POINTER(TTSStatus), _P]),
     "mmi_lm_step": (C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, C.c_int32, C.POINTER(C.c_int32), _P]),
     "mmi_lm_force_next_tokens": (C.c_int, [_P, _P, _P]),
     "mmi_lm_set_phase_callback": (C.c_int, [_P, _P, _P]),
@@ -191,10 +214,12 @@ SIGNATURES = {
 _SINCE_ROW_SAMPLING = ("mmi_row_sampling_check", "mmi_lm_set_row_sampling", "mmi_lm_clear_row_sampling", "mmi_batcher_open_with",
                        "mmi_lm_set_text_end_padding_id")
 _SINCE_ROW_CONDITION = ("mmi_lm_set_cross_capacity", "mmi_lm_cross_capacity", "mmi_lm_set_row_condition", "mmi_batcher_open_cond")
+_SINCE_TTS_MACHINE = ("mmi_lm_enable_tts_machine", "mmi_lm_set_row_script", "mmi_lm_row_script_status")
 
 
 def _missing(name, path):
-    what = "per-session conditions" if name in _SINCE_ROW_CONDITION else "per-session sampling"
+    what = ("the TTS script machine" if name in _SINCE_TTS_MACHINE else
+            "per-session conditions" if name in _SINCE_ROW_CONDITION else "per-session sampling")
 
     def refuse(*_a):
         raise RuntimeError(f"{path} does not export {name}: it was built before {what} existed")
@@ -208,7 +233,7 @@ class Lib:
         self.path = Path(path)
         self.cdll = C.CDLL(str(self.path))
         for name, (res, args) in SIGNATURES.items():
-            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION and not hasattr(self.cdll, name):
+            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION + _SINCE_TTS_MACHINE and not hasattr(self.cdll, name):
                 # an older build of the engine (MMI_LIB_PATH, A/B runs against a parent build): everything else works, these refuse
                 setattr(self, name, _missing(name, self.path))
                 continue

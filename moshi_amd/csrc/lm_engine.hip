@@ -151,6 +151,16 @@ struct mmi_lm {
     int (*phase_fn)(void*, mmi_stream) = nullptr;   // mmi_lm_set_phase_callback
     void* phase_user = nullptr;
     SampleArgs text_sample_args;    // to rebuild the depth transformer's first input when a hook changed the text token
+    // the TTS script machine (mmi_lm_enable_tts_machine): parameters and capacities belong to the handle, the rows to the stream
+    bool tts_on = false;
+    TtsParams tts_p{};
+    int tts_max_entries = 0, tts_max_tokens = 0, tts_max_prefix = 0;
+    int tts_stride = 0;             // ints per session row (lm_kernels.h: header + arrays)
+    int* tts = nullptr;             // [gen_batch][tts_stride], streaming-state arena
+    int* tts_stage = nullptr;       // pinned [gen_batch][tts_stride]: mmi_lm_set_row_script composes a row here and copies it
+    std::vector<hipEvent_t> tts_stage_ev;     // behind the copy out of a session's staging row; waited for before it is reused
+    std::vector<uint8_t> tts_stage_used;
+    bool tts_rule_done = false;     // this (hooked) step has applied the audio rule in front of on_audio_tokens: the commit does not
     long offset_cpu = 0;
     int attn_ns = 1;                                // workgroups per (session, head) of the decode attention (attn_splits)
     long depth_bound = 0;                           // no session's offset exceeds this (steps since streaming_start / the last seek; resets
@@ -836,6 +846,7 @@ void add_sample(mmi_lm* lm, uint16_t* logits, int ld, int V, bool text, int site
     sa.forced = lm->forced + site; sa.forced_stride = 1 + lm->cfg.dep_q; sa.use_forced = lm->use_forced;
     sa.rows = lm->rowtab; sa.offsets = lm->offsets; sa.thist = text ? lm->thist : nullptr; sa.text = text ? 1 : 0;
     sa.pad_id = lm->cfg.existing_text_padding_id;
+    if (text && lm->tts) { sa.bonus_id = lm->tts_p.pad; sa.bonus = lm->tts_p.padding_bonus; }
     const int B = lm->gen_batch;
     if (text) {                     // hook boundaries: the guided logits are final here, the sampler is the next op
         lm->op_text_sample = lm->prog.ops.size();
@@ -936,6 +947,10 @@ TokArgs tok_args(mmi_lm* lm) {
     t.card = lm->cfg.card; t.text_card = lm->cfg.text_card;
     t.rows = lm->rowtab; t.thist = lm->thist;
     t.text_pad = lm->cfg.existing_text_padding_id; t.text_eop = lm->text_eop;      // LMModel.end_of_text_padding_id (lm.py:261); gen.rs:79
+    t.tts = lm->tts; t.tts_stride = lm->tts_stride; t.tts_max_prefix = lm->tts_max_prefix;
+    t.tts_aprefix = MMI_TTS_HDR + 2 * lm->tts_max_tokens + 3 * lm->tts_max_entries + 1 + lm->tts_max_prefix;
+    t.tts_zero = lm->tts_p.zero; t.tts_delay_steps = lm->tts_p.delay_steps; t.tts_initial_padding = lm->tts_p.initial_padding;
+    t.tts_audio = lm->tts ? 1 : 0;
     return t;
 }
 
@@ -1083,8 +1098,35 @@ int build_program(mmi_lm* lm) {
     P.site("text_sample");
     // a demuxed text stream: the first input row is written by its own launch behind the sampler (and behind an on_text_hook,
     // which may mux a second token into the one sampled)
-    add_sample(lm, lm->text_logits, c.text_card_out, c.text_card_out, true, 0, lm->text_tok, 1, grouped && !lm->demux ? 0 : -1);
-    if (lm->demux && c.dep_q > 0) {
+    // the TTS machine writes that row itself, from ITS token: the sampler's fused write is off, and on a demuxed model the
+    // machine's launch stands where dep.in_demux stood
+    add_sample(lm, lm->text_logits, c.text_card_out, c.text_card_out, true, 0, lm->text_tok, 1, grouped && !lm->demux && !lm->tts ? 0 : -1);
+    if (lm->tts) {
+        P.site("tts.machine");
+        SampleArgs na;
+        memset(&na, 0, sizeof(na));
+        if (grouped) {
+            na.nx_pre = lm->dpre + (size_t)lm->dep_sched[0] * dd; na.nx_ld = lm->dep_nw * dd;
+            na.nx_emb = lm->dep_emb[0]; na.nx_out = lm->dx;
+            na.nx_D = dd; na.nx_T = lm->Td; na.nx_ksteps = packed_ksteps_t(lm, lm->Td, dd);
+        }
+        na.nx_dup = lm->cfg_coef != 1.f ? lm->gen_batch : 0;
+        na.out_stride = 1;
+        TtsArgs m;
+        memset(&m, 0, sizeof(m));
+        m.st = lm->tts; m.stride = lm->tts_stride; m.max_entries = lm->tts_max_entries; m.max_tokens = lm->tts_max_tokens;
+        m.max_prefix = lm->tts_max_prefix; m.p = lm->tts_p; m.offsets = lm->offsets; m.exec = lm->exec; m.text_tok = lm->text_tok;
+        m.emb2 = lm->demux ? lm->dep_emb2 : nullptr; m.demux_n = c.text_card + 1;
+        const int G = lm->gen_batch;
+        P.add([=](hipStream_t s) {
+            MMI_LAUNCH(k_tts_machine, G, 128, 0, s, na, m);
+            MMI_CHECK_LAUNCH();
+            return (int)MMI_OK;
+        });
+        // an on_text_hook next to the machine runs behind it and sees its token; the row is then rebuilt from what the hook left
+        lm->op_after_text_sample = P.ops.size();
+        lm->text_sample_args = na;
+    } else if (lm->demux && c.dep_q > 0) {
         P.site("dep.in_demux");
         SampleArgs na;
         memset(&na, 0, sizeof(na));
@@ -1161,7 +1203,9 @@ int build_program(mmi_lm* lm) {
         TokArgs t = tok_args(lm);
         const int *tt = lm->text_tok, *at = lm->audio_tok; int* out = lm->out_i32; unsigned long long* rng = lm->rng;
         P.add([=](hipStream_t s) {
-            MMI_LAUNCH(k_lm_commit, mmi_cdiv(t.B, 64), 64, 0, s, t, tt, at, out, rng);
+            TokArgs tc = t;
+            if (lm->tts_rule_done) tc.tts_audio = 0;      // a hooked step: k_tts_audio_rule ran in front of on_audio_tokens
+            MMI_LAUNCH(k_lm_commit, mmi_cdiv(tc.B, 64), 64, 0, s, tc, tt, at, out, rng);
             MMI_CHECK_LAUNCH();
             return (int)MMI_OK;
         });
@@ -1242,13 +1286,27 @@ int run_step_with_hooks(mmi_lm* lm, hipStream_t s) {
         // the sampler also wrote the depth transformer's first input row from ITS token (fused, lm.py:465-470): redo that
         // row from the token the hook left behind
         if (lm->text_sample_args.nx_out) {
+            if (lm->tts && lm->demux)
+                MMI_LAUNCH(k_dep_next_input_demux, lm->gen_batch, 128, 0, s, lm->text_sample_args, (const int*)lm->text_tok,
+                           (const uint16_t*)lm->dep_emb2, lm->cfg.text_card + 1);
+            else
             MMI_LAUNCH(k_dep_next_input, lm->gen_batch, 128, 0, s, lm->text_sample_args, (const int*)lm->text_tok);
             MMI_CHECK_LAUNCH();
         }
     }
     if ((rc = P.run_range(s, lm->op_after_text_sample, lm->op_commit))) return rc;
-    if (lm->cfg.dep_q > 0 && (rc = call(lm->hooks.on_audio_tokens))) return rc;      // no depformer, no audio tokens (lm.py:748-749)
-    return P.run_range(s, lm->op_commit, P.ops.size());
+    if (lm->cfg.dep_q > 0 && lm->hooks.on_audio_tokens) {      // no depformer, no audio tokens (lm.py:748-749)
+        if (lm->tts) {          // the machine's audio rule first: the hook sees its tokens, the commit stores what the hook leaves
+            TokArgs t = tok_args(lm);
+            MMI_LAUNCH(k_tts_audio_rule, mmi_cdiv(t.B * t.dep_q, 64), 64, 0, s, t, lm->audio_tok);
+            MMI_CHECK_LAUNCH();
+            lm->tts_rule_done = true;
+        }
+        if ((rc = call(lm->hooks.on_audio_tokens))) { lm->tts_rule_done = false; return rc; }
+    }
+    rc = P.run_range(s, lm->op_commit, P.ops.size());
+    lm->tts_rule_done = false;
+    return rc;
 }
 
 }  // namespace
@@ -1600,6 +1658,12 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
     ok &= hipSuccess == A.alloc(&lm->rng, (size_t)2);
     ok &= hipSuccess == A.alloc(&lm->rowtab, (size_t)G);
     ok &= hipSuccess == A.alloc(&lm->thist, (size_t)G * MMI_TEXT_HIST);
+    lm->tts = nullptr;
+    lm->tts_stride = 0;
+    if (lm->tts_on) {
+        lm->tts_stride = MMI_TTS_HDR + 2 * lm->tts_max_tokens + 3 * lm->tts_max_entries + 1 + (1 + c.dep_q) * lm->tts_max_prefix;
+        ok &= hipSuccess == A.alloc(&lm->tts, (size_t)G * lm->tts_stride);
+    }
     if (!ok) return fail(mmi_fail(MMI_ERR_HIP, "out of device memory (LM streaming state)"));
     MMI_HIP_CHECK(hipMemsetAsync(lm->exec, 1, G, s));
     MMI_HIP_CHECK(hipMemsetAsync(lm->offsets, 0, G * sizeof(long), s));
@@ -1623,6 +1687,16 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
     MMI_HIP_CHECK(hipMemsetAsync(lm->rowtab, 0, (size_t)G * sizeof(RowSamp), s));          // every row inactive
     MMI_HIP_CHECK(hipMemsetAsync(lm->thist, 0, (size_t)G * MMI_TEXT_HIST * sizeof(int), s));
     lm->row_active.assign(G, 0);
+    if (lm->tts) {          // no session has a script: every header word 0
+        MMI_HIP_CHECK(hipMemsetAsync(lm->tts, 0, (size_t)G * lm->tts_stride * sizeof(int), s));
+        if (hipHostMalloc((void**)&lm->tts_stage, (size_t)G * lm->tts_stride * sizeof(int), 0) != hipSuccess) {
+            lm->tts_stage = nullptr;
+            return fail(mmi_fail(MMI_ERR_HIP, "out of pinned host memory (TTS script staging)"));
+        }
+        lm->tts_stage_ev.assign(G, nullptr);
+        lm->tts_stage_used.assign(G, 0);
+        for (int i = 0; i < G; ++i) MMI_HIP_CHECK(hipEventCreateWithFlags(&lm->tts_stage_ev[i], hipEventDisableTiming));
+    }
     {   // packed activations: the padding rows / columns of a fragment are never written and must read as zero
         struct { uint16_t* p; int f; int T; } pk[] = {{lm->x, d, lm->T}, {lm->xn, d, lm->T}, {lm->att, d, lm->T}, {lm->hb, c.ffn_hidden, lm->T},
                                                       {lm->tout, d, lm->T}, {lm->dx, dd, lm->Td}, {lm->dxn, dd, lm->Td}, {lm->datt, dd, lm->Td},
@@ -1685,6 +1759,11 @@ extern "C" int mmi_lm_streaming_stop(mmi_lm* lm) {
     if (lm->trace_dev) { hipFree(lm->trace_dev); lm->trace_dev = nullptr; }
     lm->prog.clear();
     lm->st.release();
+    lm->tts = nullptr;
+    if (lm->tts_stage) { hipHostFree(lm->tts_stage); lm->tts_stage = nullptr; }
+    for (hipEvent_t e : lm->tts_stage_ev) if (e) hipEventDestroy(e);
+    lm->tts_stage_ev.clear();
+    lm->tts_stage_used.clear();
     lm->streaming = false;
     lm->batch = 0;
     lm->gen_batch = 0;
@@ -1795,6 +1874,113 @@ extern "C" int mmi_lm_set_row_condition(mmi_lm* lm, int32_t session, const mmi_r
     set.sum = reinterpret_cast<const uint16_t*>(c->condition_sum); set.D = d;
     MMI_LAUNCH(k_lm_set_row_cond, mmi_cdiv(c->condition_sum ? d : 1, 256), 256, 0, s, lm->xlen, lm->coefs, lm->cond, set);
     MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+
+// ---- the TTS script machine ---------------------------------------------------------------------------------------------------
+extern "C" int mmi_lm_enable_tts_machine(mmi_lm* lm, const mmi_tts_params* p, int32_t max_entries, int32_t max_tokens, int32_t max_prefix) {
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (lm->streaming) return mmi_fail(MMI_ERR_STATE, "the machine adds ops to the step's launch list: enable it before streaming_start");
+    if (!p) { lm->tts_on = false; return MMI_OK; }
+    const mmi_lm_cfg& c = lm->cfg;
+    if (c.dep_q == 0) return mmi_fail(MMI_ERR_UNSUPPORTED, "the TTS machine feeds the depth transformer: the model has dep_q == 0");
+    if (p->second_stream_ahead > 0 && !lm->demux)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "second_stream_ahead > 0 needs a model with a demuxed text stream");
+    if (max_entries < 0 || max_tokens < 0 || max_prefix < 0 || p->second_stream_ahead < 0 || p->max_padding < 0 || p->initial_padding < 0 ||
+        p->delay_steps < 0 || !std::isfinite(p->padding_bonus))
+        return mmi_fail(MMI_ERR_INVALID, "mmi_tts_params: negative capacity / count or a non-finite padding bonus");
+    if (p->new_word < 0 || p->new_word > c.text_card || p->pad < 0 || p->pad > c.text_card || p->new_word == p->pad)
+        return mmi_fail(MMI_ERR_INVALID, "mmi_tts_params: new_word and pad must be two ids of the text vocabulary");
+    if (p->zero != -1) return mmi_fail(MMI_ERR_INVALID, "mmi_tts_params: zero must be -1, the token the embeddings map to a zero row");
+    if (lm->demux && p->text_card != c.text_card + 1)
+        return mmi_fail(MMI_ERR_INVALID, "mmi_tts_params: text_card (the mux base) must be the model's text_card + 1");
+    if ((int64_t)2 * max_tokens + 3 * (int64_t)max_entries + (int64_t)(1 + c.dep_q) * max_prefix > (1 << 26))
+        return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_enable_tts_machine: capacities above 2^26 words per session");
+    lm->tts_p.text_card = p->text_card; lm->tts_p.new_word = p->new_word; lm->tts_p.pad = p->pad; lm->tts_p.zero = p->zero;
+    lm->tts_p.second_stream_ahead = p->second_stream_ahead; lm->tts_p.max_padding = p->max_padding;
+    lm->tts_p.initial_padding = p->initial_padding; lm->tts_p.delay_steps = p->delay_steps; lm->tts_p.padding_bonus = p->padding_bonus;
+    lm->tts_max_entries = max_entries; lm->tts_max_tokens = max_tokens; lm->tts_max_prefix = max_prefix;
+    lm->tts_on = true;
+    return MMI_OK;
+}
+
+extern "C" int mmi_lm_set_row_script(mmi_lm* lm, int32_t session, const mmi_tts_script* sc, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (!lm->streaming || !lm->tts) return mmi_fail(MMI_ERR_STATE, "the TTS machine is not enabled on a live stream (mmi_lm_enable_tts_machine, then streaming_start)");
+    if (session < 0 || session >= lm->gen_batch) return mmi_fail(MMI_ERR_INVALID, "session outside [0, batch)");
+    const mmi_lm_cfg& c = lm->cfg;
+    const int me = lm->tts_max_entries, mt = lm->tts_max_tokens, mp = lm->tts_max_prefix;
+    int ntok = 0;
+    if (sc) {       // every check before the first write: a refused call changes nothing
+        if (sc->n_entries < 0 || sc->text_prefix_len < 0 || sc->audio_prefix_len < 0) return mmi_fail(MMI_ERR_INVALID, "negative count in mmi_tts_script");
+        if (sc->n_entries > me) return mmi_fail(MMI_ERR_SHAPE, "more script entries than the machine's capacity (max_entries)");
+        if (sc->text_prefix_len > mp || sc->audio_prefix_len > mp) return mmi_fail(MMI_ERR_SHAPE, "more prefix columns than the machine's capacity (max_prefix)");
+        if (sc->n_entries > 0 && (!sc->entry_first || !sc->entry_padding)) return mmi_fail(MMI_ERR_INVALID, "null entry arrays");
+        if ((sc->text_prefix_len > 0 && !sc->text_prefix) || (sc->audio_prefix_len > 0 && !sc->audio_prefix)) return mmi_fail(MMI_ERR_INVALID, "null prefix array");
+        if (sc->n_entries > 0) {
+            if (sc->entry_first[0] != 0) return mmi_fail(MMI_ERR_INVALID, "entry_first[0] must be 0");
+            for (int e = 0; e < sc->n_entries; ++e) {
+                if (sc->entry_first[e + 1] < sc->entry_first[e]) return mmi_fail(MMI_ERR_INVALID, "entry_first must not decrease");
+                if (sc->entry_padding[e] < 0) return mmi_fail(MMI_ERR_INVALID, "negative padding in a script entry");
+            }
+            ntok = sc->entry_first[sc->n_entries];
+        }
+        if (ntok > mt) return mmi_fail(MMI_ERR_SHAPE, "more script tokens than the machine's capacity (max_tokens)");
+        if (ntok > 0 && !sc->tokens) return mmi_fail(MMI_ERR_INVALID, "null token array");
+        for (int i = 0; i < ntok; ++i)
+            if (sc->tokens[i] < 0 || sc->tokens[i] > c.text_card) return mmi_fail(MMI_ERR_INVALID, "a script token outside the text vocabulary");
+        const int64_t N = (int64_t)c.text_card + 1, top = lm->demux ? N * (N + 1) : N;        // a prefix token may be a muxed pair, or `zero`
+        for (int i = 0; i < sc->text_prefix_len; ++i)
+            if (sc->text_prefix[i] < -1 || sc->text_prefix[i] >= top) return mmi_fail(MMI_ERR_INVALID, "a text prefix token outside the text vocabulary");
+        for (int i = 0; i < c.dep_q * sc->audio_prefix_len; ++i)
+            if (sc->audio_prefix[i] < -2 || sc->audio_prefix[i] >= c.card) return mmi_fail(MMI_ERR_INVALID, "an audio prefix token outside the codebook");
+    }
+    hipStream_t s = (hipStream_t)stream;
+    // the session's own pinned row; the copy out of it of an earlier call has normally long completed (no wait in that case)
+    if (lm->tts_stage_used[session]) MMI_HIP_CHECK(hipEventSynchronize(lm->tts_stage_ev[session]));
+    int* r = lm->tts_stage + (size_t)session * lm->tts_stride;
+    memset(r, 0, (size_t)lm->tts_stride * sizeof(int));
+    r[MMI_TTS_REMAIN] = r[MMI_TTS_FORCED] = lm->tts_p.initial_padding;        // new_state (tts.py:151-158)
+    r[MMI_TTS_END] = -1;
+    if (sc) {
+        r[MMI_TTS_HAS] = 1; r[MMI_TTS_NENT] = sc->n_entries; r[MMI_TTS_TPLEN] = sc->text_prefix_len; r[MMI_TTS_APLEN] = sc->audio_prefix_len;
+        int* q = r + MMI_TTS_HDR;
+        for (int i = 0; i < ntok; ++i) q[i] = sc->tokens[i];
+        q += mt;
+        for (int e = 0; e <= sc->n_entries && sc->n_entries > 0; ++e) q[e] = sc->entry_first[e];
+        q += me + 1;
+        for (int e = 0; e < sc->n_entries; ++e) q[e] = sc->entry_padding[e];
+        q += 2 * me + mt;       // past consumption_times and the lookahead buffer
+        for (int i = 0; i < sc->text_prefix_len; ++i) q[i] = sc->text_prefix[i];
+        q += mp;
+        for (int k = 0; k < c.dep_q; ++k)
+            for (int i = 0; i < sc->audio_prefix_len; ++i) q[k * mp + i] = sc->audio_prefix[(size_t)k * sc->audio_prefix_len + i];
+    }
+    MMI_HIP_CHECK(hipMemcpyAsync(lm->tts + (size_t)session * lm->tts_stride, r, (size_t)lm->tts_stride * sizeof(int), hipMemcpyHostToDevice, s));
+    MMI_HIP_CHECK(hipEventRecord(lm->tts_stage_ev[session], s));
+    lm->tts_stage_used[session] = 1;
+    return MMI_OK;
+}
+
+extern "C" int mmi_lm_row_script_status(mmi_lm* lm, int32_t session, mmi_tts_status* out, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm || !out) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (!lm->streaming || !lm->tts) return mmi_fail(MMI_ERR_STATE, "the TTS machine is not enabled on a live stream");
+    if (session < 0 || session >= lm->gen_batch) return mmi_fail(MMI_ERR_INVALID, "session outside [0, batch)");
+    hipStream_t s = (hipStream_t)stream;
+    const int me = lm->tts_max_entries, mt = lm->tts_max_tokens;
+    const int* r = lm->tts + (size_t)session * lm->tts_stride;
+    int hdr[MMI_TTS_HDR];
+    std::vector<int> times((size_t)me);
+    MMI_HIP_CHECK(hipMemcpyAsync(hdr, r, sizeof(hdr), hipMemcpyDeviceToHost, s));
+    if (me > 0) MMI_HIP_CHECK(hipMemcpyAsync(times.data(), r + MMI_TTS_HDR + mt + 2 * me + 1, (size_t)me * sizeof(int), hipMemcpyDeviceToHost, s));
+    MMI_HIP_CHECK(hipStreamSynchronize(s));      // a status read returns host values: it waits for the steps enqueued so far
+    out->has_script = hdr[MMI_TTS_HAS];
+    out->end_step = hdr[MMI_TTS_HAS] ? hdr[MMI_TTS_END] : -1;       // a row without a script never ends (its words are all 0 after the start)
+    out->n_consumed = hdr[MMI_TTS_HAS] ? hdr[MMI_TTS_NCONS] : 0;
+    if (out->consumption_times)
+        for (int i = 0; i < hdr[MMI_TTS_NCONS] && i < out->capacity; ++i) out->consumption_times[i] = times[(size_t)i];
     return MMI_OK;
 }
 

@@ -2296,6 +2296,9 @@ struct SampleArgs {
     const int* thist;         // [B][MMI_TEXT_HIST] ring of committed text tokens; non-null at the text site only
     int text;                 // 1 = the text site (temp_text / top_k_text of the row's entry)
     int pad_id;               // existing_text_padding_id: the entry RowSamp::pad_mult lifts
+    // TTS machine (mmi_lm_enable_tts_machine): tts.py:553-555 `text_logits[..., pad] += padding_bonus` at the text site, every row
+    int bonus_id;             // TokenIds.pad
+    float bonus;              // 0 = off: the sampler's bits are those of a handle without the machine
 };
 
 __device__ __forceinline__ void mmi_sample_next_input(const SampleArgs& a, int b0, int tok) {
@@ -2326,9 +2329,7 @@ __global__ void k_dep_next_input(SampleArgs a, const int* __restrict__ tok) {
 // The depth transformer's first input row of a demuxed text stream (demux_second_text_stream): x0[b] = nx_pre[b] +
 // bf16(nx_emb[first] + emb2[second]) with the pair of k_lm_embed_demux, launched after the text sampler (and after an on_text_hook
 // that may have replaced the token with a muxed one).  One workgroup per session.
-__global__ void k_dep_next_input_demux(SampleArgs a, const int* __restrict__ tok, const uint16_t* __restrict__ emb2, int N) {
-    const int b0 = (int)blockIdx.x;
-    const int t0 = tok[(long)b0 * a.out_stride];
+__device__ __forceinline__ void mmi_sample_next_input_demux(const SampleArgs& a, int b0, int t0, const uint16_t* __restrict__ emb2, int N) {
     const int t = t0 < 0 ? 0 : t0;
     int second = t / N - 1;
     if (second > N - 1) second = N - 1;
@@ -2357,6 +2358,9 @@ __global__ void k_dep_next_input_demux(SampleArgs a, const int* __restrict__ tok
         }
         *reinterpret_cast<u32x4*>(a.nx_out + mmi_xp_index(a.nx_T, b, n0, a.nx_ksteps)) = ov;
     }
+}
+__global__ void k_dep_next_input_demux(SampleArgs a, const int* __restrict__ tok, const uint16_t* __restrict__ emb2, int N) {
+    mmi_sample_next_input_demux(a, (int)blockIdx.x, tok[(long)blockIdx.x * a.out_stride], emb2, N);
 }
 
 __device__ __forceinline__ int mmi_apply_forced(const SampleArgs& a, int b, int tok) {
@@ -2453,6 +2457,18 @@ __device__ __forceinline__ void mmi_sample_patch(u32x4 (&cache)[NV], int off, in
             }
 }
 
+// entry `off` of the thread's cached logits, read with the same compile-time-indexed compares
+template <int NV>
+__device__ __forceinline__ uint16_t mmi_sample_peek(const u32x4 (&cache)[NV], int off) {
+    unsigned word = 0u;
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+            if ((off >> 1) == v * 4 + w) word = cache[v][w];
+    return (uint16_t)((off & 1) ? (word >> 16) : (word & 0xffffu));
+}
+
 #ifndef MMI_SAMPLE_STAMP
 #define MMI_SAMPLE_STAMP(i)          // scripts/sample_microbench.hip defines it: device-clock stamps at the kernel's stages
 #endif
@@ -2541,6 +2557,13 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
     const bool s_greedy = !s_use_sampling || !(s_temp > 0.f);
 
     if constexpr (CACHE) {
+        // the TTS machine's padding bonus (tts.py:553-555), where on_text_logits_hook runs: behind the guidance mix, ahead of the
+        // repetition penalty.  bf16(float(l_pad) + bonus), the bits of the reference's in-place `+=` on its bf16 logits; like
+        // that `+=` it is visible afterwards: the owning thread stores the entry back (the text-logits tap shows it).
+        if (a.bonus != 0.f && a.bonus_id >= 0 && a.bonus_id < V && (unsigned)(a.bonus_id - i0) < (unsigned)E) {
+            mmi_sample_patch<NV>(cache, a.bonus_id - i0, 1, a.bonus);
+            const_cast<uint16_t*>(lg)[a.bonus_id] = mmi_sample_peek<NV>(cache, a.bonus_id - i0);
+        }
         if (act && a.thist) {             // text site of an active row (block-uniform)
             const int have = c_row.hist_n < (unsigned)MMI_TEXT_HIST ? (int)c_row.hist_n : MMI_TEXT_HIST;
             int ctx = c_row.rep_context < have ? c_row.rep_context : have;
@@ -2918,6 +2941,138 @@ __global__ __launch_bounds__(NT) void k_sample(SampleArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// The TTS script machine on the device (mmi_lm_enable_tts_machine): models/tts.py:160-252 `StateMachine.process` and the three
+// hooks of `TTSModel.generate` (tts.py:553-583), per session, read and written at run time like RowSamp and the row conditions.
+// ------------------------------------------------------------------------------------------------
+struct TtsParams {            // mmi_tts_params
+    int text_card, new_word, pad, zero, second_stream_ahead, max_padding, initial_padding, delay_steps;
+    float padding_bonus;
+};
+// One row of `stride` ints per session in the streaming-state arena: MMI_TTS_HDR header words, then
+//   tokens[max_tokens] | entry_first[max_entries + 1] | entry_padding[max_entries] | consumption_times[max_entries] |
+//   lookahead[max_tokens] | text_prefix[max_prefix] | audio_prefix[dep_q][max_prefix]
+// `queued` is a slice (QPOS, QEND) of tokens[]: it is always a suffix of ONE entry's tokens, because a word is only taken when it
+// is empty.  `lookahead_queued` can hold several words, so it is a real FIFO: a linear buffer with head / tail.  Every entry's
+// tokens are appended to it at most once (word j appends the second_stream_ahead-th non-empty entry behind it, and that map is
+// strictly increasing in j), so max_tokens slots cannot overflow and the indices never wrap.
+enum {
+    MMI_TTS_HAS = 0,          // 1 = the session has a script (else its sampled token passes through)
+    MMI_TTS_NENT, MMI_TTS_TPLEN, MMI_TTS_APLEN,       // entries, text prefix columns, audio prefix columns
+    MMI_TTS_NEXT,             // the next entry (State.entries as an index)
+    MMI_TTS_REMAIN, MMI_TTS_FORCED,                   // remaining_padding, forced_padding
+    MMI_TTS_QPOS, MMI_TTS_QEND, MMI_TTS_LAH, MMI_TTS_LAT,
+    MMI_TTS_END,              // end_step, -1 = none
+    MMI_TTS_NCONS,            // len(consumption_times)
+    MMI_TTS_HDR = 16
+};
+struct TtsArgs {
+    int* st;                  // [G][stride]
+    int stride, max_entries, max_tokens, max_prefix;
+    TtsParams p;
+    const long* offsets;      // the session's own step counter (tts.py:602 `offset` when every row is in step)
+    const uint8_t* exec;
+    int* text_tok;            // [G] in: the sampled (or forced) token, out: the machine's
+    const uint16_t* emb2;     // demuxed text stream: the second table of the depformer's text embedding, else null
+    int demux_n;              // text_card + 1 of the demuxed stream
+};
+__device__ __forceinline__ int mmi_tts_off_first(int me, int mt) { return MMI_TTS_HDR + mt; }
+__device__ __forceinline__ int mmi_tts_off_padding(int me, int mt) { return MMI_TTS_HDR + mt + me + 1; }
+__device__ __forceinline__ int mmi_tts_off_times(int me, int mt) { return MMI_TTS_HDR + mt + 2 * me + 1; }
+__device__ __forceinline__ int mmi_tts_off_look(int me, int mt) { return MMI_TTS_HDR + mt + 3 * me + 1; }
+__device__ __forceinline__ int mmi_tts_off_tprefix(int me, int mt) { return MMI_TTS_HDR + 2 * mt + 3 * me + 1; }
+__device__ __forceinline__ int mmi_tts_off_aprefix(int me, int mt, int mp) { return MMI_TTS_HDR + 2 * mt + 3 * me + 1 + mp; }
+
+// new_state (tts.py:151-158) of the script the row holds
+__device__ __forceinline__ void mmi_tts_rewind(int* r, int initial_padding) {
+    r[MMI_TTS_NEXT] = 0; r[MMI_TTS_REMAIN] = initial_padding; r[MMI_TTS_FORCED] = initial_padding;
+    r[MMI_TTS_QPOS] = 0; r[MMI_TTS_QEND] = 0; r[MMI_TTS_LAH] = 0; r[MMI_TTS_LAT] = 0;
+    r[MMI_TTS_END] = -1; r[MMI_TTS_NCONS] = 0;
+}
+
+// StateMachine.process (tts.py:160-252) at step `step` on the sampled `token`; the text prefix first (tts.py:577-578).  One lane.
+__device__ inline int mmi_tts_process(const TtsArgs& m, int* r, int step, int token) {
+    const TtsParams& p = m.p;
+    const int me = m.max_entries, mt = m.max_tokens;
+    if (step < r[MMI_TTS_TPLEN]) return r[mmi_tts_off_tprefix(me, mt) + step];
+    const int* toks = r + MMI_TTS_HDR;
+    const int* first = r + mmi_tts_off_first(me, mt);
+    const int* padding = r + mmi_tts_off_padding(me, mt);
+    int* times = r + mmi_tts_off_times(me, mt);
+    int* look = r + mmi_tts_off_look(me, mt);
+    const int nent = r[MMI_TTS_NENT];
+    int next = r[MMI_TTS_NEXT], remain = r[MMI_TTS_REMAIN], forced = r[MMI_TTS_FORCED];
+    int qpos = r[MMI_TTS_QPOS], qend = r[MMI_TTS_QEND], lah = r[MMI_TTS_LAH], lat = r[MMI_TTS_LAT], end = r[MMI_TTS_END];
+    if (token != p.new_word && token != p.pad) token = p.pad;                 // :174-175
+    if (qpos < qend) token = p.pad;                                           // :177-185
+    else if (forced > 0) token = p.pad;
+    else if (remain <= 0) token = p.new_word;
+    if (token == p.new_word) {                                                // :187-211
+        if (next < nent) {
+            const int e = next++;
+            times[r[MMI_TTS_NCONS]] = step;
+            r[MMI_TTS_NCONS] += 1;
+            if (first[e + 1] > first[e]) {
+                qpos = first[e]; qend = first[e + 1];
+                if (p.second_stream_ahead) {                                  // get_tokens_ahead over what is left (:105-112)
+                    int ahead = p.second_stream_ahead;
+                    for (int j = next; j < nent; ++j)
+                        if (first[j + 1] > first[j] && --ahead == 0) {
+                            for (int t = first[j]; t < first[j + 1] && lat < mt; ++t) look[lat++] = toks[t];
+                            break;
+                        }
+                }
+                remain = p.max_padding;
+            } else token = p.pad;                                             // a break: pretend the token was a pad
+            forced = padding[e];
+        } else {
+            token = p.pad;
+            if (p.second_stream_ahead && end < 0) token = p.new_word;
+            if (end < 0) end = step;
+        }
+    }
+    int out;
+    if (token == p.pad) {                                                     // :214-224
+        if (remain > 0) --remain;
+        if (forced > 0) --forced;
+        out = qpos < qend ? toks[qpos++] : p.pad;
+    } else out = p.new_word;        // :225-230; the `zero` branch cannot be reached: :174-175 left only new_word and pad
+    if (p.second_stream_ahead) {                                              // :232-249
+        int second = -1;
+        if (out == p.new_word) {
+            second = p.new_word;
+            out = qpos < qend ? toks[qpos++] : p.pad;
+        } else if (lah < lat) second = look[lah++];
+        out = (second + 1) * p.text_card + out;
+    }
+    r[MMI_TTS_NEXT] = next; r[MMI_TTS_REMAIN] = remain; r[MMI_TTS_FORCED] = forced;
+    r[MMI_TTS_QPOS] = qpos; r[MMI_TTS_QEND] = qend; r[MMI_TTS_LAH] = lah; r[MMI_TTS_LAT] = lat; r[MMI_TTS_END] = end;
+    return out;
+}
+
+// Behind the text sampler, one workgroup per session like k_dep_next_input: lane 0 runs the machine on text_tok[b] (a row whose
+// exec mask is 0, or without a script, keeps its token and its state), then the whole workgroup writes the depth transformer's
+// first input row from the machine's token - for the twin row under guidance too - which is what k_dep_next_input /
+// k_dep_next_input_demux do: the machine rides in that launch instead of standing in front of it.  a.nx_out null: only the token
+// (a model whose depformer_in runs per micro-step gathers the row in its GEMM).
+__global__ __launch_bounds__(128) void k_tts_machine(SampleArgs a, TtsArgs m) {
+    const int b = (int)blockIdx.x;
+    MMI_SHARED int s_tok;
+    if (threadIdx.x == 0) {
+        int* r = m.st + (long)b * m.stride;
+        int tok = m.text_tok[b];
+        if (r[MMI_TTS_HAS] && m.exec[b]) {
+            tok = mmi_tts_process(m, r, (int)m.offsets[b], tok);
+            m.text_tok[b] = tok;
+        }
+        s_tok = tok;
+    }
+    __syncthreads();
+    if (!a.nx_out) return;
+    if (m.emb2) mmi_sample_next_input_demux(a, b, s_tok, m.emb2, m.demux_n);
+    else mmi_sample_next_input(a, b, s_tok);
+}
+
+// ------------------------------------------------------------------------------------------------
 // LMGen delay ring (lm.py:668-783)
 // ------------------------------------------------------------------------------------------------
 struct TokArgs {
@@ -2929,7 +3084,34 @@ struct TokArgs {
     RowSamp* rows;         // [B] per-session sampling table (mmi_lm_set_row_sampling)
     int* thist;            // [B][MMI_TEXT_HIST] ring of committed text tokens of the active rows
     int text_pad, text_eop;   // with text_card (the start token): the ids the ring skips (lm_generate_multistream.rs:151-157)
+    // TTS machine (null = off): k_lm_reset rewinds a row, k_lm_commit applies the audio rule (tts_audio != 0)
+    int* tts;                 // [B][tts_stride]
+    int tts_stride, tts_aprefix, tts_max_prefix;      // tts_aprefix: where a row's audio prefix [dep_q][tts_max_prefix] starts
+    int tts_zero, tts_delay_steps, tts_initial_padding, tts_audio;
 };
+
+// _on_audio_hook (tts.py:557-570) for codebook q of session b at step `off`: `zero` while the codebook's delay (+ delay_steps) has
+// not passed, then the audio prefix column where it is not `ungenerated` - delayed per codebook as `_delayed` builds it
+// (tts.py:115-121, 548-551: column off of codebook q holds prefix[q][off - delay]).
+__device__ __forceinline__ int mmi_tts_audio_token(const TokArgs& t, int b, int q, long off, int tok) {
+    const long dl = (long)t.delays[1 + q] + t.tts_delay_steps;
+    if (off < dl) return t.tts_zero;
+    const int* r = t.tts + (long)b * t.tts_stride;
+    if (r[MMI_TTS_HAS] && off - dl < (long)r[MMI_TTS_APLEN]) {
+        const int v = r[t.tts_aprefix + q * t.tts_max_prefix + (int)(off - dl)];
+        if (v != -2) return v;
+    }
+    return tok;
+}
+
+// the audio rule in place on audio_tok, for a step that calls an on_audio_hook next to the machine (the hook sees the machine's
+// tokens; the commit behind it then stores what the hook left)
+__global__ void k_tts_audio_rule(TokArgs t, int* __restrict__ audio_tok) {
+    const int idx = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (idx >= t.B * t.dep_q) return;
+    const int b = idx / t.dep_q, q = idx % t.dep_q;
+    if (t.exec[b]) audio_tok[idx] = mmi_tts_audio_token(t, b, q, t.offsets[b], audio_tok[idx]);
+}
 
 // 1. write the user's codes at (offset+delay)%CT, 2. gather the model input at offset%CT with init-token substitution
 // 3. (threads past B*NC) the RoPE table of the step: (cos, sin)(offset[b] * max_period^(-2j/Dh)) for the new position of
@@ -2974,6 +3156,12 @@ __global__ void k_lm_commit(TokArgs t, const int* __restrict__ text_tok, const i
     if (ex) {
         const int tt = text_tok[b];
         rows[pos] = tt;
+        // TTS machine: the audio rule on the way into the ring (the depformer's own chain has used the sampled tokens, as in the
+        // reference, where the hook runs after the depformer) - a variant of this kernel, not a launch of its own: a dependent
+        // launch costs ~4.7 us whatever it computes, and the ring write is the only reader of the ruled tokens
+        if (t.tts && t.tts_audio)
+            for (int k = 0; k < t.dep_q; ++k) rows[(1 + k) * t.CT + pos] = mmi_tts_audio_token(t, b, k, off_new - 1, audio_tok[(long)b * t.dep_q + k]);
+        else
         for (int k = 0; k < t.dep_q; ++k) rows[(1 + k) * t.CT + pos] = audio_tok[(long)b * t.dep_q + k];
         // the text history of an active row: the token the step stores (after forcing and after an on_text_hook)
         if (t.rows[b].active && tt != t.text_pad && tt != t.text_eop && tt != t.text_card) {
@@ -3016,6 +3204,7 @@ __global__ void k_lm_reset(TokArgs t, const uint8_t* __restrict__ mask, uint8_t*
     t.offsets[idx] = 0;           // lm.py:537-542; transformer.py:329-334 (KV end_offset, MHA offset)
     exec[idx] = 1;                // streaming.py:43-44
     t.rows[idx].hist_n = 0u;      // the row keeps its sampling settings; its text history starts over
+    if (t.tts) mmi_tts_rewind(t.tts + (long)idx * t.tts_stride, t.tts_initial_padding);     // and its script, from new_state
 }
 
 // mmi_lm_set_row_sampling / mmi_lm_clear_row_sampling: up to 16 entries ride in the kernel arguments, so the call is

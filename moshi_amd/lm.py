@@ -8,8 +8,8 @@ from __future__ import annotations
 
 import ctypes as C
 from contextlib import contextmanager
-from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
@@ -390,6 +390,53 @@ class SessionCondition:
     condition_tensors: Optional[dict] = None
 
 
+@dataclass
+class TTSMachine:
+    """The settings of the reference's `StateMachine` and of `TTSModel.generate`'s hooks (models/tts.py:37-57, 146-149, 553-570),
+    run on the device per session (mmi_lm_enable_tts_machine).  `text_card` is `TokenIds.card`, the mux base of a demuxed text
+    stream (the model's text_card + 1).  The capacities size every session's script: entries, tokens over all entries, prefix
+    columns."""
+    text_card: int
+    new_word: int = 0
+    pad: int = 3
+    zero: int = -1
+    second_stream_ahead: int = 0
+    max_padding: int = 6
+    initial_padding: int = 2
+    delay_steps: int = 0
+    padding_bonus: float = 0.0
+    max_entries: int = 256
+    max_tokens: int = 2048
+    max_prefix: int = 0
+
+    def to_c(self) -> "_capi.TTSParams":
+        p = _capi.TTSParams()
+        p.text_card, p.new_word, p.pad, p.zero = int(self.text_card), int(self.new_word), int(self.pad), int(self.zero)
+        p.second_stream_ahead, p.max_padding = int(self.second_stream_ahead), int(self.max_padding)
+        p.initial_padding, p.delay_steps = int(self.initial_padding), int(self.delay_steps)
+        p.padding_bonus = float(self.padding_bonus)
+        return p
+
+
+@dataclass
+class TTSScript:
+    """One session's script: `entries` = [(tokens, padding), ...] (the reference's `Entry.tokens` / `Entry.padding`; no tokens =
+    a break), and optionally the rows of `generate(prefixes=...)`: `text_prefix` [T] and `audio_prefix` [dep_q, T], un-delayed
+    (-2 = leave the sampled token)."""
+    entries: Sequence = field(default_factory=list)
+    text_prefix: Optional[Sequence[int]] = None
+    audio_prefix: Optional[Sequence[Sequence[int]]] = None
+
+
+@dataclass
+class TTSScriptStatus:
+    """`TTSResult.end_steps[b]` (None while the script has not run out) and `all_consumption_times[b]` of one session."""
+    has_script: bool
+    end_step: Optional[int]
+    n_consumed: int
+    consumption_times: list
+
+
 class LMGen:
     """Streaming generation (reference: lm.py:556-850), including classifier-free guidance (`cfg_coef`,
     `cfg_is_masked_until`, `cfg_is_no_text`), `sum` condition tensors through `lm_model.fuser` and the per-step hooks
@@ -400,7 +447,7 @@ class LMGen:
                  top_k: int = 250, top_k_text: int = 25, cfg_coef: float = 1.0, check: bool = False,
                  condition_tensors=None, on_text_hook=None, on_text_logits_hook=None, on_audio_hook=None,
                  support_out_of_sync: bool = False, cfg_is_masked_until=None, cfg_is_no_text: bool = False,
-                 seed: int = 0):
+                 seed: int = 0, tts_machine: Optional[TTSMachine] = None):
         assert not lm_model.training, "generation shouldn't be used in training mode."
         if cfg_coef != 1.:                                # lm.py:600-603
             if not cfg_is_no_text and not cfg_is_masked_until:
@@ -426,6 +473,8 @@ class LMGen:
         self.support_out_of_sync = support_out_of_sync
         self.max_delay = max(lm_model.delays)
         self.seed = seed
+        # the reference's TTS state machine and generate()'s three hooks on the device; host hooks set next to it run after it
+        self.tts_machine = tts_machine
         self._lib = lm_model._lib
         self._batch: Optional[int] = None
 
@@ -486,6 +535,12 @@ class LMGen:
             mu = (C.c_int64 * int(batch_size))(*[int(v) for v in self.cfg_is_masked_until])
             keep.append(mu)
             g.cfg_is_masked_until = C.cast(mu, C.c_void_p)
+        if self.tts_machine is not None:
+            m = self.tts_machine
+            self._lib.check(self._lib.mmi_lm_enable_tts_machine(lm._handle, C.byref(m.to_c()), int(m.max_entries), int(m.max_tokens),
+                                                                int(m.max_prefix)))
+        elif hasattr(self._lib.cdll, "mmi_lm_enable_tts_machine"):       # (an older build of the engine has no machine to switch off)
+            self._lib.check(self._lib.mmi_lm_enable_tts_machine(lm._handle, None, 0, 0, 0))
         if self.device.type == "cuda":
             torch.cuda.current_stream(self.device).synchronize()
         self._lib.check(self._lib.mmi_lm_streaming_start_guided(lm._handle, int(batch_size), C.byref(s), C.byref(g), self._stream()))
@@ -611,6 +666,48 @@ class LMGen:
                 rc.cross_len = int(cx.shape[1])
         self._lib.check(self._lib.mmi_lm_set_row_condition(lm._handle, int(session), C.byref(rc), self._stream()))
         self._cond_keep.append(keep)         # alive until the next step has been enqueued behind the call
+
+    # ---- per-session TTS scripts (mmi_lm_set_row_script) ---------------------------------------------
+    def set_session_script(self, session: int, script: Optional[TTSScript]) -> None:
+        """Session `session` runs `script` from its start from the next step on (None: no script, its sampled text token passes
+        through).  Needs `LMGen(tts_machine=...)`.  Stream-ordered; the launch list and a captured step graph stay as they are,
+        and no other session changes.  `reset_streaming` rewinds the session to the start of the same script."""
+        assert self.is_streaming
+        h = self.lm_model._handle
+        if script is None:
+            self._lib.check(self._lib.mmi_lm_set_row_script(h, int(session), None, self._stream()))
+            return
+        toks, first, pads = [], [0], []
+        for tokens, padding in script.entries:
+            toks.extend(int(t) for t in tokens)
+            first.append(len(toks))
+            pads.append(int(padding))
+        arr = lambda v: (C.c_int32 * max(len(v), 1))(*v)
+        sc = _capi.TTSScriptC()
+        keep = [arr(toks), arr(first), arr(pads)]
+        sc.tokens, sc.entry_first, sc.entry_padding = (C.cast(k, C.POINTER(C.c_int32)) for k in keep)
+        sc.n_entries = len(pads)
+        if script.text_prefix is not None:
+            tp = [int(v) for v in (script.text_prefix.tolist() if isinstance(script.text_prefix, torch.Tensor) else script.text_prefix)]
+            keep.append(arr(tp))
+            sc.text_prefix, sc.text_prefix_len = C.cast(keep[-1], C.POINTER(C.c_int32)), len(tp)
+        if script.audio_prefix is not None:
+            ap = torch.as_tensor(script.audio_prefix, dtype=torch.int64).cpu()
+            assert ap.dim() == 2 and ap.shape[0] == self.lm_model.dep_q, "audio_prefix must be [dep_q, T]"
+            keep.append(arr([int(v) for v in ap.reshape(-1).tolist()]))
+            sc.audio_prefix, sc.audio_prefix_len = C.cast(keep[-1], C.POINTER(C.c_int32)), int(ap.shape[1])
+        self._lib.check(self._lib.mmi_lm_set_row_script(h, int(session), C.byref(sc), self._stream()))     # the call copies the arrays
+
+    def session_script_status(self, session: int) -> TTSScriptStatus:
+        """Where session `session`'s script stands (waits for the steps enqueued so far)."""
+        assert self.is_streaming
+        cap = int(self.tts_machine.max_entries) if self.tts_machine is not None else 0
+        times = (C.c_int32 * max(cap, 1))()
+        st = _capi.TTSStatus()
+        st.consumption_times, st.capacity = C.cast(times, C.POINTER(C.c_int32)), cap
+        self._lib.check(self._lib.mmi_lm_row_script_status(self.lm_model._handle, int(session), C.byref(st), self._stream()))
+        return TTSScriptStatus(bool(st.has_script), None if st.end_step < 0 else int(st.end_step), int(st.n_consumed),
+                               [int(times[i]) for i in range(min(st.n_consumed, cap))])
 
     def get_streaming_state(self) -> dict:
         """streaming.py:158-166: the complete streaming state (a copy: one opaque device tensor + the host step counter)."""
