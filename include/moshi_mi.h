@@ -232,6 +232,13 @@ typedef struct mmi_lm_cfg_ext mmi_lm_cfg_ext;
  * are used.  dep_q up to 32, n_q == dep_q allowed (no user audio stream: mmi_lm_step takes n_user = 0). */
 int mmi_lm_create_ext(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ext, const mmi_tensor_desc* weights, int32_t n_weights,
                       int32_t max_batch, mmi_lm** out);
+/* A handle of up to 128 MODEL rows (sessions, or two rows per guided session).  mmi_lm_create / mmi_lm_create_ext refuse
+ * max_batch > 64; this call takes max_rows 65..128 (ext may be NULL): the step's linears then run on k_gemm_rows, three or four
+ * batch tiles of 32 in one pass over the weights, norms as separate launches.  max_rows <= 64 is mmi_lm_create_ext: the same
+ * launch lists and the same bits.  Refused above 64 rows with MMI_ERR_UNSUPPORTED: int8 / fp8 linears; max_rows > 128.  Everything
+ * downstream (streaming_start, the per-row calls, snapshots, mmi_lm_debug_linear, mmi_batcher_create) follows the handle's value. */
+int mmi_lm_create_rows(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ext_or_null, const mmi_tensor_desc* weights, int32_t n_weights,
+                       int32_t max_rows, mmi_lm** out);
 void mmi_lm_destroy(mmi_lm* lm);
 
 /* LMGen.streaming(batch) enter/exit (lm.py:605-666). */
@@ -270,7 +277,8 @@ int mmi_mimi_device(const mmi_mimi* m);
  * kernel (k_gemm_xlds); 1: bit v set = step program v (short-ring / deep-ring decode attention) is captured and instantiated -
  * both are from the stream's first step on, so that the switch is never a capture inside a live session; 2: the host's bound on
  * the ring depth (steps since streaming_start / seek / the offsets of a restored snapshot); 3: the depth transformer's MFMA tile
- * (16 at <= 32 sessions with bf16 weights, else 32). */
+ * (16 at <= 32 sessions with bf16 weights, else 32); 4: GEMM launches (or captured graph nodes) that took k_gemm_rows (more
+ * than 64 model rows). */
 int64_t mmi_lm_stat(const mmi_lm* lm, int32_t which);
 /* LMGen.step_with_extra_heads (lm.py:793-807): softmax(extra_head(transformer_out)) of the LAST step for every head:
  * probs f32 [model rows, extra_heads_num_heads, extra_heads_dim]. */

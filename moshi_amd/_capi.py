@@ -156,6 +156,7 @@ SIGNATURES = {
     "mmi_duplex_get_stamps": (C.c_int, [_P, _P, _P]),
     "mmi_lm_create": (C.c_int, [C.POINTER(LMCfg), C.POINTER(TensorDesc), C.c_int32, C.c_int32, C.POINTER(_P)]),
     "mmi_lm_create_ext": (C.c_int, [C.POINTER(LMCfg), C.POINTER(LMCfgExt), C.POINTER(TensorDesc), C.c_int32, C.c_int32, C.POINTER(_P)]),
+    "mmi_lm_create_rows": (C.c_int, [C.POINTER(LMCfg), C.POINTER(LMCfgExt), C.POINTER(TensorDesc), C.c_int32, C.c_int32, C.POINTER(_P)]),
     "mmi_lm_destroy": (None, [_P]),
     "mmi_lm_streaming_start": (C.c_int, [_P, C.c_int32, C.POINTER(Sampling), _P]),
     "mmi_lm_streaming_start_guided": (C.c_int, [_P, C.c_int32, C.POINTER(Sampling), C.POINTER(Guidance), _P]),
@@ -215,10 +216,12 @@ _SINCE_ROW_SAMPLING = ("mmi_row_sampling_check", "mmi_lm_set_row_sampling", "mmi
                        "mmi_lm_set_text_end_padding_id")
 _SINCE_ROW_CONDITION = ("mmi_lm_set_cross_capacity", "mmi_lm_cross_capacity", "mmi_lm_set_row_condition", "mmi_batcher_open_cond")
 _SINCE_TTS_MACHINE = ("mmi_lm_enable_tts_machine", "mmi_lm_set_row_script", "mmi_lm_row_script_status")
+_SINCE_MANY_ROWS = ("mmi_lm_create_rows",)
 
 
 def _missing(name, path):
-    what = ("the TTS script machine" if name in _SINCE_TTS_MACHINE else
+    what = ("handles above 64 model rows" if name in _SINCE_MANY_ROWS else
+            "the TTS script machine" if name in _SINCE_TTS_MACHINE else
             "per-session conditions" if name in _SINCE_ROW_CONDITION else "per-session sampling")
 
     def refuse(*_a):
@@ -233,7 +236,7 @@ class Lib:
         self.path = Path(path)
         self.cdll = C.CDLL(str(self.path))
         for name, (res, args) in SIGNATURES.items():
-            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION + _SINCE_TTS_MACHINE and not hasattr(self.cdll, name):
+            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION + _SINCE_TTS_MACHINE + _SINCE_MANY_ROWS and not hasattr(self.cdll, name):
                 # an older build of the engine (MMI_LIB_PATH, A/B runs against a parent build): everything else works, these refuse
                 setattr(self, name, _missing(name, self.path))
                 continue

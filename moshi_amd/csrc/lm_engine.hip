@@ -166,6 +166,7 @@ struct mmi_lm {
     long depth_bound = 0;                           // no session's offset exceeds this (steps since streaming_start / the last seek; resets
                                                     // only lower offsets): picks the step program's variant (attn_variant)
     long xlds_launches = 0;         // launches (or graph nodes captured) that took k_gemm_xlds: mmi_lm_stat(lm, 0)
+    long rows_launches = 0;         // launches (or graph nodes captured) that took k_gemm_rows: mmi_lm_stat(lm, 4)
     bool precapture_failed = false; // capturing the second attention program ahead of time failed once: not tried again for this stream
     bool dominant_xlds = false;     // the profiled (dominant) GEMM ran on k_gemm_xlds
     MmiProgram prog;
@@ -502,7 +503,54 @@ int launch_once(hipStream_t s, int T, int mt, int kmax, dim3 groups, const GemmA
     return MMI_OK;
 }
 
+// k_gemm_rows: more than two batch tiles of 32 (a handle of mmi_lm_create_rows, 65..128 model rows; bf16 linears).  Two n-tiles
+// per workgroup once that still leaves every CU a workgroup (halves the activation bytes read from L2), else one.
+// knobs.rows_ntw = 1 / 2 forces either (same-box A/B; bit-identical).
+template <int MT>
+int launch_rows_mt(hipStream_t s, int ntw, int NT, int ksplit, const GemmArgs& a) {
+    const dim3 groups(mmi_cdiv(NT, ntw), ksplit);
+    if (ntw == 2) MMI_LAUNCH((k_gemm_rows<32, MT, 2, 1>), groups, 256, 0, s, a);
+    else MMI_LAUNCH((k_gemm_rows<32, MT, 1, 2>), groups, 256, 0, s, a);
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+int launch_rows(const MmiKnobs& k, hipStream_t s, const GemmW& g, const GemmPlan& p, int mt, const GemmArgs& a) {
+    if (g.T != 32 || g.wq != 0 || a.wq != 0) return mmi_fail(MMI_ERR_UNSUPPORTED, "more than 64 rows need bf16 linears at the 32-row tile");
+    int ntw = (long)g.NT * p.ksplit >= 512 ? 2 : 1;
+    if (k.rows_ntw) ntw = k.rows_ntw;
+    if (mt == 3) return launch_rows_mt<3>(s, ntw, g.NT, p.ksplit, a);
+    if (mt == 4) return launch_rows_mt<4>(s, ntw, g.NT, p.ksplit, a);
+    return mmi_fail(MMI_ERR_UNSUPPORTED, "batch too large for the many-row GEMM");
+}
+
+// The A/B control of k_gemm_rows (knobs.rows_groups, off by default): the same GEMM as one launch of the <= 64-row kernels per
+// group of two batch tiles - the weights cross HBM once per group.  GemmArgs moved to the group's rows, as
+// mmi_gemm_batch_tile_view does on the device.  Only for the epilogues whose addressing is per row (store, gate, RoPE + ring).
+bool rows_groups_ok(const GemmArgs& a) { return a.epi == MMI_EPI_STORE || a.epi == MMI_EPI_GATE || a.epi == MMI_EPI_ROPE_KV; }
+GemmArgs rows_group_view(const GemmArgs& a_in, int r0, int rows) {
+    GemmArgs a = a_in;
+    a.xp += (long)(r0 / 32) * a.KSTEPS * 64;
+    const long oshift = a.out_mode == MMI_OUT_PACKED ? (long)(r0 / 32) * a.out_ksteps * 512 : (long)r0 * a.out_ld;
+    if (a.out) a.out += oshift;
+    if (a.epi == MMI_EPI_ROPE_KV) {
+        const long ring = (long)r0 * a.H * a.cap * a.Dh / (a.kv8 ? 2 : 1);      // uint16 units: an fp8 ring holds bytes
+        a.qrot += (long)r0 * a.H * a.Dh; a.kc += ring; a.vc += ring;
+        a.offsets += r0; a.rope += (long)r0 * a.Dh;
+    }
+    a.B = rows;
+    return a;
+}
+
 int launch_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, GemmArgs a, bool is_dominant) {
+    if (lm->knobs.rows_groups && a.B > 64 && g.T == 32 && g.wq == 0 && rows_groups_ok(a)) {
+        GemmArgs full = a;
+        full.KSTEPS = g.KSTEPS;
+        for (int r0 = 0; r0 < a.B; r0 += 64) {
+            const int rc = launch_gemm(lm, s, g, rows_group_view(full, r0, a.B - r0 < 64 ? a.B - r0 : 64), is_dominant && r0 == 0);
+            if (rc) return rc;
+        }
+        return MMI_OK;
+    }
     a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT;
     a.wscale = g.scale; a.wscb = g.scb; a.gate_rows = g.gate ? g.N : 0;
     a.wq = (g.wq == 1 && a.wq >= 3) ? a.wq : g.wq;             // int8 linears: 3 / 4 = int8 activations (set by the program builder)
@@ -527,7 +575,11 @@ int launch_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, GemmArgs a, bool is_d
     int rc;
     mmi_record_bytes((long)g.bytes);
     if (is_dominant) lm->dominant_xlds = xl.on;
-    if (xl.on) {
+    if (mt > 2) {
+        lm->rows_launches += 1;
+        a.osplit = 1;
+        rc = launch_rows(k, s, g, p, mt, a);
+    } else if (xl.on) {
         lm->xlds_launches += 1;
         rc = mt == 1 ? launch_xlds<1>(s, xl, a) : launch_xlds<2>(s, xl, a);
     } else if (const int kmax = once_kmax(k.gemm_once, g, p, mt, a)) {
@@ -734,7 +786,7 @@ void add_norm_gemm(mmi_lm* lm, const GemmW& g, uint16_t* x, const uint16_t* alph
                    int out_features, bool out_packed, int epi, const DepKv* kv = nullptr) {
     const bool a8 = lm->act8 && g.wq == 1;
     const int wq = a8 ? 3 : g.wq;
-    const bool fuse = g.KSTEPS <= (wq ? 32 : 64) && !lm->knobs.no_norm_fusion;
+    const bool fuse = g.KSTEPS <= (wq ? 32 : 64) && !lm->knobs.no_norm_fusion && mmi_cdiv(lm->batch, g.T) <= 2;   // k_gemm_rows has no fused norm
     if (!fuse) {
         if (a8) {
             add_resid_rmsnorm(lm, x, Pending{}, alpha, xn_scratch, D, lm->dxnq, lm->sx_dxn, g.T);
@@ -1319,11 +1371,29 @@ extern "C" int mmi_lm_create(const mmi_lm_cfg* cfg, const mmi_tensor_desc* weigh
     return mmi_lm_create_ext(cfg, nullptr, weights, n_weights, max_batch, out);
 }
 
+static int lm_create_rows(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ext, const mmi_tensor_desc* weights, int32_t n_weights,
+                          int32_t max_batch, mmi_lm** out);
+
 extern "C" int mmi_lm_create_ext(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ext, const mmi_tensor_desc* weights, int32_t n_weights,
                                  int32_t max_batch, mmi_lm** out) {
+    if (max_batch > 64)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "max_batch > 64 sessions per GPU is not supported by mmi_lm_create / mmi_lm_create_ext: "
+                                             "mmi_lm_create_rows takes up to 128 model rows (bf16 linears)");
+    return lm_create_rows(cfg, ext, weights, n_weights, max_batch, out);
+}
+
+// Up to 128 model rows per handle: above 64 the step's linears run on k_gemm_rows (3 or 4 batch tiles of 32, bf16 weights).
+// max_rows <= 64 is mmi_lm_create_ext: the same launch lists, the same bits.
+extern "C" int mmi_lm_create_rows(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ext, const mmi_tensor_desc* weights, int32_t n_weights,
+                                  int32_t max_rows, mmi_lm** out) {
+    if (max_rows > 128) return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_create_rows: max_rows > 128 model rows per handle is not supported");
+    return lm_create_rows(cfg, ext, weights, n_weights, max_rows, out);
+}
+
+static int lm_create_rows(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ext, const mmi_tensor_desc* weights, int32_t n_weights,
+                          int32_t max_batch, mmi_lm** out) {
     const MmiKnobs knobs = mmi_knobs_from_env();     // the handle's one reading of the environment
     if (!cfg || !weights || !out || max_batch <= 0) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_create: bad argument");
-    if (max_batch > 64) return mmi_fail(MMI_ERR_UNSUPPORTED, "max_batch > 64 sessions per GPU is not supported yet");
     mmi_lm_cfg norm_cfg = *cfg;
     if (norm_cfg.dep_q == 0) {   // "No-Depformer --- e.g., an ASR model" (lm.py:218-221): text stream only; the depth-transformer
         norm_cfg.depformer_num_layers = 0;   // fields are then unused, give them inert values so that the sizing code stays generic
@@ -1355,6 +1425,10 @@ extern "C" int mmi_lm_create_ext(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ex
     const int low_rank = x.depformer_low_rank;
     if (low_rank < 0 || low_rank % 8) return mmi_fail(MMI_ERR_INVALID, "depformer_low_rank_embeddings must be a multiple of 8");
     const bool demux = x.demux_second_text_stream != 0;
+    if (max_batch > 64)   // k_gemm_rows is bf16.  Mixed widths are refused by load_linear, so any quantised linear's descriptor
+        for (int i = 0; i < n_weights; ++i)   // settles it - before a byte of the model is uploaded and packed
+            if (weights[i].ndim == 2 && (weights[i].dtype == MMI_I8 || weights[i].dtype == MMI_F8E4M3))
+                return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_create_rows: int8 / fp8 linears are not supported above 64 model rows (k_gemm_rows is bf16)");
     mmi_lm* lm = new mmi_lm();
     lm->knobs = knobs;
     lm->wts.poison = lm->st.poison = knobs.debug_poison;
@@ -2315,6 +2389,8 @@ extern "C" int mmi_lm_debug_linear(mmi_lm* lm, const char* weight_name, const ch
         return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_linear: codes / absmax exist on the int8 x int8 paths that materialise the operand (plain, split-K, norm)");
     hipStream_t s = (hipStream_t)stream;
     const int T = g.T, mt = mmi_cdiv(rows, T), KS = mmi_kstep(T);
+    if (mt > 2 && (path == MMI_DBG_FUSED || path == MMI_DBG_NORM_FUSED))
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_linear: the fused forms are not selected above 64 rows (k_gemm_rows + a norm launch)");
     const int K = g.K, N = g.N, kin = packed_ksteps_t(lm, T, K), kout = packed_ksteps_t(lm, T, N);
     const int nthK = [&] { int n = mmi_cdiv(K / 8, 64) * 64; return n > 1024 ? 1024 : n; }();
     MmiArena A;
@@ -2423,6 +2499,7 @@ extern "C" int64_t mmi_lm_stat(const mmi_lm* lm, int32_t which) {
     }
     if (which == 2) return (int64_t)lm->depth_bound;
     if (which == 3) return (int64_t)lm->Td;               // the depth transformer's MFMA tile (16 / 32)
+    if (which == 4) return (int64_t)lm->rows_launches;
     return -1;
 }
 

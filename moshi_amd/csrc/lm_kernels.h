@@ -19,11 +19,11 @@
 // ------------------------------------------------------------------------------------------------
 // fragment-packed layouts
 // ------------------------------------------------------------------------------------------------
-// Every GEMM of the step is out[b][n] = sum_k x[b][k] * W[n][k] with a handful of batch rows (B <= 64) and weights
+// Every GEMM of the step is out[b][n] = sum_k x[b][k] * W[n][k] with a handful of batch rows (one to four tiles of T) and weights
 // that are read exactly once per step, i.e. an HBM stream.  Both operands are kept in HBM in the order the MFMA
 // wants them in registers, so that one wave instruction (16 bytes per lane) is one contiguous, fully coalesced
 // 1 KiB read that feeds one MFMA without any shuffling:
-//   T = 32 (v_mfma_f32_32x32x16_bf16, 17..64 sessions): k-step = 16; lane l holds rows/cols (l & 31), k = 8*(l>>5)+e
+//   T = 32 (v_mfma_f32_32x32x16_bf16, 17..128 rows)   : k-step = 16; lane l holds rows/cols (l & 31), k = 8*(l>>5)+e
 //   T = 16 (v_mfma_f32_16x16x32_bf16, <= 16 sessions) : k-step = 32; lane l holds rows/cols (l & 15), k = 8*(l>>4)+e
 //   weights     Wp[nt][ks][lane][e] = W[nt*T + (l & (T-1))][ks*KS + 8*(l / T) + e]            (zero padded)
 //   activations Xp[mt][ks][lane][e] = x[mt*T + (l & (T-1))][ks*KS + 8*(l / T) + e]            (zero padded)
@@ -705,6 +705,115 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemm_xp_once(GemmArgs a) {
 #pragma unroll
         for (int r = 0; r < R; ++r) accv[0][m][r] = acc[m][r];
     mmi_gemm_epilogue<TN, MT, 1, WAVES>(a, accv, wave, lane, nt0, pre, nullptr, g_lo, g_hi);
+}
+
+// The many-row GEMM: 65..128 model rows = MT = 3 or 4 batch tiles of 32 against bf16 weights (a handle of mmi_lm_create_rows).
+// Same packed operands and the same weight stream as k_gemm_xp; every weight fragment a wave loads meets all MT activation tiles
+// before it is dropped, so the weights of a launch cross HBM once whatever the row count.  K is cut over gridDim.y workgroups and
+// then over the workgroup's 4 waves exactly as in k_gemm_xp, each wave walks its slice in ascending k and the waves' partial
+// tiles are summed in wave order: a row's sums do not depend on MT, on NTW, on the tile the row sits in or on how full the tiles
+// are (MFMA columns are independent).
+// NTW n-tiles per workgroup (2 for the wide GEMMs: every workgroup reads the whole MT KiB-per-k-step activation matrix from L2,
+// four times the bytes of one weight tile at MT = 4, and two tiles per workgroup halve that traffic).
+// Registers (MT = 4): 64 accumulators per n-tile + (NTW + MT) * 4 per fragment set in flight, two sets of U k-steps:
+// NTW = 1, U = 2: 64 + 80; NTW = 2, U = 1: 128 + 48 - held under 256 so that two workgroups share a CU.
+// Reduction scratch: WAVES * MT * 64 * LS floats for ONE n-tile = 64 KiB at 4 waves, MT = 4 (LS = 16) - the static array of
+// mmi_gemm_epilogue.  Fewer waves (4, not 8) is what makes it fit; with NTW = 2 the tiles go through the same scratch one
+// after the other (a barrier between them), not side by side.
+template <int TN, int MT, int NTW, int U>
+__global__ __launch_bounds__(256, 2) void k_gemm_rows(GemmArgs a) {
+    static_assert(TN == 32 && MT >= 3 && MT <= 4 && NTW >= 1 && NTW <= 2, "k_gemm_rows: 32-row tiles, 3 or 4 of them");
+    constexpr int WAVES = 4, R = 16;
+    typedef float acc_t __attribute__((ext_vector_type(R)));
+    const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
+    const int nt0 = (int)blockIdx.x * NTW;
+    u32x4 pre[NTW];
+#pragma unroll
+    for (int t = 0; t < NTW; ++t) pre[t] = mmi_gemm_prefetch_addend<TN, MT, 1>(a, nt0 + t);
+
+    // K range of this workgroup (gridDim.y > 1: split-K over workgroups), then of this wave: k_gemm_xp's partition
+    const int kb_per = (a.KSTEPS + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int kb0 = min(a.KSTEPS, (int)blockIdx.y * kb_per), kb1 = min(a.KSTEPS, kb0 + kb_per);
+    const int kper = (kb1 - kb0 + WAVES - 1) / WAVES;
+    const int ks0 = min(kb1, kb0 + wave * kper);
+    const int nks = min(kb1, ks0 + kper) - ks0;
+    const int ksl = min(ks0, a.KSTEPS - 1);          // an empty slice (nks == 0) still forms valid addresses
+
+    const u32x4* wp[NTW];
+    const u32x4* xp[MT];
+#pragma unroll
+    for (int t = 0; t < NTW; ++t) wp[t] = a.wp + ((long)min(nt0 + t, a.NT - 1) * a.KSTEPS + ksl) * 64 + lane;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) xp[m] = a.xp + ((long)m * a.KSTEPS + ksl) * 64 + lane;
+
+    acc_t acc[NTW][MT];
+#pragma unroll
+    for (int t = 0; t < NTW; ++t)
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int r = 0; r < R; ++r) acc[t][m][r] = 0.f;
+
+    u32x4 wA[U][NTW], xA[U][MT], wB[U][NTW], xB[U][MT];
+#define MMI_R_LOAD(W_, X_, base)                                                              \
+    _Pragma("unroll") for (int u = 0; u < U; ++u) {                                           \
+        _Pragma("unroll") for (int t = 0; t < NTW; ++t) W_[u][t] = mmi_load_nt(wp[t] + ((base) + u) * 64); \
+        _Pragma("unroll") for (int m = 0; m < MT; ++m) X_[u][m] = xp[m][((base) + u) * 64];   \
+    }
+#define MMI_R_MMA1(W_, X_, u)                                                                 \
+    _Pragma("unroll") for (int t = 0; t < NTW; ++t)                                           \
+        _Pragma("unroll") for (int m = 0; m < MT; ++m) acc[t][m] = mmi_mfma_bf16_32x32x16(W_[u][t], X_[u][m], acc[t][m]);
+#define MMI_R_MMA(W_, X_)                                                                     \
+    _Pragma("unroll") for (int u = 0; u < U; ++u) { MMI_R_MMA1(W_, X_, u) }
+    const int nfull = nks / U;
+    if (nfull > 0) {
+        // steady state without conditional loads (see k_gemm_xp): the loads of the next group stay in flight behind the MFMAs
+        MMI_R_LOAD(wA, xA, 0);
+        int g = 0;
+        for (; g + 2 < nfull; g += 2) {
+            MMI_R_LOAD(wB, xB, (g + 1) * U);
+            MMI_R_MMA(wA, xA);
+            MMI_R_LOAD(wA, xA, (g + 2) * U);
+            MMI_R_MMA(wB, xB);
+        }
+        if (nfull - g == 2) {
+            MMI_R_LOAD(wB, xB, (g + 1) * U);
+            MMI_R_MMA(wA, xA);
+            MMI_R_MMA(wB, xB);
+        } else {
+            MMI_R_MMA(wA, xA);
+        }
+    }
+    // remainder of the slice (fewer than U k-steps): loaded together from clamped (valid) entries, only the live ones multiplied
+    if constexpr (U > 1) {
+        const int rem = nks - nfull * U;
+        if (rem > 0) {
+#pragma unroll
+            for (int u = 0; u < U - 1; ++u) {
+                const int ks = nfull * U + min(u, rem - 1);
+#pragma unroll
+                for (int t = 0; t < NTW; ++t) wA[u][t] = mmi_load_nt(wp[t] + ks * 64);
+#pragma unroll
+                for (int m = 0; m < MT; ++m) xA[u][m] = xp[m][ks * 64];
+            }
+#pragma unroll
+            for (int u = 0; u < U - 1; ++u)
+                if (u < rem) { MMI_R_MMA1(wA, xA, u) }
+        }
+    }
+#undef MMI_R_LOAD
+#undef MMI_R_MMA
+#undef MMI_R_MMA1
+#pragma unroll
+    for (int t = 0; t < NTW; ++t) {
+        float accv[1][MT][R];
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int r = 0; r < R; ++r) accv[0][m][r] = acc[t][m][r];
+        if (t > 0) __syncthreads();                  // the previous tile's sums have been read out of the scratch
+        mmi_gemm_epilogue<TN, MT, 1, WAVES>(a, accv, wave, lane, nt0 + t, pre[t]);
+    }
 }
 
 // RMSNorm fused into the GEMM that consumes it (the depth transformer: norm1 -> in_proj, norm2 -> linear_in; rows of

@@ -41,6 +41,10 @@ struct MmiKnobs {
     bool q8_act_bf16 = false;       // MMI_Q8_ACT=bf16: int8 linears weight-only (rounds 1-3) instead of int8 x int8
     bool q8_u2 = false;             // MMI_Q8_U=2: two entries per register buffer on int8 x int8 (the weight-only depth, same-box A/B)
     bool q8_tiles_serial = false;   // MMI_Q8_TILES=serial: k_gemm_q8 at 33..64 sessions walks both batch tiles in one workgroup (the round-4 form)
+    // ---- LM engine: more than 64 model rows (mmi_lm_create_rows)
+    bool rows_groups = false;       // MMI_ROWS_GROUPS=1: the A/B control of k_gemm_rows - the store / gate / RoPE GEMMs as one launch of the
+                                    // <= 64-row kernels per group of two batch tiles (the weights cross HBM once per group)
+    int rows_ntw = 0;               // MMI_ROWS_NTW=1 / 2: n-tiles per k_gemm_rows workgroup (same-box A/B; bit-identical); unset = by tile count
     // ---- LM engine: attention
     bool attn_split = false;        // MMI_ATTN: "wave" (default since round 4) = k_lm_attn_wave; "split" = the chunked kernel of rounds 1-3
     int attn_ns = 0;                // MMI_ATTN_NS=1..16: test hook: the split + combine path on rings too short to need it
@@ -121,6 +125,11 @@ inline MmiKnobs mmi_knobs_from_env() {
     k.q8_act_bf16 = first("MMI_Q8_ACT") == 'b';
     k.q8_u2 = first("MMI_Q8_U") == '2';
     k.q8_tiles_serial = first("MMI_Q8_TILES") == 's';
+    {
+        const char* e = getenv("MMI_ROWS_GROUPS");
+        k.rows_groups = e && e[0] && e[0] != '0';
+    }
+    k.rows_ntw = one_of(number("MMI_ROWS_NTW", 0), {1, 2});
     k.attn_split = first("MMI_ATTN") == 's';
     {
         const int v = number("MMI_ATTN_NS", 0);

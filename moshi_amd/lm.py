@@ -112,7 +112,9 @@ class LMModel:
         state_dict: bf16 tensors named as in the reference checkpoints.
         config: architecture hyper-parameters (defaults = Moshi-7B, loaders.py:90-119).
         device: a ROCm `cuda` device for the product library.
-        max_batch: largest number of concurrent sessions `LMGen.streaming` will be asked for.
+        max_batch: largest number of concurrent sessions `LMGen.streaming` will be asked for (at most 64).
+        max_rows: instead of `max_batch`, a handle of up to 128 MODEL rows (mmi_lm_create_rows; bf16 linears): sessions, or two
+            rows per guided session.  `lm.max_batch` then reports it.  Not together with `max_batch > 64`.
         quantize: True converts the linears to row-wise int8 (`weight` + `weight_scb`), like the reference's `quantize=True`;
             "fp8" converts them to e4m3fn (`weight` + `weight_scale`) for the fp8 MFMA path (BASELINE configs[4]);
             a state dict that already carries int8 / fp8 weights is used as is.
@@ -121,7 +123,13 @@ class LMModel:
     def __init__(self, state_dict: Dict[str, torch.Tensor], config: Optional[LMConfig] = None,
                  device: torch.device | str = "cuda", max_batch: int = 32, lib: Optional[_capi.Lib] = None,
                  quantize: bool | str = False, fuser: Optional[ConditionFuser] = None, kv_cache: Optional[str] = None,
-                 cross_capacity: Optional[int] = None):
+                 cross_capacity: Optional[int] = None, max_rows: Optional[int] = None):
+        if max_rows is not None:
+            if max_batch > 64:
+                raise ValueError("max_rows and max_batch > 64 are mutually exclusive: max_rows alone sizes the handle")
+            if int(max_rows) < 1:
+                raise ValueError("max_rows must be >= 1")
+            max_batch = int(max_rows)
         self.config = config or LMConfig()
         if kv_cache is not None:         # "fp8": e4m3 KV ring (half the attention stream); default: the config's (bf16)
             from dataclasses import replace
@@ -163,7 +171,10 @@ class LMModel:
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         with _capi.device_scope(self.device):             # the handle binds to the device current at create
-            if ext is None:
+            if max_rows is not None:
+                lib.check(lib.mmi_lm_create_rows(C.byref(cfg), C.byref(ext) if ext is not None else None, descs, len(sd), max_batch,
+                                                 C.byref(self._handle)))
+            elif ext is None:
                 lib.check(lib.mmi_lm_create(C.byref(cfg), descs, len(sd), max_batch, C.byref(self._handle)))
             else:
                 lib.check(lib.mmi_lm_create_ext(C.byref(cfg), C.byref(ext), descs, len(sd), max_batch, C.byref(self._handle)))

@@ -152,9 +152,10 @@ def get_condition_fuser(cfg: dict) -> ConditionFuser:    # loaders.py:476-483
 def get_moshi_lm(filename: str | Path | None, lm_kwargs: Optional[Dict[str, Any]] = None, device: torch.device | str = "cuda",
                  dtype: torch.dtype = torch.bfloat16, lora_weights: str | Path | None = None, fuse_lora: bool = False,
                  lm_kwargs_overrides: Optional[dict] = None, max_batch: int = 32, lib=None, state_patch=None,
-                 quantize: Optional[bool | str] = None) -> LMModel:
+                 quantize: Optional[bool | str] = None, max_rows: Optional[int] = None) -> LMModel:
     """loaders.get_moshi_lm (loaders.py:366-446): bf16 weights; `quantize` in the config (a `.q8` checkpoint carrying int8
-    `weight` + `weight_scb`, or fp8 `weight` + `weight_scale`) is taken from the tensors themselves."""
+    `weight` + `weight_scb`, or fp8 `weight` + `weight_scale`) is taken from the tensors themselves.  `max_rows`: a handle of
+    up to 128 model rows instead of `max_batch` sessions (LMModel)."""
     assert dtype == torch.bfloat16, "the engine computes the LM in bf16 (fp32 accumulation), like the reference's default"
     kw = dict(lm_kwargs) if lm_kwargs is not None else None
     if kw is not None:
@@ -194,7 +195,14 @@ def get_moshi_lm(filename: str | Path | None, lm_kwargs: Optional[Dict[str, Any]
     if state_patch is not None:
         state_patch(state)
     already = any(v.dtype in (torch.int8, torch.float8_e4m3fn) for v in state.values())
-    return LMModel(state, cfg, device=device, max_batch=max_batch, lib=lib, quantize=False if already else quantize, fuser=fuser)
+    return LMModel(state, cfg, device=device, max_batch=max_batch, lib=lib, quantize=False if already else quantize, fuser=fuser,
+                   max_rows=max_rows)
+
+
+def lm_size_kwargs(slots: int, rows_per_session: int = 1) -> Dict[str, int]:
+    """How a caller that knows its sessions sizes the LM handle: `max_batch` up to 64 model rows, `max_rows` above (LMModel)."""
+    rows = int(slots) * int(rows_per_session)
+    return {"max_rows": rows} if rows > 64 else {"max_batch": rows}
 
 
 def export_quantized(src: str | Path, dst: str | Path, fmt: str = "int8", lm_kwargs: Optional[dict] = None) -> Dict[str, int]:

@@ -165,7 +165,7 @@ def main(argv: Optional[List[str]] = None) -> None:
     log("info", "loading mimi")
     mimi = info.get_mimi(device=args.device, max_batch=args.batch_size)
     log("info", "loading moshi")
-    lm = info.get_moshi(device=args.device, max_batch=args.batch_size * (2 if args.cfg_coef != 1.0 else 1),
+    lm = info.get_moshi(device=args.device, **loaders.lm_size_kwargs(args.batch_size, 2 if args.cfg_coef != 1.0 else 1),
                         quantize=None if args.quantize == "none" else args.quantize)
     tokenizer = None
     if info.tokenizer is not None:

@@ -365,7 +365,7 @@ def main(argv=None):                                  # pragma: no cover - needs
     from aiohttp import web
 
     from .batcher import SessionBatcher
-    from .loaders import CheckpointInfo
+    from .loaders import CheckpointInfo, lm_size_kwargs
     ap = argparse.ArgumentParser()
     ap.add_argument("--host", default="localhost")
     ap.add_argument("--port", default=8998, type=int)
@@ -377,7 +377,7 @@ def main(argv=None):                                  # pragma: no cover - needs
     args = ap.parse_args(argv)
     info = CheckpointInfo.from_local(args.checkpoint)
     mimi = info.get_mimi(device=args.device, max_batch=args.slots)
-    lm = info.get_moshi(device=args.device, max_batch=args.slots * (2 if args.cfg_coef != 1.0 else 1))
+    lm = info.get_moshi(device=args.device, **lm_size_kwargs(args.slots, 2 if args.cfg_coef != 1.0 else 1))
     text_piece = None
     if info.tokenizer is not None and info.tokenizer.exists():
         import sentencepiece

@@ -7,8 +7,21 @@
 //   hipcc --offload-arch=gfx950 -O2 -std=c++17 -ffp-contract=off -Iinclude scripts/native_selftest.cpp -Lmoshi_amd -lmoshi_mi \
 //         -Wl,-rpath,'$ORIGIN/../moshi_amd' -o build/native_selftest && build/native_selftest tests/golden/native_selftest
 //
+// `native_selftest <dir> --rows 65,128`: the LM alone on handles of that many model rows (mmi_lm_create_rows, the many-row GEMM): row r
+// replays the fixture's session r % B against the same recorded values, and a snapshot taken mid-stream resumes bit for bit.
+//
 // The same source builds against the CPU simulator (-DMMI_SELFTEST_SIM, tests/test_native_selftest.py), which is how the expected
 // values and this program are checked where there is no GPU.  The checker side (oracle) never runs here: only its recorded output.
+//
+// The sanitizer run (host code only: the engine and its kernels compiled for the simulator into ONE program with this main, no
+// LD_PRELOAD, no GPU); both modes must end in SELFTEST PASSED with no report:
+//
+//   clang++ -O1 -g -std=c++17 -ffp-contract=off -pthread -w -fsanitize=address,undefined -fno-omit-frame-pointer \
+//         -DHIPSIM_UCONTEXT -DMMI_SELFTEST_SIM -Itests/hipsim -Imoshi_amd/csrc -Iinclude -x c++ \
+//         moshi_amd/csrc/{api_common,mimi_engine,lm_engine,batcher,duplex}.hip tests/hipsim/hipsim.cpp scripts/native_selftest.cpp \
+//         -o build/native_selftest_san
+//   export MMI_NO_GRAPH=1 ASAN_OPTIONS=detect_leaks=0:detect_stack_use_after_return=0 UBSAN_OPTIONS=print_stacktrace=1
+//   build/native_selftest_san tests/golden/native_selftest && build/native_selftest_san tests/golden/native_selftest --rows 65,128
 #include "moshi_mi.h"
 #ifdef MMI_SELFTEST_SIM
 #include "hipsim.h"
@@ -40,7 +53,14 @@ struct Tensor { std::string model, name; int bf16, ndim; long d[4]; float base, 
 struct Expected { std::string name; int i64; long count, off; };
 
 int main(int argc, char** argv) {
-    const std::string dir = argc > 1 ? argv[1] : "tests/golden/native_selftest";
+    const std::string dir = argc > 1 && strncmp(argv[1], "--", 2) ? argv[1] : "tests/golden/native_selftest";
+    // --rows N[,N...]: instead of the codec + LM pass, the LM alone on handles of N model rows made by mmi_lm_create_rows (65..128:
+    // the many-row GEMM).  Row r replays the fixture's session r % B - rows never mix, so its ring outputs and
+    // logits are the oracle's recorded ones - then a snapshot taken mid-stream must resume bit for bit.
+    std::vector<int> many_rows;
+    for (int i = 1; i + 1 < argc; ++i)
+        if (!strcmp(argv[i], "--rows"))
+            for (const char* q = argv[i + 1]; *q; q = strchr(q, ',') ? strchr(q, ',') + 1 : q + strlen(q)) many_rows.push_back(atoi(q));
     FILE* mf = fopen((dir + "/manifest.txt").c_str(), "r");
     if (!mf) { printf("cannot open %s/manifest.txt\n", dir.c_str()); return 2; }
     mmi_mimi_cfg mc; mmi_lm_cfg lc;
@@ -112,7 +132,7 @@ int main(int argc, char** argv) {
     int failures = 0;
 
     // ---- Mimi: encode FR frames, decode the oracle's codes
-    {
+    if (many_rows.empty()) {
         mmi_mimi* m = nullptr;
         MCK(mmi_mimi_create(&mc, md.data(), (int32_t)md.size(), B, &m));
         MCK(mmi_mimi_set_num_codebooks(m, K));
@@ -151,7 +171,7 @@ int main(int argc, char** argv) {
         mmi_mimi_destroy(m);
     }
     // ---- LM: greedy steps, teacher-forced with the oracle's tokens
-    {
+    if (many_rows.empty()) {
         mmi_lm* lm = nullptr;
         MCK(mmi_lm_create(&lc, ld.data(), (int32_t)ld.size(), B, &lm));
         mmi_sampling sp; memset(&sp, 0, sizeof(sp));
@@ -196,6 +216,76 @@ int main(int argc, char** argv) {
         failures += tok_diffs != 0 || !(worst_max <= 0.05) || !(worst_mean <= 0.012);
         MCK(mmi_lm_streaming_stop(lm));
         mmi_lm_destroy(lm);
+    }
+    for (int R : many_rows) {
+        mmi_lm* lm = nullptr;
+        MCK(mmi_lm_create_rows(&lc, nullptr, ld.data(), (int32_t)ld.size(), R, &lm));
+        mmi_sampling sp; memset(&sp, 0, sizeof(sp));
+        sp.use_sampling = 0; sp.temp = 0.8f; sp.temp_text = 0.7f; sp.top_k = 250; sp.top_k_text = 25; sp.seed = 0;
+        MCK(mmi_lm_streaming_start(lm, R, &sp, nullptr));
+        const int NT = dep_q + 1;
+        const int64_t* eforced = (const int64_t*)expect("lm_forced");
+        const int64_t* eout = (const int64_t*)expect("lm_out");
+        const float* etl = (const float*)expect("lm_text_logits");
+        const float* eal = (const float*)expect("lm_audio_logits");
+        int64_t *duc, *dforced, *dout; float *dtl, *dal; void* dsnap;
+        HCK(hipMalloc((void**)&duc, (size_t)R * n_user * 8)); HCK(hipMalloc((void**)&dforced, (size_t)R * NT * 8));
+        HCK(hipMalloc((void**)&dout, (size_t)R * NT * 8));
+        HCK(hipMalloc((void**)&dtl, (size_t)R * text_card * 4)); HCK(hipMalloc((void**)&dal, (size_t)R * dep_q * card * 4));
+        const int64_t snap_bytes = mmi_lm_state_bytes(lm);
+        HCK(hipMalloc(&dsnap, (size_t)snap_bytes));
+        long tok_diffs = 0, snap_diffs = 0; double worst_max = 0, worst_mean = 0;
+        auto site = [&](const float* a, const float* r, int n) {
+            double mx = 1e-6, dmax = 0, dsum = 0;
+            for (int i = 0; i < n; ++i) { mx = fmax(mx, fabs(r[i])); const double d = fabs(a[i] - r[i]); dmax = fmax(dmax, d); dsum += d; }
+            worst_max = fmax(worst_max, dmax / mx); worst_mean = fmax(worst_mean, dsum / n / mx);
+        };
+        std::vector<int64_t> o((size_t)R * NT); std::vector<float> tl((size_t)R * text_card), al((size_t)R * dep_q * card);
+        auto step = [&](int s) {
+            std::vector<int64_t> uc1((size_t)B * n_user), uc((size_t)R * n_user), fo((size_t)R * NT);
+            for (size_t i = 0; i < uc1.size(); ++i) uc1[i] = (int64_t)((u_of(9000u + s, (uint32_t)i) + 1.0f) * 32768.0f) % card;
+            for (int r = 0; r < R; ++r) {
+                memcpy(uc.data() + (size_t)r * n_user, uc1.data() + (size_t)(r % B) * n_user, (size_t)n_user * 8);
+                memcpy(fo.data() + (size_t)r * NT, eforced + ((size_t)s * B + r % B) * NT, (size_t)NT * 8);
+            }
+            HCK(hipMemcpy(duc, uc.data(), uc.size() * 8, hipMemcpyHostToDevice));
+            HCK(hipMemcpy(dforced, fo.data(), fo.size() * 8, hipMemcpyHostToDevice));
+            MCK(mmi_lm_force_next_tokens(lm, dforced, nullptr));
+            int32_t valid = 0;
+            MCK(mmi_lm_step(lm, duc, n_user, dout, dtl, dal, nullptr, R, &valid, nullptr));
+            HCK(hipDeviceSynchronize());
+            HCK(hipMemcpy(o.data(), dout, o.size() * 8, hipMemcpyDeviceToHost));
+            HCK(hipMemcpy(tl.data(), dtl, tl.size() * 4, hipMemcpyDeviceToHost));
+            HCK(hipMemcpy(al.data(), dal, al.size() * 4, hipMemcpyDeviceToHost));
+        };
+        auto against_oracle = [&](int s) {
+            for (int r = 0; r < R; ++r) {
+                const int b = r % B;
+                for (int i = 0; i < NT; ++i) tok_diffs += o[(size_t)r * NT + i] != eout[((size_t)s * B + b) * NT + i];
+                site(tl.data() + (size_t)r * text_card, etl + ((size_t)s * B + b) * text_card, text_card);
+                for (int k = 0; k < dep_q; ++k) site(al.data() + ((size_t)r * dep_q + k) * card, eal + (((size_t)s * B + b) * dep_q + k) * card, card);
+            }
+        };
+        const int cut = ST / 2;
+        int64_t host_word = 0;
+        for (int s = 0; s < cut; ++s) { step(s); against_oracle(s); }
+        MCK(mmi_lm_state_save(lm, dsnap, snap_bytes, &host_word, nullptr));
+        std::vector<std::vector<int64_t>> first_o; std::vector<std::vector<float>> first_tl, first_al;
+        for (int s = cut; s < ST; ++s) { step(s); against_oracle(s); first_o.push_back(o); first_tl.push_back(tl); first_al.push_back(al); }
+        step(0);                                         // wander off
+        MCK(mmi_lm_state_load(lm, dsnap, snap_bytes, host_word, nullptr));
+        for (int s = cut; s < ST; ++s) {
+            step(s);
+            snap_diffs += o != first_o[s - cut] || memcmp(tl.data(), first_tl[s - cut].data(), tl.size() * 4) != 0 ||
+                          memcmp(al.data(), first_al[s - cut].data(), al.size() * 4) != 0;
+        }
+        printf("lm %d rows (mmi_lm_create_rows, %lld k_gemm_rows launches): %ld of %d token-ring outputs differ from the oracle (must be 0); logits "
+               "worst max %.4f (<= 0.05), worst mean %.4f (<= 0.012); %ld of %d steps differ after the snapshot (must be 0)\n",
+               R, (long long)mmi_lm_stat(lm, 4), tok_diffs, ST * R * NT, worst_max, worst_mean, snap_diffs, ST - cut);
+        failures += tok_diffs != 0 || !(worst_max <= 0.05) || !(worst_mean <= 0.012) || snap_diffs != 0 || (R > 64 && mmi_lm_stat(lm, 4) <= 0);
+        MCK(mmi_lm_streaming_stop(lm));
+        mmi_lm_destroy(lm);
+        hipFree(duc); hipFree(dforced); hipFree(dout); hipFree(dtl); hipFree(dal); hipFree(dsnap);
     }
     printf(failures ? "SELFTEST FAILED\n" : "SELFTEST PASSED\n");
     return failures ? 1 : 0;
