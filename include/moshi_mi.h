@@ -45,7 +45,9 @@ typedef enum mmi_status {
     MMI_ERR_NO_CHANNEL = -8      /* batcher: the channel id names no open channel (closed, or re-opened under a new id) */
 } mmi_status;
 
-typedef enum mmi_dtype { MMI_F32 = 0, MMI_BF16 = 1, MMI_I64 = 2, MMI_F16 = 3, MMI_I8 = 4, MMI_F8E4M3 = 5 /* OCP e4m3fn */ } mmi_dtype;
+typedef enum mmi_dtype { MMI_F32 = 0, MMI_BF16 = 1, MMI_I64 = 2, MMI_F16 = 3, MMI_I8 = 4, MMI_F8E4M3 = 5 /* OCP e4m3fn */,
+                         MMI_F4E2M1X2 = 6 /* OCP MXFP4 codes, two E2M1 per byte (element 2i in the low nibble) */,
+                         MMI_E8M0 = 7 /* OCP MX block scale, 2^(s - 127) */ } mmi_dtype;
 
 typedef void* mmi_stream; /* hipStream_t */
 
@@ -203,7 +205,15 @@ typedef struct mmi_lm mmi_lm;
  * `<linear>.weight_scb` MMI_F32 [out] row absmax; or as fp8 (BASELINE configs[4], run on the fp8 MFMA): `<linear>.weight`
  * MMI_F8E4M3 [out,in] codes, `<linear>.weight_scale` MMI_F32 [out] (W ~= code * scale) and an optional scalar
  * `<linear>.input_scale` MMI_F32 (static activation scale: x8 = e4m3(x / input_scale), default 1).  Embeddings and norms
- * stay bf16.  The linears must be all bf16, all int8 or all fp8. */
+ * stay bf16.  The linears must be all bf16, all int8 or all fp8.
+ * Or as OCP MXFP4 (Microscaling v1.0; weight-only, widened to bf16 inside the GEMM by v_cvt_scalef32_pk_bf16_fp4 - exact, so
+ * the engine computes what the bf16 engine computes on the dequantised weights): `<linear>.weight` MMI_F4E2M1X2 [out, in/2],
+ * two E2M1 codes per byte (element 2i in the low nibble; bit 3 sign, bits 2..0 magnitude of {0, 0.5, 1, 1.5, 2, 3, 4, 6}),
+ * and `<linear>.weight_scale_e8m0` MMI_E8M0 [out, in/32], one scale 2^(s-127) per 32 consecutive input features of a row.
+ * Refused, before anything is uploaded: in_features not a multiple of 32 (MMI_ERR_UNSUPPORTED), a missing or mis-shaped scale
+ * tensor (MMI_ERR_MISSING_WEIGHT / MMI_ERR_SHAPE), a scale byte 255 - the E8M0 NaN - (MMI_ERR_INVALID), scale bytes outside
+ * 2..252 (MMI_ERR_UNSUPPORTED: every dequantised weight stays a normal, finite bf16), other quantised widths next to it,
+ * cross-attention layers, low-rank or demuxed embeddings, and more than 64 model rows (MMI_ERR_UNSUPPORTED). */
 int mmi_lm_create(const mmi_lm_cfg* cfg, const mmi_tensor_desc* weights, int32_t n_weights,
                   int32_t max_batch, mmi_lm** out);
 

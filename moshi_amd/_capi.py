@@ -18,10 +18,11 @@ DEFAULT_LIB = _PKG / "libmoshi_mi.so"
 
 MMI_OK, MMI_ERR_INVALID, MMI_ERR_SHAPE, MMI_ERR_STATE, MMI_ERR_HIP, MMI_ERR_MISSING_WEIGHT, MMI_ERR_UNSUPPORTED, MMI_ERR_BUSY, \
     MMI_ERR_NO_CHANNEL = 0, -1, -2, -3, -4, -5, -6, -7, -8
-MMI_F32, MMI_BF16, MMI_I64, MMI_F16, MMI_I8, MMI_F8E4M3 = 0, 1, 2, 3, 4, 5
+MMI_F32, MMI_BF16, MMI_I64, MMI_F16, MMI_I8, MMI_F8E4M3, MMI_F4E2M1X2, MMI_E8M0 = 0, 1, 2, 3, 4, 5, 6, 7
 
 _DTYPES = {torch.float32: MMI_F32, torch.bfloat16: MMI_BF16, torch.int64: MMI_I64, torch.float16: MMI_F16,
-           torch.int8: MMI_I8, torch.float8_e4m3fn: MMI_F8E4M3}
+           torch.int8: MMI_I8, torch.float8_e4m3fn: MMI_F8E4M3, torch.uint8: MMI_F4E2M1X2}
+MXFP4_SCALE_SUFFIX = ".weight_scale_e8m0"
 
 
 class TensorDesc(C.Structure):
@@ -305,6 +306,8 @@ def tensor_descs(state: Dict[str, torch.Tensor]):
         arr[i].name = nm
         arr[i].data = tc.data_ptr()
         arr[i].dtype = _DTYPES[t.dtype]
+        if t.dtype == torch.uint8:                 # MXFP4 storage: E2M1 code pairs and their E8M0 block scales, told apart by key
+            arr[i].dtype = MMI_E8M0 if name.endswith(MXFP4_SCALE_SUFFIX) else MMI_F4E2M1X2
         arr[i].ndim = tc.dim()
         if tc.dim() > 4:
             raise ValueError(f"rank > 4 tensor {name}")

@@ -16,7 +16,9 @@ struct GemmW {              // one packed nn.Linear
     int N = 0, K = 0, NT = 0, KSTEPS = 0, gate = 0;   // gate: N = hidden, gate/value rows interleaved per tile
     float* scale = nullptr;   // int8 weights: SCB / 127 per original weight row; fp8: weight_scale * input_scale; KSTEPS then counts k-step PAIRS
     float* scb = nullptr;     // int8 weights: the raw SCB (`weight_scb`), for the int8 x int8 dequantisation (mmi_i8_dequant)
-    int wq = 0;               // 0 bf16, 1 int8, 2 fp8
+    int wq = 0;               // 0 bf16, 1 int8, 2 fp8, 4 MXFP4 (KSTEPS then counts entries of FOUR k-steps; scale / scb stay null)
+    int ksteps = 0;           // MXFP4: the row's k-steps before padding to whole entries - what plan_gemm's thresholds count
+    uint8_t* s4 = nullptr;    // MXFP4: the E8M0 scale bytes in entry order (k_pack_w_fp4)
     float xinv = 1.f;         // fp8: 1 / input_scale
     size_t bytes = 0;
     int T = 32;               // the MFMA tile the weight is packed for (lm->T; the depth transformer's linears: lm->Td) - also the
@@ -54,7 +56,8 @@ struct mmi_lm {
                                     // microbenchmark's -0.13 ms (round 5, independent launches) does not survive the dependent chain.
                                     // Kept as an opt-in: the boundaries are row-major either way (dpre, dqkv, the logits)
     int q8 = -1;                    // -1 undecided, 0 bf16 linears, 1 int8 linears (`weight` int8 + `weight_scb`, utils/quantize.py),
-                                    // 2 fp8 linears (`weight` e4m3fn + `weight_scale` [+ `input_scale`]) run on the fp8 MFMA
+                                    // 2 fp8 linears (`weight` e4m3fn + `weight_scale` [+ `input_scale`]) run on the fp8 MFMA,
+                                    // 4 MXFP4 linears (`weight` E2M1 pairs + `weight_scale_e8m0`), widened to bf16 in the GEMM
     int NC = 0, CT = 0, max_delay = 0;
     MmiArena wts;
     // weights
@@ -212,16 +215,17 @@ __global__ void k_scb_to_scale(const float* __restrict__ scb, float* __restrict_
 
 // wp_dst / scale_dst: pack into a slice of a caller-owned allocation instead of a fresh one (see load_dep_in_group)
 int load_linear(mmi_lm* lm, const MmiWeights& W, const std::string& name, int N, int K, int gate_hidden, GemmW* g,
-                void* wp_dst = nullptr, float* scale_dst = nullptr, float* scb_dst = nullptr, int tile = 0) {
+                void* wp_dst = nullptr, float* scale_dst = nullptr, float* scb_dst = nullptr, int tile = 0, uint8_t* s4_dst = nullptr) {
     const mmi_tensor_desc* d = W.find(name);
     if (!d) return mmi_fail(MMI_ERR_MISSING_WEIGHT, "missing weight: " + name);
-    if (d->dtype != MMI_BF16 && d->dtype != MMI_I8 && d->dtype != MMI_F8E4M3)
+    if (d->dtype != MMI_BF16 && d->dtype != MMI_I8 && d->dtype != MMI_F8E4M3 && d->dtype != MMI_F4E2M1X2)
         return mmi_fail(MMI_ERR_UNSUPPORTED, "LM linear weights must be bf16, int8 or fp8 (e4m3fn): " + name);
     if (d->ndim != 2) return mmi_fail(MMI_ERR_SHAPE, "unexpected rank for " + name);
-    const int q8 = d->dtype == MMI_I8 ? 1 : (d->dtype == MMI_F8E4M3 ? 2 : 0);
+    const int q8 = d->dtype == MMI_I8 ? 1 : (d->dtype == MMI_F8E4M3 ? 2 : (d->dtype == MMI_F4E2M1X2 ? 4 : 0));
     if (lm->q8 >= 0 && lm->q8 != q8) return mmi_fail(MMI_ERR_UNSUPPORTED, "mixed bf16 / int8 / fp8 linear weights: " + name);
     lm->q8 = q8;
-    if (d->shape[0] != N || d->shape[1] != K) return mmi_fail(MMI_ERR_SHAPE, "shape mismatch for " + name);
+    if (q8 == 4 && K % 32 != 0) return mmi_fail(MMI_ERR_UNSUPPORTED, "MXFP4 linears need in_features to be a multiple of 32: " + name);
+    if (d->shape[0] != N || d->shape[1] != (q8 == 4 ? K / 2 : K)) return mmi_fail(MMI_ERR_SHAPE, "shape mismatch for " + name);
     if (K % 8 != 0) return mmi_fail(MMI_ERR_UNSUPPORTED, "in_features must be a multiple of 8: " + name);
     const int TN = tile ? tile : lm->T;
     g->T = TN;
@@ -232,7 +236,26 @@ int load_linear(mmi_lm* lm, const MmiWeights& W, const std::string& name, int N,
     const int rows_per_tile = gate_hidden > 0 ? TN / 2 : TN;
     g->NT = mmi_cdiv(g->N, rows_per_tile);
     const int ksteps = mmi_cdiv(K, mmi_kstep(TN));
-    if (!q8) {
+    if (q8 == 4) {
+        // `<linear>.weight_scale_e8m0`: one byte per 32 input features of a row (its values were checked by check_mxfp4_descs)
+        const std::string sname = name + "_scale_e8m0";
+        const mmi_tensor_desc* sc = W.find(sname);
+        if (!sc) return mmi_fail(MMI_ERR_MISSING_WEIGHT, "missing weight: " + sname);
+        if (sc->dtype != MMI_E8M0 || sc->ndim != 2 || sc->shape[0] != N || sc->shape[1] != K / 32)
+            return mmi_fail(MMI_ERR_SHAPE, "MXFP4 block scales must be e8m0 [out_features, in_features / 32]: " + sname);
+        g->wq = 4;
+        g->KSTEPS = mmi_cdiv(ksteps, 4);                       // entries of four k-steps
+        g->ksteps = ksteps;
+        const size_t n = (size_t)g->NT * g->KSTEPS * 1024, ns = (size_t)g->NT * g->KSTEPS * 64 * (TN == 32 ? 2 : 4);
+        uint8_t* p = reinterpret_cast<uint8_t*>(wp_dst);
+        if (!p) MMI_HIP_CHECK(lm->wts.alloc(&p, n));
+        g->wp = reinterpret_cast<u32x4*>(p);
+        g->s4 = s4_dst;
+        if (!g->s4) MMI_HIP_CHECK(lm->wts.alloc(&g->s4, ns));
+        g->bytes = n + ns;                                     // 0.5 B per weight + the scale bytes as the GEMM streams them
+        MMI_LAUNCH(k_pack_w_fp4, (int)mmi_cdiv64((int64_t)n, 256), 256, 0, (hipStream_t)0, (const uint8_t*)d->data, (const uint8_t*)sc->data,
+                   p, g->s4, N, K, TN, g->NT, g->KSTEPS, gate_hidden);
+    } else if (!q8) {
         g->KSTEPS = ksteps;
         size_t n = (size_t)g->NT * g->KSTEPS * 512;
         uint16_t* p = reinterpret_cast<uint16_t*>(wp_dst);
@@ -325,9 +348,12 @@ GemmPlan plan_gemm(const MmiKnobs& k, const GemmW& g, bool may_split) {
     p.ntw = 1;
     p.ksplit = 1;
     // few n-tiles (N = 4096 at the 32-row tile): split K over workgroups so that every CU streams weights
-    if (may_split && g.NT < 200 && g.KSTEPS >= 128) p.ksplit = g.NT <= 64 ? 4 : 2;
+    // (the thresholds count k-steps: an MXFP4 linear, whose KSTEPS are entries of four, is planned from the k-steps of its row -
+    // the split-K and wave plan of its bf16 twin, also where the row is no whole number of entries)
+    const int kst = g.wq == 4 ? g.ksteps : g.KSTEPS;
+    if (may_split && g.NT < 200 && kst >= 128) p.ksplit = g.NT <= 64 ? 4 : 2;
     if (k.gemm_ksplit && may_split && g.KSTEPS >= k.gemm_ksplit) p.ksplit = k.gemm_ksplit;      // test hook: force the split-K path
-    const int ks = g.KSTEPS / p.ksplit;
+    const int ks = kst / p.ksplit;
     p.waves = ks >= 32 ? 8 : 4;
     // fragments in flight per register buffer: 2 for the widest GEMM (the temporal FFN linear_in, 704 n-tiles: fewer
     // registers -> 3 workgroups per CU -> all 704 resident at once; 36.8 vs 39.3 us in the microbenchmark), else 4
@@ -369,8 +395,23 @@ int launch_gemm_q(hipStream_t s, dim3 groups, int waves, const GemmArgs& a) {
     return MMI_OK;
 }
 
+// MXFP4 entries (four k-steps each): two entries per register buffer at one batch tile, one at two (8 activation fragments per
+// entry there); no instantiation carries scratch (profiles/mxfp4/kernel_resources.csv)
+template <int TN, int MT, int NTW>
+int launch_gemm_f4(hipStream_t s, dim3 groups, int waves, const GemmArgs& a) {
+    constexpr int U = MT == 1 ? 2 : 1;
+    if constexpr (MT * NTW <= 2) {
+        if (waves == 8) MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 8, U, 4>), groups, 512, 0, s, a);
+        else MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 4, U, 4>), groups, 256, 0, s, a);
+        MMI_CHECK_LAUNCH();
+        return MMI_OK;
+    }
+    return mmi_fail(MMI_ERR_UNSUPPORTED, "MXFP4 linears run one n-tile and at most two batch tiles per workgroup");
+}
+
 template <int TN, int MT, int NTW>
 int launch_gemm_w(hipStream_t s, dim3 groups, int waves, int u, int wq, bool q8_u2, const GemmArgs& a) {
+    if (wq == 4) return launch_gemm_f4<TN, MT, NTW>(s, groups, waves, a);
     if (wq == 1) return launch_gemm_q<TN, MT, NTW, 1>(s, groups, waves, a);
     if (wq == 2) return launch_gemm_q<TN, MT, NTW, 2>(s, groups, waves, a);
     if (wq == 3) {
@@ -420,7 +461,7 @@ XldsPlan plan_xlds(const mmi_lm* lm, const GemmW& g, const GemmArgs& a, int mt) 
     XldsPlan p{false, 0, 0, 0, false};
     const MmiKnobs& k = lm->knobs;
     const char mode = k.gemm_lds ? k.gemm_lds : (g.wq == 0 ? '2' : '0');
-    if (mode == '0' || g.T != 32 || mt > 2) return p;
+    if (mode == '0' || g.T != 32 || mt > 2 || g.wq == 4) return p;   // (k_gemm_xlds has no MXFP4 form)
     if (a.epi != MMI_EPI_GATE && a.epi != MMI_EPI_ROPE_KV && a.epi != MMI_EPI_STORE) return p;   // no prefetched addend, no split-K
     int cus = 256;                                             // MI355X: 256 CUs
     const bool tg = k.gemm_lds_grid != MmiKnobs::UNSET;        // test hook: small grids / short chunks for the tiny shapes
@@ -552,7 +593,7 @@ int launch_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, GemmArgs a, bool is_d
         return MMI_OK;
     }
     a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT;
-    a.wscale = g.scale; a.wscb = g.scb; a.gate_rows = g.gate ? g.N : 0;
+    a.wscale = g.scale; a.wscb = g.scb; a.ws4 = g.s4; a.gate_rows = g.gate ? g.N : 0;
     a.wq = (g.wq == 1 && a.wq >= 3) ? a.wq : g.wq;             // int8 linears: 3 / 4 = int8 activations (set by the program builder)
     a.xinv = g.xinv;
     const int mt = mmi_cdiv(a.B, g.T);
@@ -600,6 +641,7 @@ bool act8_of(const mmi_lm* lm) { return lm->q8 == 1 && !lm->cfg.cross_attention 
 // carry k-step pairs, and the padding k-step reads as zero)
 int packed_ksteps_t(const mmi_lm* lm, int T, int features) {
     const int ks = mmi_cdiv(features, mmi_kstep(T));
+    if (lm->q8 == 4) return 4 * mmi_cdiv(ks, 4);       // MXFP4 entries carry four k-steps
     return lm->q8 >= 1 ? 2 * mmi_cdiv(ks, 2) : ks;
 }
 int packed_ksteps(const mmi_lm* lm, int features) { return packed_ksteps_t(lm, lm->T, features); }
@@ -733,6 +775,11 @@ int launch_norm_fused(hipStream_t s, int T, int mt, int wq, int NT, bool tiles_o
         else if (T == 32 && tiles_over_grid) MMI_LAUNCH((k_gemm_q8<32, 1, 8, 4, true>), dim3(NT, mt), 512, 0, s, a);
         else if (T == 32) MMI_LAUNCH((k_gemm_q8<32, 2, 8, 4, true>), NT, 512, 0, s, a);
         else MMI_LAUNCH((k_gemm_q8<16, 1, 8, 4, true>), NT, 512, 0, s, a);
+    } else if (wq == 4) {      // rows of <= 16 entries: two per wave
+        if (T == 32 && mt == 1) MMI_LAUNCH((k_gemm_xp_norm<32, 1, 8, 2, 4>), NT, 512, 0, s, a);
+        else if (T == 32) MMI_LAUNCH((k_gemm_xp_norm<32, 2, 8, 2, 4>), NT, 512, 0, s, a);
+        else if (mt == 1) MMI_LAUNCH((k_gemm_xp_norm<16, 1, 8, 2, 4>), NT, 512, 0, s, a);
+        else MMI_LAUNCH((k_gemm_xp_norm<16, 2, 8, 2, 4>), NT, 512, 0, s, a);
     } else if (wq == 2) {
         if (T == 32 && mt == 1) MMI_LAUNCH((k_gemm_xp_norm<32, 1, 8, 4, 2>), NT, 512, 0, s, a);
         else if (T == 32) MMI_LAUNCH((k_gemm_xp_norm<32, 2, 8, 4, 2>), NT, 512, 0, s, a);
@@ -779,6 +826,9 @@ static int q8_fused_osplit(const MmiKnobs& k, const GemmW& g, int epi, int T) {
     return os;
 }
 
+// longest row (in weight entries) of the norm-fused GEMM: 8 waves x 8 k-steps
+static int norm_fused_max(int wq) { return wq == 4 ? 16 : (wq ? 32 : 64); }
+
 // RMSNorm(x) * alpha fused into the GEMM (k_gemm_xp_norm) when a workgroup's 8 waves can hold the whole row slice in
 // registers (rows of <= 1024 features at the 32-wide tile: the depth transformer); otherwise norm kernel + GEMM.
 // lm->act8: the normalised row is quantised inside the GEMM (k_gemm_q8, fused) or by the norm launch
@@ -786,7 +836,7 @@ void add_norm_gemm(mmi_lm* lm, const GemmW& g, uint16_t* x, const uint16_t* alph
                    int out_features, bool out_packed, int epi, const DepKv* kv = nullptr) {
     const bool a8 = lm->act8 && g.wq == 1;
     const int wq = a8 ? 3 : g.wq;
-    const bool fuse = g.KSTEPS <= (wq ? 32 : 64) && !lm->knobs.no_norm_fusion && mmi_cdiv(lm->batch, g.T) <= 2;   // k_gemm_rows has no fused norm
+    const bool fuse = g.KSTEPS <= norm_fused_max(wq) && !lm->knobs.no_norm_fusion && mmi_cdiv(lm->batch, g.T) <= 2;   // k_gemm_rows has no fused norm
     if (!fuse) {
         if (a8) {
             add_resid_rmsnorm(lm, x, Pending{}, alpha, xn_scratch, D, lm->dxnq, lm->sx_dxn, g.T);
@@ -807,7 +857,7 @@ void add_norm_gemm(mmi_lm* lm, const GemmW& g, uint16_t* x, const uint16_t* alph
     a.out_ksteps = packed_ksteps_t(lm, g.T, out_features);
     a.alpha = alpha; a.D = D; a.eps = 1e-8f;
     a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT;
-    a.wscale = g.scale; a.wscb = g.scb; a.gate_rows = g.gate ? g.N : 0;
+    a.wscale = g.scale; a.wscb = g.scb; a.ws4 = g.s4; a.gate_rows = g.gate ? g.N : 0;
     a.wq = wq; a.xinv = g.xinv;
     a.osplit = 1;
     const int T = g.T, mt = mmi_cdiv(lm->batch, g.T), NT = g.NT * (a.osplit > 1 ? a.osplit : 1);
@@ -1374,6 +1424,44 @@ extern "C" int mmi_lm_create(const mmi_lm_cfg* cfg, const mmi_tensor_desc* weigh
 static int lm_create_rows(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ext, const mmi_tensor_desc* weights, int32_t n_weights,
                           int32_t max_batch, mmi_lm** out);
 
+// MXFP4 linears (`weight` MMI_F4E2M1X2 + `weight_scale_e8m0` MMI_E8M0): everything that can be refused is refused here, from the
+// descriptors and the scale bytes, before anything is allocated or packed.  The scale range 2..252 keeps every dequantised weight
+// a normal, finite bf16 (0.5 * 2^(2-127) = 2^-126 is the smallest normal; 6 * 2^(253-127) would overflow), which is what makes the
+// conversion exact (mmi_fp4.h).
+static int check_mxfp4_descs(const mmi_lm_cfg& c, bool low_rank_or_demux, const mmi_tensor_desc* weights, int32_t n_weights) {
+    MmiWeights W{weights, n_weights};
+    bool any = false;
+    for (int i = 0; i < n_weights; ++i) any = any || weights[i].dtype == MMI_F4E2M1X2;
+    if (!any) return MMI_OK;
+    if (c.cross_attention) return mmi_fail(MMI_ERR_UNSUPPORTED, "cross-attention layers with quantised linears are not supported");
+    if (low_rank_or_demux) return mmi_fail(MMI_ERR_UNSUPPORTED, "quantised linears with low-rank or demuxed embeddings are not supported");
+    std::vector<uint8_t> host;
+    for (int i = 0; i < n_weights; ++i) {
+        const mmi_tensor_desc& d = weights[i];
+        const std::string name = d.name ? d.name : "";
+        if (d.dtype == MMI_I8 || d.dtype == MMI_F8E4M3) return mmi_fail(MMI_ERR_UNSUPPORTED, "mixed bf16 / int8 / fp8 linear weights: " + name);
+        if (d.dtype != MMI_F4E2M1X2) continue;
+        if (d.ndim != 2) return mmi_fail(MMI_ERR_SHAPE, "unexpected rank for " + name);
+        const int64_t N = d.shape[0], K = 2 * d.shape[1];
+        if (K % 32 != 0) return mmi_fail(MMI_ERR_UNSUPPORTED, "MXFP4 linears need in_features to be a multiple of 32: " + name);
+        const std::string sname = name + "_scale_e8m0";
+        const mmi_tensor_desc* sc = W.find(sname);
+        if (!sc) return mmi_fail(MMI_ERR_MISSING_WEIGHT, "missing weight: " + sname);
+        if (sc->dtype != MMI_E8M0 || sc->ndim != 2 || sc->shape[0] != N || sc->shape[1] != K / 32)
+            return mmi_fail(MMI_ERR_SHAPE, "MXFP4 block scales must be e8m0 [out_features, in_features / 32]: " + sname);
+        host.resize((size_t)(N * (K / 32)));
+        if (host.empty()) continue;
+        MMI_HIP_CHECK(hipMemcpy(host.data(), sc->data, host.size(), hipMemcpyDeviceToHost));
+        for (uint8_t b : host) {
+            if (b == 255) return mmi_fail(MMI_ERR_INVALID, "MXFP4 block scale 255 is the E8M0 NaN: " + sname);
+            if (b < 2 || b > 252)
+                return mmi_fail(MMI_ERR_UNSUPPORTED, "MXFP4 block scales must be 2..252 (2^-125..2^125: every weight a normal, finite bf16), found " +
+                                                         std::to_string((int)b) + ": " + sname);
+        }
+    }
+    return MMI_OK;
+}
+
 extern "C" int mmi_lm_create_ext(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ext, const mmi_tensor_desc* weights, int32_t n_weights,
                                  int32_t max_batch, mmi_lm** out) {
     if (max_batch > 64)
@@ -1429,6 +1517,11 @@ static int lm_create_rows(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ext, cons
         for (int i = 0; i < n_weights; ++i)   // settles it - before a byte of the model is uploaded and packed
             if (weights[i].ndim == 2 && (weights[i].dtype == MMI_I8 || weights[i].dtype == MMI_F8E4M3))
                 return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_create_rows: int8 / fp8 linears are not supported above 64 model rows (k_gemm_rows is bf16)");
+    if (max_batch > 64)
+        for (int i = 0; i < n_weights; ++i)
+            if (weights[i].dtype == MMI_F4E2M1X2)
+                return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_create_rows: MXFP4 linears are not supported above 64 model rows (k_gemm_rows is bf16)");
+    if ((rc = check_mxfp4_descs(norm_cfg, low_rank != 0 || demux, weights, n_weights))) return rc;
     mmi_lm* lm = new mmi_lm();
     lm->knobs = knobs;
     lm->wts.poison = lm->st.poison = knobs.debug_poison;
@@ -1521,14 +1614,18 @@ static int lm_create_rows(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ext, cons
         // depformer_in[k] all read transformer_out, so they are packed back to back and run as ONE GEMM with
         // dep_q * depformer_dim output features ahead of the micro-step loop (build_program).  Needs whole n-tiles per step.
         const bool group = c.dep_q > 0 && dd % lm->T == 0 && !knobs.no_dep_in_group;
-        uint8_t* wp_all = nullptr;
+        uint8_t *wp_all = nullptr, *s4_all = nullptr;
         float *scale_all = nullptr, *scb_all = nullptr;
-        size_t per = 0;
+        size_t per = 0, per4 = 0;
         if (group) {
             const int NT = dd / lm->T, ksteps = mmi_cdiv(d, mmi_kstep(lm->T));
-            per = lm->q8 >= 1 ? (size_t)NT * mmi_cdiv(ksteps, 2) * 1024 : (size_t)NT * ksteps * 512 * sizeof(uint16_t);
+            per = lm->q8 == 4 ? (size_t)NT * mmi_cdiv(ksteps, 4) * 1024
+                  : lm->q8 >= 1 ? (size_t)NT * mmi_cdiv(ksteps, 2) * 1024 : (size_t)NT * ksteps * 512 * sizeof(uint16_t);
+            per4 = lm->q8 == 4 ? (size_t)NT * mmi_cdiv(ksteps, 4) * 64 * (lm->T == 32 ? 2 : 4) : 0;
             if (lm->wts.alloc(&wp_all, per * nw) != hipSuccess) return fail(mmi_fail(MMI_ERR_HIP, "out of device memory (depformer_in)"));
-            if (lm->q8 >= 1 && lm->wts.alloc(&scale_all, (size_t)dd * nw) != hipSuccess)
+            if (per4 && lm->wts.alloc(&s4_all, per4 * nw) != hipSuccess)
+                return fail(mmi_fail(MMI_ERR_HIP, "out of device memory (depformer_in scales)"));
+            if (lm->q8 >= 1 && lm->q8 != 4 && lm->wts.alloc(&scale_all, (size_t)dd * nw) != hipSuccess)
                 return fail(mmi_fail(MMI_ERR_HIP, "out of device memory (depformer_in scales)"));
             if (lm->q8 == 1 && lm->wts.alloc(&scb_all, (size_t)dd * nw) != hipSuccess)
                 return fail(mmi_fail(MMI_ERR_HIP, "out of device memory (depformer_in scales)"));
@@ -1536,7 +1633,7 @@ static int lm_create_rows(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ext, cons
         for (int k = 0; k < nw; ++k) {
             if ((rc = load_linear(lm, W, "depformer_in." + std::to_string(k) + ".weight", dd, d, 0, &lm->dep_in[k],
                                   group ? wp_all + per * k : nullptr, scale_all ? scale_all + (size_t)dd * k : nullptr,
-                                  scb_all ? scb_all + (size_t)dd * k : nullptr)))
+                                  scb_all ? scb_all + (size_t)dd * k : nullptr, 0, s4_all ? s4_all + per4 * k : nullptr)))
                 return fail(rc);
         }
         for (int k = 1; group && k < nw; ++k)
@@ -2468,10 +2565,10 @@ extern "C" int mmi_lm_debug_linear(mmi_lm* lm, const char* weight_name, const ch
         if (rc) return done(rc);
     } else if (path == MMI_DBG_NORM_FUSED) {
         const int wq = (a8 && g.wq == 1) ? 3 : g.wq;
-        if (g.KSTEPS > (wq ? 32 : 64)) return done(mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_linear: the row is too long for the norm-fused GEMM"));
+        if (g.KSTEPS > norm_fused_max(wq)) return done(mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_linear: the row is too long for the norm-fused GEMM"));
         a.xp = reinterpret_cast<const u32x4*>(xp);
         a.alpha = alpha; a.D = K; a.eps = 1e-8f;
-        a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT; a.wscale = g.scale; a.wscb = g.scb; a.gate_rows = gated ? g.N : 0;
+        a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT; a.wscale = g.scale; a.wscb = g.scb; a.ws4 = g.s4; a.gate_rows = gated ? g.N : 0;
         a.wq = wq; a.xinv = g.xinv; a.osplit = 1;
         rc = launch_norm_fused(s, T, mt, wq, g.NT, !lm->knobs.q8_tiles_serial, a);
         if (rc) return done(rc);
@@ -2579,12 +2676,14 @@ extern "C" int mmi_lm_profile_end(mmi_lm* lm, double* mean_ms, int64_t* n_launch
     if (bytes_per_launch) {
         const mmi_lm_cfg& c = lm->cfg;
         // algorithmic bytes of one FFN linear_in launch: packed weights + activations in + gated activations out
-        const int64_t wbytes = lm->q8 >= 1 ? (int64_t)2 * c.ffn_hidden * c.dim + (int64_t)2 * c.ffn_hidden * 4 : (int64_t)2 * c.ffn_hidden * c.dim * 2;
+        const int64_t wbytes = lm->q8 == 4 ? (int64_t)2 * c.ffn_hidden * c.dim / 2 + (int64_t)2 * c.ffn_hidden * c.dim / 16
+                               : lm->q8 >= 1 ? (int64_t)2 * c.ffn_hidden * c.dim + (int64_t)2 * c.ffn_hidden * 4 : (int64_t)2 * c.ffn_hidden * c.dim * 2;
         *bytes_per_launch = wbytes + (int64_t)lm->batch * c.dim * 2 + (int64_t)lm->batch * c.ffn_hidden * 2;
     }
     if (kernel_name)
         *kernel_name = lm->act8      ? "k_gemm_xp<32, MT, 1, 8, 2, 3> (temporal FFN linear_in, int8 weights x int8 activations on v_mfma_i32_32x32x32_i8 + SiLU gate)"
                        : lm->q8 == 1 ? "k_gemm_xp<32, 1, 1, 8, 2, 1> (temporal FFN linear_in, int8 weights + SiLU gate)"
+                       : lm->q8 == 4 ? "k_gemm_xp<32, MT, 1, 8, U, 4> (temporal FFN linear_in, MXFP4 weights widened to bf16 + SiLU gate)"
                        : lm->q8 == 2 ? "k_gemm_xp<32, 1, 1, 8, 2, 2> (temporal FFN linear_in, fp8 weights on the fp8 MFMA + SiLU gate)"
                        : lm->dominant_xlds ? (lm->batch > 32 ? "k_gemm_xlds<2, 32, 3, true, 0> (temporal FFN linear_in + SiLU gate)"
                                                              : "k_gemm_xlds<1, 64, 3, true, 0> (temporal FFN linear_in + SiLU gate)")

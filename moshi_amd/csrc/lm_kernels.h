@@ -15,6 +15,7 @@
 //   token ring      [B][17][max_delay+2] int32 (lm.py:605-613).
 #pragma once
 #include "mmi_common.h"
+#include "mmi_fp4.h"
 
 // ------------------------------------------------------------------------------------------------
 // fragment-packed layouts
@@ -98,6 +99,49 @@ __global__ void k_pack_w_i8(const int8_t* __restrict__ W, int8_t* __restrict__ P
     int8_t v = 0;
     if (valid && k < K) v = W[row * K + k];
     P[idx] = v;
+}
+
+// MXFP4 weights (OCP Microscaling: `weight` = E2M1 codes, two per byte [N][K / 2]; `weight_scale_e8m0` = one E8M0 byte per 32
+// input features [N][K / 32]; mmi_fp4.h).  Same tile order again with FOUR k-steps per 16-byte lane entry: Wq[nt][ke][lane][16],
+// word j of the entry = the lane's eight codes of k-step 4ke + j (zero padded to whole entries).  The scale bytes travel in
+// the same order, Sq[nt][ke][lane][SB], one byte per MX block the lane's entry touches: SB = 2 at the 32-row tile (a k-step
+// is 16 features: words 0, 1 share byte 0, words 2, 3 byte 1), SB = 4 at the 16-row tile (a k-step is one block).  The lanes of
+// one row hold the same bytes: a lane fetches its entry's scales with one 2- or 4-byte load next to the 16-byte entry.
+// Padding carries scale byte 127 (2^0) over zero codes.  One thread per code byte.
+__global__ void k_pack_w_fp4(const uint8_t* __restrict__ W, const uint8_t* __restrict__ S, uint8_t* __restrict__ P,
+                             uint8_t* __restrict__ PS, int N, int K, int TN, int NT, int KE, int gate_hidden) {
+    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long total = (long)NT * KE * 1024;
+    if (idx >= total) return;
+    int e = (int)(idx & 15);
+    int lane = (int)((idx >> 4) & 63);
+    long rest = idx >> 10;
+    int ke = (int)(rest % KE);
+    int nt = (int)(rest / KE);
+    int i, kq, kstep;
+    if (TN == 32) { i = lane & 31; kq = lane >> 5; kstep = 16; } else { i = lane & 15; kq = lane >> 4; kstep = 32; }
+    int k = (4 * ke + (e >> 2)) * kstep + 8 * kq + 2 * (e & 3);      // the byte's low-nibble element; k + 1 sits in the high nibble
+    long row;
+    bool valid;
+    if (gate_hidden > 0) {
+        int half = TN / 2;
+        int r = nt * half + (i < half ? i : i - half);
+        valid = r < gate_hidden;
+        row = (i < half ? 0 : gate_hidden) + r;
+    } else {
+        row = (long)nt * TN + i;
+        valid = row < N;
+    }
+    uint8_t v = 0;
+    if (valid && k < K) v = W[row * (K / 2) + (k >> 1)];
+    P[idx] = v;
+    const int SB = TN == 32 ? 2 : 4;
+    if (e < SB) {
+        const int blk = TN == 32 ? 2 * ke + e : 4 * ke + e;           // MX block (32 features) of the row
+        uint8_t sc = 127;
+        if (valid && blk * 32 < K) sc = S[row * (K / 32) + blk];
+        PS[((rest * 64) + lane) * SB + e] = sc;
+    }
 }
 
 // 16 int8 -> two bf16 fragments (k-step 2kp, k-step 2kp+1)
@@ -198,7 +242,9 @@ struct GemmArgs {
     const float* wscb;      // int8 weights: the raw row absmax SCB (`weight_scb`), read by the int8 x int8 dequantisation
                             // out32 * (SCA[b] * SCB[n]) * (1 / 127^2) - the oracle's restatement of bitsandbytes' int8_mm_dequant, in its order
     float xinv;             // fp8: 1 / input_scale, applied to the activations before the e4m3 conversion
-    int wq;                 // host side only: 0 bf16, 1 int8 (widened to bf16), 2 fp8 (fp8 MFMA) weights, 3 int8 weights x int8 activations
+    int wq;                 // host side only: 0 bf16, 1 int8 (widened to bf16), 2 fp8 (fp8 MFMA) weights, 3 int8 weights x int8 activations,
+                            // 4 MXFP4 (widened to bf16)
+    const uint8_t* ws4;     // MXFP4 weights: the E8M0 scale bytes in entry order [NT][KSTEPS][64][TN == 32 ? 2 : 4] (k_pack_w_fp4); else null
     const float* sx;        // WQ = 3 with pre-quantised activations: xp holds int8 entries Xq[mt][kp][lane][16] (k_quant_rows_i8 / the
                             // norm kernel) and sx[b] the row absmax they were scaled by (bitsandbytes' SCA); the epilogue multiplies
                             // the int32 sum by SCA[b] / 127 * SCB[n] / 127.  k_gemm_q8: written here for the epilogue (LDS)
@@ -494,10 +540,19 @@ __device__ __forceinline__ void mmi_gemm_epilogue(const GemmArgs& a, float (&acc
     }
 }
 
+// MXFP4: the scale bytes of one weight entry as the lane loads them, and the byte that scales word j (k-step 4ke + j) of it
+template <int TN> struct MmiFp4Scale { typedef uint16_t type; };
+template <> struct MmiFp4Scale<16> { typedef uint32_t type; };
+template <int TN>
+__device__ __forceinline__ uint32_t mmi_fp4_scale_of(uint32_t s, int j) { return TN == 32 ? (s >> (8 * (j >> 1))) & 0xffu : (s >> (8 * j)) & 0xffu; }
+
 // WQ = 1 (int8) / 2 (fp8) weights: one 16-byte weight entry carries two k-steps, so the loop runs over k-step PAIRS
 // (a.KSTEPS then counts pairs; the activation buffers hold 2*KSTEPS k-steps, zero padded).
 // WQ = 3: int8 weight entries x int8 activation entries (a.xp = Xq, one 16-byte entry per weight entry, a.sx = row absmax) on
 // v_mfma_i32_{32x32x32,16x16x64}_i8; the int32 sums are converted to fp32 once per wave and go through the common epilogue.
+// WQ = 4 (MXFP4): one 16-byte weight entry carries FOUR k-steps (a.KSTEPS counts entries; the activation buffers hold
+// 4*KSTEPS k-steps, zero padded): the WQ = 1 loop with four activation fragments per entry.  Each word of the entry is widened
+// to one bf16 fragment under its MX block's scale (mmi_fp4x8_to_bf16: 4 conversions, exact) and meets the bf16 MFMA.
 // The 16-row tile (<= 16 sessions) with bf16 weights is held to 128 registers: two 8-wave workgroups per CU, so that one's
 // reduction + epilogue runs under the other's weight stream (136 registers unbounded; 8 spill, outside the loop).  Same-box at
 // 1 / 8 / 16 sessions: -0.12 / -0.14 / -0.12 ms per step (in_proj 20.9 -> 19.4 us, linear_in 38.4 -> 35.5, text head 48.9 ->
@@ -506,7 +561,8 @@ template <int TN, int MT, int NTW, int WAVES, int U, int WQ = 0>
 __global__ __launch_bounds__(WAVES * 64, (TN == 16 && MT == 1 && NTW == 1 && WQ == 0 && WAVES == 8) ? 4 : 1) void k_gemm_xp(GemmArgs a) {
     constexpr bool W8 = WQ == 1;
     constexpr int R = TN == 32 ? 16 : 4;          // accumulator registers per MFMA tile
-    constexpr int XS = (WQ == 1 || WQ == 2) ? 2 : 1;   // activation fragments per weight entry
+    constexpr int XS = WQ == 4 ? 4 : ((WQ == 1 || WQ == 2) ? 2 : 1);   // activation fragments per weight entry
+    typedef typename MmiFp4Scale<TN>::type s4_t;      // WQ = 4: the scale bytes of one entry (2 at the 32-row tile, 4 at the 16-row tile)
     typedef int iacc_t __attribute__((ext_vector_type(R)));
     typedef float acc_t __attribute__((ext_vector_type(R)));
     const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
@@ -543,10 +599,19 @@ __global__ __launch_bounds__(WAVES * 64, (TN == 16 && MT == 1 && NTW == 1 && WQ 
 #pragma unroll
             for (int r = 0; r < R; ++r) acc[t][m][r] = 0.f;
 
+    const s4_t* sp[NTW];
+    if constexpr (WQ == 4) {
+#pragma unroll
+        for (int t = 0; t < NTW; ++t) sp[t] = reinterpret_cast<const s4_t*>(a.ws4) + ((long)min(nt0 + t, a.NT - 1) * a.KSTEPS + ks0) * 64 + wlane;
+    }
     u32x4 wA[U][NTW], xA[U][MT][XS], wB[U][NTW], xB[U][MT][XS];
-#define MMI_G_LOAD(W_, X_, base)                                                              \
+    uint32_t sA[U][NTW], sB[U][NTW];                  // WQ = 4 only
+#define MMI_G_LOAD(W_, X_, S_, base)                                                          \
     _Pragma("unroll") for (int u = 0; u < U; ++u) {                                           \
         _Pragma("unroll") for (int t = 0; t < NTW; ++t) W_[u][t] = mmi_load_nt(wp[t] + ((base) + u) * 64); \
+        if constexpr (WQ == 4) {                                                              \
+            _Pragma("unroll") for (int t = 0; t < NTW; ++t) S_[u][t] = sp[t][((base) + u) * 64]; \
+        }                                                                                     \
         _Pragma("unroll") for (int m = 0; m < MT; ++m)                                        \
             _Pragma("unroll") for (int x = 0; x < XS; ++x) X_[u][m][x] = xp[m][(((base) + u) * XS + x) * 64]; \
     }
@@ -571,9 +636,15 @@ __global__ __launch_bounds__(WAVES * 64, (TN == 16 && MT == 1 && NTW == 1 && WQ 
             }                                                                                 \
         }                                                                                     \
     }
-#define MMI_G_MMA1(W_, X_, u)                                                                 \
+#define MMI_G_MMA1(W_, X_, S_, u)                                                             \
         if constexpr (WQ == 2) MMI_G_MMA8(W_, X_, u)                                          \
-        else if constexpr (WQ == 3) {                                                       \
+        else if constexpr (WQ == 4) {   /* (j & (XS - 1)) == j here: the mask only keeps this branch well-formed where XS < 4 */ \
+            _Pragma("unroll") for (int t = 0; t < NTW; ++t)                                   \
+                _Pragma("unroll") for (int j = 0; j < 4; ++j) {                               \
+                    const u32x4 wf_ = mmi_fp4x8_to_bf16(W_[u][t][j], mmi_fp4_scale_of<TN>(S_[u][t], j)); \
+                    _Pragma("unroll") for (int m = 0; m < MT; ++m) { MMI_G_MFMA(wf_, X_[u][m][j & (XS - 1)], acc[t][m]) } \
+                }                                                                             \
+        } else if constexpr (WQ == 3) {                                                       \
             _Pragma("unroll") for (int t = 0; t < NTW; ++t)                                   \
                 _Pragma("unroll") for (int m = 0; m < MT; ++m) {                              \
                     if constexpr (TN == 32) acc[t][m] = __builtin_bit_cast(acc_t, mmi_mfma_i8_32x32x32(W_[u][t], X_[u][m][0], __builtin_bit_cast(iacc_t, acc[t][m]))); \
@@ -593,26 +664,26 @@ __global__ __launch_bounds__(WAVES * 64, (TN == 16 && MT == 1 && NTW == 1 && WQ 
             }                                                                                 \
         }                                                                                     \
         }
-#define MMI_G_MMA(W_, X_)                                                                     \
-    _Pragma("unroll") for (int u = 0; u < U; ++u) MMI_G_MMA1(W_, X_, u)
+#define MMI_G_MMA(W_, X_, S_)                                                                 \
+    _Pragma("unroll") for (int u = 0; u < U; ++u) MMI_G_MMA1(W_, X_, S_, u)
     const int nfull = nks / U;
     if (nfull > 0) {
         // steady state has no conditional loads, so that the compiler's s_waitcnt vmcnt(N) before each MFMA only waits
         // for the older buffer and the loads of the next group stay in flight behind it
-        MMI_G_LOAD(wA, xA, 0);
+        MMI_G_LOAD(wA, xA, sA, 0);
         int g = 0;
         for (; g + 2 < nfull; g += 2) {
-            MMI_G_LOAD(wB, xB, (g + 1) * U);
-            MMI_G_MMA(wA, xA);
-            MMI_G_LOAD(wA, xA, (g + 2) * U);
-            MMI_G_MMA(wB, xB);
+            MMI_G_LOAD(wB, xB, sB, (g + 1) * U);
+            MMI_G_MMA(wA, xA, sA);
+            MMI_G_LOAD(wA, xA, sA, (g + 2) * U);
+            MMI_G_MMA(wB, xB, sB);
         }
         if (nfull - g == 2) {
-            MMI_G_LOAD(wB, xB, (g + 1) * U);
-            MMI_G_MMA(wA, xA);
-            MMI_G_MMA(wB, xB);
+            MMI_G_LOAD(wB, xB, sB, (g + 1) * U);
+            MMI_G_MMA(wA, xA, sA);
+            MMI_G_MMA(wB, xB, sB);
         } else {
-            MMI_G_MMA(wA, xA);
+            MMI_G_MMA(wA, xA, sA);
         }
     }
     // remainder of the slice (fewer than U entries): requested together - one memory round trip, not one per entry - from
@@ -624,6 +695,10 @@ __global__ __launch_bounds__(WAVES * 64, (TN == 16 && MT == 1 && NTW == 1 && WQ 
             const int ks = nfull * U + min(u, rem - 1);
 #pragma unroll
             for (int t = 0; t < NTW; ++t) wA[u][t] = mmi_load_nt(wp[t] + ks * 64);
+            if constexpr (WQ == 4) {
+#pragma unroll
+                for (int t = 0; t < NTW; ++t) sA[u][t] = sp[t][ks * 64];
+            }
 #pragma unroll
             for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -631,7 +706,7 @@ __global__ __launch_bounds__(WAVES * 64, (TN == 16 && MT == 1 && NTW == 1 && WQ 
         }
 #pragma unroll
         for (int u = 0; u < U - 1; ++u)
-            if (u < rem) { MMI_G_MMA1(wA, xA, u) }
+            if (u < rem) { MMI_G_MMA1(wA, xA, sA, u) }
     }
 #undef MMI_G_LOAD
 #undef MMI_G_MMA
@@ -822,13 +897,15 @@ __global__ __launch_bounds__(256, 2) void k_gemm_rows(GemmArgs a) {
 // everything in flight at once, these GEMMs are latency bound - the waves combine their sums of squares through
 // LDS, normalise their own fragments in registers and only then run the MFMAs.  No split-K over workgroups here.
 // WQ = 1 / 2: int8 / fp8 weights, a.KSTEPS counts k-step pairs (see k_gemm_xp); KMAX = weight entries per wave.
+// WQ = 4: MXFP4 weights, a.KSTEPS counts entries of four k-steps.
 template <int TN, int MT, int WAVES, int KMAX, int WQ = 0>
 __global__ __launch_bounds__(WAVES * 64, (TN == 16 && KMAX == 4 && WQ == 0) ? 4 : 1) void k_gemm_xp_norm(GemmArgs a) {   // 16-row tile, short rows: two workgroups per CU
     constexpr bool W8 = WQ == 1;
     constexpr int R = TN == 32 ? 16 : 4;
     constexpr int KS = TN == 32 ? 16 : 32;
-    constexpr int XS = WQ ? 2 : 1;
+    constexpr int XS = WQ == 4 ? 4 : (WQ ? 2 : 1);
     constexpr int XMAX = KMAX * XS;                           // activation fragments per wave
+    typedef typename MmiFp4Scale<TN>::type s4_t;
     typedef float acc_t __attribute__((ext_vector_type(R)));
     const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
     const int nt0 = (int)blockIdx.x;                          // one n-tile per workgroup (octet sharing of these GEMMs measured
@@ -839,6 +916,7 @@ __global__ __launch_bounds__(WAVES * 64, (TN == 16 && KMAX == 4 && WQ == 0) ? 4 
     const int kq = TN == 32 ? (lane >> 5) : (lane >> 4);
 
     u32x4 wv[KMAX], xv[MT][XMAX], al[XMAX];
+    uint32_t sv[KMAX];                                        // WQ = 4: the entries' scale bytes
     const u32x4 zero = {0u, 0u, 0u, 0u};
     // every load is unconditional from a clamped (valid) address and masked afterwards: conditional loads would be
     // serialised behind s_waitcnt vmcnt(0) by the compiler, and these GEMMs live on having the whole slice in flight
@@ -848,6 +926,7 @@ __global__ __launch_bounds__(WAVES * 64, (TN == 16 && KMAX == 4 && WQ == 0) ? 4 
     for (int u = 0; u < KMAX; ++u) {
         const int uu = min(u, nks > 0 ? nks - 1 : 0);
         wv[u] = mmi_load_nt(a.wp + ((long)min(nt0, a.NT - 1) * a.KSTEPS + ksl + uu) * 64 + wlane);
+        if constexpr (WQ == 4) sv[u] = reinterpret_cast<const s4_t*>(a.ws4)[((long)min(nt0, a.NT - 1) * a.KSTEPS + ksl + uu) * 64 + wlane];
 #pragma unroll
         for (int x = 0; x < XS; ++x) {
             const int k = ((ksl + uu) * XS + x) * KS + 8 * kq;
@@ -903,7 +982,10 @@ __global__ __launch_bounds__(WAVES * 64, (TN == 16 && KMAX == 4 && WQ == 0) ? 4 
     for (int u = 0; u < KMAX; ++u) {
         u32x4 wf[XS];
         if constexpr (W8) mmi_i8x16_to_bf16(wv[u], wf[0], wf[XS - 1]);
-        else wf[0] = wv[u];
+        else if constexpr (WQ == 4) {       // (a masked entry is zero codes: zero under any scale)
+#pragma unroll
+            for (int x = 0; x < XS; ++x) wf[x] = mmi_fp4x8_to_bf16(wv[u][x], mmi_fp4_scale_of<TN>(sv[u], x));
+        } else wf[0] = wv[u];
         const u32x2 w8f[2] = {{wv[u][0], wv[u][1]}, {wv[u][2], wv[u][3]}};   // fp8: the two k-steps of the entry
 #pragma unroll
         for (int x = 0; x < XS; ++x) {

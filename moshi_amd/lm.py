@@ -117,7 +117,9 @@ class LMModel:
             rows per guided session.  `lm.max_batch` then reports it.  Not together with `max_batch > 64`.
         quantize: True converts the linears to row-wise int8 (`weight` + `weight_scb`), like the reference's `quantize=True`;
             "fp8" converts them to e4m3fn (`weight` + `weight_scale`) for the fp8 MFMA path (BASELINE configs[4]);
-            a state dict that already carries int8 / fp8 weights is used as is.
+            "mxfp4" converts them to OCP MXFP4 (`weight` uint8 code pairs + `weight_scale_e8m0`; weight-only, widened to bf16 in
+            the GEMM - exactly the bf16 engine on `dequantize_lm_state_dict_mxfp4`); in_features must be multiples of 32;
+            a state dict that already carries int8 / fp8 / MXFP4 weights is used as is.
     """
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], config: Optional[LMConfig] = None,
@@ -142,13 +144,16 @@ class LMModel:
             lib = _capi.load()
         self._lib = lib
         self._handle = C.c_void_p()
-        from .weights import normalize_lm_state_dict, quantize_lm_state_dict, quantize_lm_state_dict_fp8
+        from .weights import (is_mxfp4_state_dict, normalize_lm_state_dict, quantize_lm_state_dict, quantize_lm_state_dict_fp8,
+                              quantize_lm_state_dict_mxfp4)
         state_dict = normalize_lm_state_dict(state_dict, self.config)     # fused multi-step projections of released checkpoints
         if quantize == "fp8":
             state_dict = quantize_lm_state_dict_fp8(state_dict)
+        elif quantize == "mxfp4":
+            state_dict = quantize_lm_state_dict_mxfp4(state_dict)
         elif quantize:                                                    # the reference's `quantize=True` (lm.py:242-243)
             state_dict = quantize_lm_state_dict(state_dict)
-        self.quantized = any(v.dtype in (torch.int8, torch.float8_e4m3fn) for v in state_dict.values())
+        self.quantized = any(v.dtype in (torch.int8, torch.float8_e4m3fn) for v in state_dict.values()) or is_mxfp4_state_dict(state_dict)
         if self.quantized and getattr(config, "cross_attention", False):
             # the engine runs one weight format per model (activation buffers are laid out for it) and keeps cross-attention
             # linears bf16: fail here, with the reason, instead of inside mmi_lm_create
@@ -160,7 +165,7 @@ class LMModel:
                                       "load the bf16 checkpoint (quantize=False)")
 
         def place(k, v):     # quantised weights and their fp32 scales keep their dtype (utils/quantize.py:29-34); the rest is bf16
-            if v.dtype in (torch.int8, torch.float8_e4m3fn):
+            if v.dtype in (torch.int8, torch.float8_e4m3fn, torch.uint8):
                 return v.detach().to(self.device)
             scale = k.endswith("_scb") or k.endswith(".weight_scale") or k.endswith(".input_scale")
             return v.detach().to(device=self.device, dtype=torch.float32 if scale else torch.bfloat16)

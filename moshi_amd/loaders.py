@@ -154,7 +154,8 @@ def get_moshi_lm(filename: str | Path | None, lm_kwargs: Optional[Dict[str, Any]
                  lm_kwargs_overrides: Optional[dict] = None, max_batch: int = 32, lib=None, state_patch=None,
                  quantize: Optional[bool | str] = None, max_rows: Optional[int] = None) -> LMModel:
     """loaders.get_moshi_lm (loaders.py:366-446): bf16 weights; `quantize` in the config (a `.q8` checkpoint carrying int8
-    `weight` + `weight_scb`, or fp8 `weight` + `weight_scale`) is taken from the tensors themselves.  `max_rows`: a handle of
+    `weight` + `weight_scb`, fp8 `weight` + `weight_scale`, or MXFP4 `weight` + `weight_scale_e8m0`) is taken from the tensors
+    themselves; `quantize="mxfp4"` converts a bf16 checkpoint at load.  `max_rows`: a handle of
     up to 128 model rows instead of `max_batch` sessions (LMModel)."""
     assert dtype == torch.bfloat16, "the engine computes the LM in bf16 (fp32 accumulation), like the reference's default"
     kw = dict(lm_kwargs) if lm_kwargs is not None else None
@@ -194,7 +195,8 @@ def get_moshi_lm(filename: str | Path | None, lm_kwargs: Optional[Dict[str, Any]
         state = fuse_lora_state_dict(normalize_lm_state_dict(state, cfg), _load_state(lora_weights), float(lora_scaling))
     if state_patch is not None:
         state_patch(state)
-    already = any(v.dtype in (torch.int8, torch.float8_e4m3fn) for v in state.values())
+    from .weights import is_mxfp4_state_dict
+    already = any(v.dtype in (torch.int8, torch.float8_e4m3fn) for v in state.values()) or is_mxfp4_state_dict(state)
     return LMModel(state, cfg, device=device, max_batch=max_batch, lib=lib, quantize=False if already else quantize, fuser=fuser,
                    max_rows=max_rows)
 
@@ -208,10 +210,12 @@ def lm_size_kwargs(slots: int, rows_per_session: int = 1) -> Dict[str, int]:
 def export_quantized(src: str | Path, dst: str | Path, fmt: str = "int8", lm_kwargs: Optional[dict] = None) -> Dict[str, int]:
     """scripts/export_quantized.py:38-64 without the hub: read a bf16 Moshi checkpoint, convert the linears
     (`replace_linear_with_qlinear`: temporal + depth transformers, depformer_in, linears, text_linear) to the reference's int8
-    storage (`weight` int8 + `weight_scb`) or to fp8 (`weight` e4m3fn + `weight_scale`), and write a safetensors file."""
+    storage (`weight` int8 + `weight_scb`), to fp8 (`weight` e4m3fn + `weight_scale`) or to OCP MXFP4 (`weight` uint8 code
+    pairs + `weight_scale_e8m0`), and write a safetensors file."""
     from safetensors.torch import save_file
 
-    from .weights import normalize_lm_state_dict, quantize_lm_state_dict, quantize_lm_state_dict_fp8
+    from .weights import (is_lm_linear_weight, normalize_lm_state_dict, quantize_lm_state_dict, quantize_lm_state_dict_fp8,
+                          quantize_lm_state_dict_mxfp4)
     state = _load_state(src, ("fsdp_best_state", "model"))
     # released checkpoints fuse the per-step attention projections (`self_attn.in_proj_weight`): split them first, as the
     # reference's load hook does before `replace_linear_with_qlinear` sees the modules (transformer.py:422-446)
@@ -233,10 +237,14 @@ def export_quantized(src: str | Path, dst: str | Path, fmt: str = "int8", lm_kwa
         out = quantize_lm_state_dict(state)
     elif fmt == "fp8":
         out = quantize_lm_state_dict_fp8(state)
+    elif fmt == "mxfp4":
+        out = quantize_lm_state_dict_mxfp4(state)
     else:
-        raise ValueError("fmt must be 'int8' or 'fp8'")
+        raise ValueError("fmt must be 'int8', 'fp8' or 'mxfp4'")
     save_file({k: v.contiguous() for k, v in out.items()}, str(dst))
-    return {"tensors": len(out), "quantized": sum(v.dtype in (torch.int8, torch.float8_e4m3fn) for v in out.values()),
+    return {"tensors": len(out),
+            "quantized": sum(v.dtype in (torch.int8, torch.float8_e4m3fn) or (v.dtype == torch.uint8 and is_lm_linear_weight(k))
+                             for k, v in out.items()),
             "bytes": sum(v.numel() * v.element_size() for v in out.values())}
 
 

@@ -298,6 +298,87 @@ def quantize_lm_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tenso
 
 
 # --------------------------------------------------------------------------------------------------------------------
+# MXFP4 weights (OCP Microscaling Formats v1.0: E2M1 elements under one shared E8M0 scale per block of 32)
+# --------------------------------------------------------------------------------------------------------------------
+MXFP4_BLOCK = 32
+MXFP4_SCALE_SUFFIX = "_scale_e8m0"                      # `<linear>.weight_scale_e8m0` next to `<linear>.weight`
+MXFP4_SCALE_MIN, MXFP4_SCALE_MAX = 2, 252               # the scale bytes the engine admits: every weight a normal, finite bf16
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # magnitude of code bits 2..0; bit 3 is the sign
+
+
+def is_mxfp4_state_dict(sd: Dict[str, torch.Tensor]) -> bool:
+    return any(k.endswith(".weight" + MXFP4_SCALE_SUFFIX) for k in sd)
+
+
+def quantize_mxfp4(w: torch.Tensor):
+    """[out, in] -> (codes uint8 [out, in / 2], scales uint8 [out, in / 32]) by the OCP rule: per block of 32 input features
+    the shared scale is 2^(floor(log2(absmax)) - 2) (2 = emax of E2M1), the elements are v / scale rounded to the nearest E2M1
+    value, ties to the even code, saturating at +-6; an all-zero block gets scale byte 127 and zero codes.  Two codes per byte,
+    element 2i in the low nibble.  The scale byte is clamped to the engine's 2..252 (never reached by bf16 checkpoint weights)."""
+    if w.dim() != 2 or w.shape[1] % MXFP4_BLOCK:
+        raise ValueError(f"MXFP4 needs [out, in] with in_features a multiple of {MXFP4_BLOCK}, got {tuple(w.shape)}")
+    n, k = w.shape
+    wf = w.detach().to(torch.float32).reshape(n, k // MXFP4_BLOCK, MXFP4_BLOCK)
+    absmax = wf.abs().amax(dim=2)
+    _, ex = torch.frexp(absmax)                          # absmax = m * 2^ex, m in [0.5, 1): floor(log2(absmax)) = ex - 1
+    sbyte = (ex.to(torch.int32) - 1 - 2 + 127).clamp_(MXFP4_SCALE_MIN, MXFP4_SCALE_MAX)
+    sbyte = torch.where(absmax > 0, sbyte, torch.full_like(sbyte, 127))
+    inv = ((254 - sbyte) << 23).view(torch.float32)      # 2^-(s - 127), exact
+    a = wf.abs() * inv[:, :, None]                       # exact: a power-of-two factor
+    # midpoints of neighbouring E2M1 values; a tie goes to the even code (the upper one where the lower code is odd)
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75).to(torch.uint8) + (a > 1.25).to(torch.uint8) + (a >= 1.75).to(torch.uint8)
+            + (a > 2.5).to(torch.uint8) + (a >= 3.5).to(torch.uint8) + (a > 5.0).to(torch.uint8))
+    code = (code | (torch.signbit(wf).to(torch.uint8) << 3)).reshape(n, k)
+    packed = code[:, 0::2] | (code[:, 1::2] << 4)
+    return packed.contiguous(), sbyte.to(torch.uint8).contiguous()
+
+
+def dequantize_mxfp4(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """(codes [out, in / 2], scales [out, in / 32]) -> bf16 [out, in]; exact for scale bytes 2..252 (one mantissa bit times a
+    power of two is a bf16 value)."""
+    n, k = codes.shape[0], codes.shape[1] * 2
+    if tuple(scales.shape) != (n, k // MXFP4_BLOCK) or k % MXFP4_BLOCK:
+        raise ValueError(f"MXFP4 scales must be [out, in / 32]: codes {tuple(codes.shape)}, scales {tuple(scales.shape)}")
+    c = torch.stack([codes & 15, codes >> 4], dim=2).reshape(n, k).to(torch.int64)
+    lut = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32, device=codes.device)
+    scale = (scales.to(torch.int32) << 23).view(torch.float32)      # 2^(s - 127), exact
+    out = lut[c].reshape(n, k // MXFP4_BLOCK, MXFP4_BLOCK) * scale[:, :, None]
+    return out.reshape(n, k).to(torch.bfloat16)
+
+
+def quantize_lm_state_dict_mxfp4(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """MXFP4 linears (the same set as `quantize_lm_state_dict`): `weight` = uint8 code pairs [out, in / 2],
+    `<key>_scale_e8m0` = uint8 block scales [out, in / 32].  W ~= dequantize_lm_state_dict_mxfp4(...)[key], exactly what the
+    engine multiplies by."""
+    out: Dict[str, torch.Tensor] = {}
+    for key, w in sd.items():
+        if key.endswith(".weight" + MXFP4_SCALE_SUFFIX):
+            out[key] = w
+            continue
+        if not is_lm_linear_weight(key) or (w.dtype == torch.uint8 and key + MXFP4_SCALE_SUFFIX in sd):
+            out[key] = w
+            continue
+        try:
+            out[key], out[key + MXFP4_SCALE_SUFFIX] = quantize_mxfp4(w)
+        except ValueError as e:
+            raise ValueError(f"{key}: {e}") from None
+    return out
+
+
+def dequantize_lm_state_dict_mxfp4(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """The bf16 state dict an MXFP4 one stands for (exact): what the bf16 engine and the bf16 oracle are fed for parity."""
+    out: Dict[str, torch.Tensor] = {}
+    for key, w in sd.items():
+        if key.endswith(".weight" + MXFP4_SCALE_SUFFIX):
+            continue
+        if key + MXFP4_SCALE_SUFFIX in sd:
+            out[key] = dequantize_mxfp4(w, sd[key + MXFP4_SCALE_SUFFIX])
+        else:
+            out[key] = w
+    return out
+
+
+# --------------------------------------------------------------------------------------------------------------------
 # LoRA adapters (modules/lora.py): merged into the base weights at load
 # --------------------------------------------------------------------------------------------------------------------
 def fuse_lora_state_dict(sd: Dict[str, torch.Tensor], lora_sd: Dict[str, torch.Tensor], scaling: float) -> Dict[str, torch.Tensor]:
