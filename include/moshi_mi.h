@@ -384,6 +384,37 @@ int mmi_lm_cross_capacity(const mmi_lm* lm);
  * cross-attention layers MMI_ERR_INVALID; cross_len outside [1, capacity] MMI_ERR_SHAPE. */
 int mmi_lm_set_row_condition(mmi_lm* lm, int32_t session, const mmi_row_condition* c, mmi_stream stream);
 
+/* ---- per-session LoRA adapters, unmerged, on one base model (modules/lora.py; loaders.py:486-516) ------------------------------
+ * The reference runs a LoRA fine-tune either merged (fuse_lora=True: W' = W + scaling * B A, what a caller gets by merging before
+ * mmi_lm_create) or unmerged: frozen_W(x) + lora_B(lora_A(x)) * scaling (lora.py:116-118).  An adapter handle keeps up to
+ * max_adapters adapters of rank <= max_rank NEXT TO one base model and runs every model row with the adapter of its session:
+ *   t = bf16(A x)   (a shrink launch in front of every linear: lora_A's bf16 output)
+ *   out = epilogue(W x + bf16(scaling * B) t)   (one fp32 accumulator inside the linear's own GEMM)
+ * Adapted: every nn.Linear the reference wraps - the four linears of every temporal and depth-transformer layer, depformer_in.{k},
+ * text_linear, linears.{k}.
+ *
+ * mmi_lm_enable_adapters: before streaming_start (like mmi_lm_enable_tts_machine); allocates the zeroed banks.  max_adapters 1..8,
+ * max_rank 32 / 64 / 96 / 128; (0, 0) turns adapters off again and frees the banks.  MMI_ERR_UNSUPPORTED, with the reason: quantised
+ * linears of any width, more than 64 model rows, cross-attention layers, extra heads, low-rank or demuxed embeddings (the
+ * reference wraps their linears too), the depth transformer on its own tile (MMI_DEP_TILE), a handle that is streaming.  A handle that never calls it is unchanged: same launch list, same bits, same mmi_lm_state_bytes. */
+int mmi_lm_enable_adapters(mmi_lm* lm, int32_t max_adapters, int32_t max_rank);
+/* Adapter `slot` = the bf16 DEVICE tensors `<linear>.lora_A.weight` [r, in] and `<linear>.lora_B.weight` [out, r] (names as the
+ * engine's own weights, un-fused per step; `<linear>.frozen_W.weight` entries are ignored).  Checked before anything is written
+ * (MMI_ERR_INVALID): r a multiple of 8 and <= max_rank, shapes fit the base linear, every A has its B, no unknown keys
+ * (loaders.py:508-511), every value finite - scaling * lora_B in bf16 included.  A linear the adapter does not mention keeps
+ * zero columns.  bf16(scaling * B) is formed here, exact for the reference's default scaling 2 and any power of two.  Allowed
+ * while streaming, ordered on `stream` (which it synchronises once, for the check); MMI_ERR_STATE while a live session runs on
+ * the slot. */
+int mmi_lm_load_adapter(mmi_lm* lm, int32_t slot, float scaling, const mmi_tensor_desc* tensors, int32_t n_tensors, mmi_stream stream);
+/* Zeroes the slot, under the same rule. */
+int mmi_lm_unload_adapter(mmi_lm* lm, int32_t slot, mmi_stream stream);
+/* Session `session` (both model rows of a guided one) runs on adapter `slot` (-1 = none) from the next step on.  Stream ordered;
+ * the launch list and a captured step graph stay as they are.  streaming_start sets every session to -1; mmi_lm_reset leaves the
+ * slot alone, an exec mask does not apply; mmi_lm_state_save / load carry the table. */
+int mmi_lm_set_row_adapter(mmi_lm* lm, int32_t session, int32_t slot_or_minus1, mmi_stream stream);
+/* The session's slot; -1: none (also without adapters, outside a stream or for a session outside the batch). */
+int32_t mmi_lm_row_adapter(const mmi_lm* lm, int32_t session);
+
 /* The TTS script machine on the device: what TTSModel.generate's three host hooks do on every frame
  * (models/tts.py:553-583) - StateMachine.process per row (tts.py:160-252), the zeroed / prefixed audio codebooks, the padding
  * bonus - as part of the launch list, so that a TTS step stays one captured graph.  The fields are StateMachine's and
@@ -520,6 +551,14 @@ enum { MMI_DBG_PLAIN = 0, MMI_DBG_SPLITK = 1, MMI_DBG_FUSED = 2, MMI_DBG_NORM = 
 int mmi_lm_debug_linear(mmi_lm* lm, const char* weight_name, const char* alpha_name_or_null, int32_t path, const void* x_bf16,
                         int32_t rows, void* out_bf16, int8_t* codes_or_null, float* absmax_or_null, void* norm_out_or_null,
                         mmi_stream stream);
+
+/* mmi_lm_debug_linear on an adapter handle (mmi_lm_enable_adapters): the shrink launch plus the GEMM of that linear as the step
+ * runs them, for rows whose adapter slots are row_slots[rows] (HOST int32, -1 = no adapter).  Paths MMI_DBG_PLAIN and
+ * MMI_DBG_SPLITK (an adapter handle takes no fused form); out = bf16(W x + bf16(scaling * B) bf16(A x)) through the linear's
+ * usual epilogue. */
+int mmi_lm_debug_linear_lora(mmi_lm* lm, const char* weight_name, const char* alpha_name_or_null, int32_t path, const void* x_bf16,
+                             int32_t rows, void* out_bf16, int8_t* codes_or_null, float* absmax_or_null, void* norm_out_or_null,
+                             const int32_t* row_slots, mmi_stream stream);
 
 /* The launch list of one frame step, recorded while the step ran for the first time: one line "site<TAB>kernel[<TAB>weight bytes]" per kernel
  * launch in launch order (sites: "L.in_proj", "L.ffn_in", "dep.out_proj", "text_linear", ...).  scripts/rocpd_sites.py joins
@@ -668,6 +707,12 @@ typedef struct mmi_batcher_condition mmi_batcher_condition;
  * would refuse is refused here with the same status, and no slot is claimed. */
 int mmi_batcher_open_cond(mmi_batcher* b, const mmi_row_sampling* settings_or_null, const mmi_batcher_condition* cond_or_null,
                           int64_t* channel_id);
+/* mmi_batcher_open_cond for a channel that runs on adapter slot `adapter_slot` (-1 = none) of an adapter handle
+ * (mmi_lm_enable_adapters before mmi_batcher_create): the slot's row gets it with the slot's reset, before the row's first step,
+ * and keeps it for the channel's life; mmi_batcher_close returns the row to -1.  A slot mmi_lm_set_row_adapter would refuse is
+ * refused here with the same status, and no slot is claimed. */
+int mmi_batcher_open_lora(mmi_batcher* b, const mmi_row_sampling* settings_or_null, const mmi_batcher_condition* cond_or_null,
+                          int32_t adapter_slot, int64_t* channel_id);
 int mmi_batcher_close(mmi_batcher* b, int64_t channel_id);
 /* Append 24 kHz mono PCM (host f32) to the channel's FIFO (batched_asr.rs:77-90 extend_data). */
 int mmi_batcher_push_pcm(mmi_batcher* b, int64_t channel_id, const float* pcm, int32_t n_samples);

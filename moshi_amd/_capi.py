@@ -203,6 +203,13 @@ SIGNATURES = {
     "mmi_batcher_pop": (C.c_int, [_P, C.c_int64, _P, _P, C.POINTER(C.c_int32)]),
     "mmi_batcher_get_stats": (C.c_int, [_P, C.POINTER(BatcherStats)]),
     "mmi_lm_debug_linear": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    "mmi_lm_debug_linear_lora": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, C.POINTER(C.c_int32), _P]),
+    "mmi_lm_enable_adapters": (C.c_int, [_P, C.c_int32, C.c_int32]),
+    "mmi_lm_load_adapter": (C.c_int, [_P, C.c_int32, C.c_float, C.POINTER(TensorDesc), C.c_int32, _P]),
+    "mmi_lm_unload_adapter": (C.c_int, [_P, C.c_int32, _P]),
+    "mmi_lm_set_row_adapter": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
+    "mmi_lm_row_adapter": (C.c_int32, [_P, C.c_int32]),
+    "mmi_batcher_open_lora": (C.c_int, [_P, C.POINTER(RowSampling), C.POINTER(BatcherCondition), C.c_int32, C.POINTER(C.c_int64)]),
     "mmi_lm_launch_list": (C.c_int64, [_P, _P, C.c_int64]),
     "mmi_mimi_launch_list": (C.c_int64, [_P, C.c_int32, _P, C.c_int64]),
     "mmi_lm_seek": (C.c_int, [_P, _P, _P]),
@@ -218,10 +225,13 @@ _SINCE_ROW_SAMPLING = ("mmi_row_sampling_check", "mmi_lm_set_row_sampling", "mmi
 _SINCE_ROW_CONDITION = ("mmi_lm_set_cross_capacity", "mmi_lm_cross_capacity", "mmi_lm_set_row_condition", "mmi_batcher_open_cond")
 _SINCE_TTS_MACHINE = ("mmi_lm_enable_tts_machine", "mmi_lm_set_row_script", "mmi_lm_row_script_status")
 _SINCE_MANY_ROWS = ("mmi_lm_create_rows",)
+_SINCE_ADAPTERS = ("mmi_lm_debug_linear_lora", "mmi_lm_enable_adapters", "mmi_lm_load_adapter", "mmi_lm_unload_adapter",
+                   "mmi_lm_set_row_adapter", "mmi_lm_row_adapter", "mmi_batcher_open_lora")
 
 
 def _missing(name, path):
-    what = ("handles above 64 model rows" if name in _SINCE_MANY_ROWS else
+    what = ("per-session adapters" if name in _SINCE_ADAPTERS else
+            "handles above 64 model rows" if name in _SINCE_MANY_ROWS else
             "the TTS script machine" if name in _SINCE_TTS_MACHINE else
             "per-session conditions" if name in _SINCE_ROW_CONDITION else "per-session sampling")
 
@@ -237,7 +247,7 @@ class Lib:
         self.path = Path(path)
         self.cdll = C.CDLL(str(self.path))
         for name, (res, args) in SIGNATURES.items():
-            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION + _SINCE_TTS_MACHINE + _SINCE_MANY_ROWS and not hasattr(self.cdll, name):
+            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION + _SINCE_TTS_MACHINE + _SINCE_MANY_ROWS + _SINCE_ADAPTERS and not hasattr(self.cdll, name):
                 # an older build of the engine (MMI_LIB_PATH, A/B runs against a parent build): everything else works, these refuse
                 setattr(self, name, _missing(name, self.path))
                 continue

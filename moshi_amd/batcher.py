@@ -104,14 +104,18 @@ class SessionBatcher:
         self.close_all()
 
     # ---- channels ------------------------------------------------------------------------------------
-    def open(self, sampling=None, condition=None) -> int:
+    def open(self, sampling=None, condition=None, adapter: Optional[int] = None) -> int:
         """Claim a slot.  `sampling`: a `moshi_amd.SessionSampling` - the channel samples with its own settings and its own seeded
         draw stream (the same tokens whichever slot it lands in); None = the batcher's settings.  `condition`: a
         `moshi_amd.SessionCondition` - the channel's own condition tensors (fused like the batcher's; two rows when the batcher
         runs guided; a `cross` source of up to the model's `cross_capacity` positions) and guidance coefficient; None = the
-        batcher's own condition for that slot.  What the engine refuses raises here and claims no slot."""
+        batcher's own condition for that slot.  `adapter`: the slot of `LMModel(adapters=...)` the channel runs on for its life
+        (`close` returns the row to the base model); None = no adapter.  What the engine refuses raises here and claims no slot."""
         ch = C.c_int64(0)
-        if sampling is None and condition is None:
+        if adapter is not None and condition is None:
+            sp = C.byref(sampling.to_c()) if sampling is not None else None
+            self._lib.check(self._lib.mmi_batcher_open_lora(self._handle, sp, None, int(adapter), C.byref(ch)))
+        elif sampling is None and condition is None:
             self._lib.check(self._lib.mmi_batcher_open(self._handle, C.byref(ch)))
         elif condition is None:
             self._lib.check(self._lib.mmi_batcher_open_with(self._handle, C.byref(sampling.to_c()), C.byref(ch)))
@@ -138,7 +142,10 @@ class SessionBatcher:
                     bc.condition_cross = host(cx)
                     bc.cross_len = int(cx.shape[1])
             sp = C.byref(sampling.to_c()) if sampling is not None else None
-            self._lib.check(self._lib.mmi_batcher_open_cond(self._handle, sp, C.byref(bc), C.byref(ch)))
+            if adapter is not None:
+                self._lib.check(self._lib.mmi_batcher_open_lora(self._handle, sp, C.byref(bc), int(adapter), C.byref(ch)))
+            else:
+                self._lib.check(self._lib.mmi_batcher_open_cond(self._handle, sp, C.byref(bc), C.byref(ch)))
         return int(ch.value)
 
     def close(self, channel: int) -> None:

@@ -32,6 +32,7 @@ struct Channel {                 // batched_asr.rs:61-69
     float coef = 1.f;
     int cross_len = 0;
     std::vector<uint16_t> cond_sum, cond_cross;   // bf16 [R][dim] / [R][cross_len][dim], copied at open; empty = keep
+    int adapter = -1;            // mmi_batcher_open_lora: the row runs on this adapter slot for the channel's life
     long frames = 0;             // input frames consumed
     std::deque<float> in;        // PCM FIFO
     std::deque<OutFrame> out;
@@ -120,6 +121,7 @@ struct mmi_batcher {
     struct CondPlan { int what; float coef; bool sum, cross; int len; bool prev; };   // prev: the slot's last owner had one too   // what: 0 nothing, 1 the channel's own, 2 cfg.guidance's again
     std::vector<CondPlan> cond_plan;
     std::vector<uint8_t> row_has_cond;   // the slot's rows currently hold a channel's own condition
+    std::vector<int> row_adapter, adapter_plan;   // the adapter slot each row holds / takes at this step (-2: stays as it is)
     int64_t next_id = 1;
     mmi_batcher_stats stats;
 };
@@ -214,6 +216,8 @@ int create_impl(mmi_batcher* b) {
     b->cond_slot = (size_t)b->R * b->dim * (1 + (size_t)b->cross_cap);
     b->cond_plan.assign(B, mmi_batcher::CondPlan{0, 1.f, false, false, 0, false});
     b->row_has_cond.assign(B, 0);
+    b->row_adapter.assign(B, -1);
+    b->adapter_plan.assign(B, -2);
     if (b->has_sum || b->has_cross) {
         const size_t bytes = (size_t)B * b->cond_slot * sizeof(uint16_t), D = (size_t)b->dim;
         MMI_HIP_CHECK(hipHostMalloc((void**)&b->h_cond, bytes, 0));
@@ -269,10 +273,22 @@ extern "C" int mmi_batcher_open_with(mmi_batcher* b, const mmi_row_sampling* set
     return mmi_batcher_open_cond(b, settings, nullptr, channel_id);
 }
 
+int mmi_lm_adapter_slots(const mmi_lm* lm);      // lm_engine.hip: max_adapters of an adapter handle, else 0
+
 extern "C" int mmi_batcher_open_cond(mmi_batcher* b, const mmi_row_sampling* settings, const mmi_batcher_condition* cond, int64_t* channel_id) {
+    return mmi_batcher_open_lora(b, settings, cond, -1, channel_id);
+}
+
+extern "C" int mmi_batcher_open_lora(mmi_batcher* b, const mmi_row_sampling* settings, const mmi_batcher_condition* cond, int32_t adapter_slot,
+                                     int64_t* channel_id) {
     MmiDeviceGuard dev_guard_(b ? mmi_lm_device(b->lm) : -1);
     if (!b || !channel_id) return mmi_fail(MMI_ERR_INVALID, "null argument");
     int rc;
+    if (adapter_slot != -1) {     // what mmi_lm_set_row_adapter would refuse at the step, refused now
+        const int S = mmi_lm_adapter_slots(b->lm);
+        if (!S) return mmi_fail(MMI_ERR_STATE, "adapters are not enabled on a live stream (mmi_lm_enable_adapters before mmi_batcher_create)");
+        if (adapter_slot < -1 || adapter_slot >= S) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_set_row_adapter: slot must be -1 (none) or in [0, max_adapters)");
+    }
     if (settings && (rc = mmi_row_sampling_check(settings))) return rc;
     if (cond) {     // what mmi_lm_set_row_condition would refuse at the step, refused now: no slot is claimed
         if (!std::isfinite(cond->cfg_coef)) return mmi_fail(MMI_ERR_INVALID, "cfg_coef must be finite");
@@ -290,6 +306,7 @@ extern "C" int mmi_batcher_open_cond(mmi_batcher* b, const mmi_row_sampling* set
         c.live = true;
         c.pending_reset = true;
         if (settings) { c.own_sampling = true; c.sampling = *settings; }
+        c.adapter = adapter_slot;
         if (cond) {
             c.own_cond = true;
             c.coef = cond->cfg_coef;
@@ -341,7 +358,7 @@ extern "C" int mmi_batcher_step(mmi_batcher* b, int32_t* n_active) {
     const int B = b->B, F = b->F;
     Staging& h = b->host;
     Staging& d = b->dev;
-    int active = 0, resets = 0, firsts = 0, sets = 0;
+    int active = 0, resets = 0, firsts = 0, sets = 0, adapts = 0;
     {   // ---- pre_process (batched_asr.rs:279-374)
         std::lock_guard<std::mutex> g(b->mu);
         for (int r = 0; r < B; ++r) {
@@ -349,6 +366,11 @@ extern "C" int mmi_batcher_step(mmi_batcher* b, int32_t* n_active) {
             h.exec[r] = h.first[r] = h.reset[r] = 0;
             b->row_owner[r] = c.live ? c.id : 0;
             float* dst = h.pcm + (size_t)r * F;
+            {   // the row's adapter follows its channel: the owner's for the channel's life, none once it is closed
+                const int want = c.live ? c.adapter : -1;
+                b->adapter_plan[r] = want != b->row_adapter[r] ? want : -2;
+                if (b->adapter_plan[r] != -2) ++adapts;
+            }
             if (c.live && c.pending_reset) {
                 h.reset[r] = 1;
                 c.pending_reset = false;
@@ -385,11 +407,16 @@ extern "C" int mmi_batcher_step(mmi_batcher* b, int32_t* n_active) {
         }
     }
     if (n_active) *n_active = active;
-    if (active == 0 && resets == 0) return MMI_OK;
+    if (active == 0 && resets == 0 && adapts == 0) return MMI_OK;
     hipStream_t s = b->stream;
     int rc;
     MMI_HIP_CHECK(hipEventRecord(b->ev_begin, s));
     MMI_HIP_CHECK(hipMemcpyAsync(d.up, h.up, h.h2d_bytes, hipMemcpyHostToDevice, s));
+    for (int r = 0; adapts && r < B; ++r) {      // the mirror follows the engine: a failed step leaves the change to be made again
+        if (b->adapter_plan[r] == -2) continue;
+        if ((rc = mmi_lm_set_row_adapter(b->lm, r, b->adapter_plan[r], s))) return rc;
+        b->row_adapter[r] = b->adapter_plan[r];
+    }
     if (resets) {   // handle_chat: mimi.reset_streaming(); lm_gen.reset_streaming() (server.py:163-164), for the new rows only
         if ((rc = mmi_mimi_reset(b->mimi, d.reset, s))) return rc;
         if ((rc = mmi_lm_reset(b->lm, d.reset, s))) return rc;

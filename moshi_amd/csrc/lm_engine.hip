@@ -41,6 +41,11 @@ struct DepLayerW {
 
 struct EvPair { hipEvent_t a, b; };
 
+// The adapter bank of one linear (mmi_lm_enable_adapters): a = packed A_all [S * R][K] (a weight of S * R output rows at the
+// linear's tile), b = packed bf16(scaling * B_all) [N][S * R] (a weight of S * R input features, gate / value rows interleaved
+// like the linear's own); slot j owns rows / columns [j * R, (j + 1) * R), zero where nothing is loaded
+struct LoraBank { u32x4* a = nullptr; u32x4* b = nullptr; };
+
 }  // namespace
 
 struct mmi_lm {
@@ -164,6 +169,16 @@ struct mmi_lm {
     std::vector<hipEvent_t> tts_stage_ev;     // behind the copy out of a session's staging row; waited for before it is reused
     std::vector<uint8_t> tts_stage_used;
     bool tts_rule_done = false;     // this (hooked) step has applied the audio rule in front of on_audio_tokens: the commit does not
+    // per-row LoRA adapters, unmerged (modules/lora.py): the banks belong to the handle, the slot table to the stream
+    bool lora_on = false;
+    int lora_S = 0, lora_R = 0;     // max_adapters, max_rank
+    MmiArena lora_mem;
+    std::map<const void*, LoraBank> lora_by_wp;       // by the packed weight (GemmW::wp) of the linear
+    std::map<std::string, const void*> lora_by_name;  // `<linear>.weight` -> that key
+    int* lora_bad = nullptr;        // device flag of mmi_lm_load_adapter's finiteness check
+    int* row_slot = nullptr;        // [gen_batch] adapter slot per session, -1 = none (streaming-state arena: snapshots carry it)
+    std::vector<int> row_slot_h;    // the host's mirror (a slot is not reloaded while a live row selects it)
+    uint16_t* lora_t = nullptr;     // packed t = bf16(A x) of the linear in flight (adapters need Td == T: one tile, one buffer)
     long offset_cpu = 0;
     int attn_ns = 1;                                // workgroups per (session, head) of the decode attention (attn_splits)
     long depth_bound = 0;                           // no session's offset exceeds this (steps since streaming_start / the last seek; resets
@@ -451,6 +466,26 @@ int launch_gemm_t(hipStream_t s, const GemmPlan& p, int NT, int mt, bool q8_u2, 
     return mmi_fail(MMI_ERR_UNSUPPORTED, "batch too large for the skinny GEMM");
 }
 
+// Adapter handles (mmi_lm_enable_adapters): the LORA forms of k_gemm_xp - bf16, one n-tile per workgroup, at most two batch
+// tiles - under launch_gemm_w's choice of waves and fragments in flight
+template <int TN, int MT>
+int launch_gemm_lora(hipStream_t s, dim3 groups, int waves, int u, const GemmArgs& a) {
+    if (waves == 8 && u == 2 && MT == 1) {
+        if constexpr (MT == 1) MMI_LAUNCH((k_gemm_xp<TN, MT, 1, 8, 2, 0, true>), groups, 512, 0, s, a);
+    } else if (waves == 8) MMI_LAUNCH((k_gemm_xp<TN, MT, 1, 8, 4, 0, true>), groups, 512, 0, s, a);
+    else if (waves == 4) MMI_LAUNCH((k_gemm_xp<TN, MT, 1, 4, 4, 0, true>), groups, 256, 0, s, a);
+    else return mmi_fail(MMI_ERR_UNSUPPORTED, "unsupported waves per GEMM workgroup");
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+template <int TN, int MT>
+int launch_lora_shrink_t(hipStream_t s, dim3 groups, int waves, const GemmArgs& a) {
+    if (waves == 8) MMI_LAUNCH((k_gemm_xp<TN, MT, 1, 8, 4, 0, false, true>), groups, 512, 0, s, a);
+    else MMI_LAUNCH((k_gemm_xp<TN, MT, 1, 4, 4, 0, false, true>), groups, 256, 0, s, a);
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+
 // k_gemm_xlds (activations resident in LDS, one workgroup per CU): which GEMMs take it, and how.  knobs.gemm_lds: '2' = with
 // the staggered tail (each tile's epilogue under the last chunk's weight stream; the DEFAULT for bf16 weights at the 32-row
 // tile: same-box A/B of the default benchmark 8.10 / 8.12 ms against 8.17 / 8.20 ms with k_gemm_xp, dominant kernel 38.6
@@ -582,7 +617,33 @@ GemmArgs rows_group_view(const GemmArgs& a_in, int r0, int rows) {
     return a;
 }
 
-int launch_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, GemmArgs a, bool is_dominant) {
+// The shrink launch in front of an adapted linear g: t = bf16(A_all x) for the columns of each row's own slot (MMI_EPI_LORA_T),
+// packed as the operand of g's tail.  An ordinary k_gemm_xp launch of S * R / T n-tiles over the linear's K: the waves of a
+// workgroup split K as for any GEMM, and with 4..32 n-tiles the row octets of a tile are shared out (plan_osplit)
+int launch_lora_shrink(mmi_lm* lm, hipStream_t s, const GemmW& g, const u32x4* xp, int B, const int* row_slot, int tok_rows, uint16_t* t) {
+    auto it = lm->lora_by_wp.find(g.wp);
+    if (it == lm->lora_by_wp.end()) return mmi_fail(MMI_ERR_STATE, "adapter handle: a linear without a bank");
+    const int SR = lm->lora_S * lm->lora_R, mt = mmi_cdiv(B, g.T);
+    GemmW ga;
+    ga.wp = it->second.a; ga.N = SR; ga.K = g.K; ga.NT = SR / g.T; ga.KSTEPS = g.KSTEPS; ga.T = g.T;
+    ga.bytes = (size_t)ga.NT * ga.KSTEPS * 1024;
+    GemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.wp = ga.wp; a.xp = xp; a.out = t; a.B = B; a.N = SR; a.KSTEPS = ga.KSTEPS; a.NT = ga.NT;
+    a.out_mode = MMI_OUT_PACKED; a.out_ld = SR; a.out_ksteps = SR / mmi_kstep(g.T);
+    a.epi = MMI_EPI_LORA_T; a.row_slot = row_slot; a.tok_rows = tok_rows; a.lora_rank = lm->lora_R;
+    const GemmPlan p = plan_gemm(lm->knobs, ga, false);
+    a.osplit = plan_osplit(lm->knobs, ga, p, a.epi, g.T);
+    const dim3 groups(ga.NT * (a.osplit > 1 ? a.osplit : 1), 1);
+    mmi_record_bytes((long)ga.bytes);
+    if (mt == 1) return g.T == 32 ? launch_lora_shrink_t<32, 1>(s, groups, p.waves, a) : launch_lora_shrink_t<16, 1>(s, groups, p.waves, a);
+    if (mt == 2) return g.T == 32 ? launch_lora_shrink_t<32, 2>(s, groups, p.waves, a) : launch_lora_shrink_t<16, 2>(s, groups, p.waves, a);
+    return mmi_fail(MMI_ERR_UNSUPPORTED, "adapters run at most two batch tiles per linear");
+}
+
+// lora_t (adapter handles): the packed t of the shrink launch in front of this linear - the linear runs the LORA form of k_gemm_xp.
+// An explicit argument, not a member of `a`: the lora_* members share their bytes with others (GemmArgs)
+int launch_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, GemmArgs a, bool is_dominant, const u32x4* lora_t = nullptr) {
     if (lm->knobs.rows_groups && a.B > 64 && g.T == 32 && g.wq == 0 && rows_groups_ok(a)) {
         GemmArgs full = a;
         full.KSTEPS = g.KSTEPS;
@@ -593,7 +654,8 @@ int launch_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, GemmArgs a, bool is_d
         return MMI_OK;
     }
     a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT;
-    a.wscale = g.scale; a.wscb = g.scb; a.ws4 = g.s4; a.gate_rows = g.gate ? g.N : 0;
+    a.wscale = g.scale; a.wscb = g.scb; a.gate_rows = g.gate ? g.N : 0;
+    if (!lora_t) a.ws4 = g.s4;
     a.wq = (g.wq == 1 && a.wq >= 3) ? a.wq : g.wq;             // int8 linears: 3 / 4 = int8 activations (set by the program builder)
     a.xinv = g.xinv;
     const int mt = mmi_cdiv(a.B, g.T);
@@ -615,8 +677,21 @@ int launch_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, GemmArgs a, bool is_d
     }
     int rc;
     mmi_record_bytes((long)g.bytes);
-    if (is_dominant) lm->dominant_xlds = xl.on;
-    if (mt > 2) {
+    if (is_dominant) lm->dominant_xlds = xl.on && !lora_t;
+    if (lora_t) {
+        // an adapter handle: every linear on the LORA form of k_gemm_xp (the forms that never materialise their operand or own
+        // their main loop - k_gemm_xlds, k_gemm_xp_once - are not selected; their knobs are ignored)
+        auto it = lm->lora_by_wp.find(g.wp);
+        if (it == lm->lora_by_wp.end() || g.wq != 0 || a.wq != 0) return mmi_fail(MMI_ERR_STATE, "adapter handle: a linear without a bank");
+        a.lora_wp = it->second.b;
+        a.lora_xp = lora_t;
+        a.lora_ksteps = lm->lora_S * lm->lora_R / mmi_kstep(g.T);
+        a.lora_slot_ksteps = lm->lora_R / mmi_kstep(g.T);
+        const dim3 groups(g.NT * (a.osplit > 1 ? a.osplit : 1), p.ksplit);
+        if (mt == 1) rc = g.T == 32 ? launch_gemm_lora<32, 1>(s, groups, p.waves, p.u, a) : launch_gemm_lora<16, 1>(s, groups, p.waves, p.u, a);
+        else if (mt == 2) rc = g.T == 32 ? launch_gemm_lora<32, 2>(s, groups, p.waves, p.u, a) : launch_gemm_lora<16, 2>(s, groups, p.waves, p.u, a);
+        else rc = mmi_fail(MMI_ERR_UNSUPPORTED, "adapters run at most two batch tiles per linear");
+    } else if (mt > 2) {
         lm->rows_launches += 1;
         a.osplit = 1;
         rc = launch_rows(k, s, g, p, mt, a);
@@ -656,6 +731,21 @@ struct DepKv { uint16_t* kc; uint16_t* vc; int H, Dh, steps; };
 // int8 activations of one GEMM (lm->act8): `x` is the int8 operand Xq and sx its rows' absmax (wq 3)
 struct Q8 { int wq = 0; const float* sx = nullptr; };
 
+// Adapter handles: the shrink launch of linear g on its packed operand xp, as an op of its own under the site `<site>.lora`.
+// Returns the packed t the linear's tail reads (launch_gemm's lora_t); null on a handle without adapters (nothing is added)
+const u32x4* add_lora_shrink(mmi_lm* lm, const GemmW& g, const u32x4* xp) {
+    if (!lm->lora_on) return nullptr;
+    uint16_t* t = lm->lora_t;
+    const std::string site = lm->prog.site_;
+    lm->prog.site(site + ".lora");
+    GemmW gw = g;
+    const int B = lm->batch, G = lm->gen_batch;
+    const int* row_slot = lm->row_slot;
+    lm->prog.add([=](hipStream_t s) { return launch_lora_shrink(lm, s, gw, xp, B, row_slot, G, t); });
+    lm->prog.site(site);
+    return reinterpret_cast<const u32x4*>(t);
+}
+
 void add_gemm(mmi_lm* lm, const GemmW& g, const uint16_t* x, uint16_t* out, int out_features, bool out_packed, int epi,
               const uint16_t* resid, const uint16_t* emb = nullptr, const int* tok = nullptr, int tok_stride = 0,
               bool dominant = false, const DepKv* kv = nullptr, const Q8* q8 = nullptr) {
@@ -668,8 +758,9 @@ void add_gemm(mmi_lm* lm, const GemmW& g, const uint16_t* x, uint16_t* out, int 
     a.out_mode = out_packed ? MMI_OUT_PACKED : MMI_OUT_ROWMAJOR;
     a.out_ld = out_features;
     a.out_ksteps = packed_ksteps_t(lm, g.T, out_features);
+    const u32x4* lt = add_lora_shrink(lm, g, a.xp);
     GemmW gw = g;
-    lm->prog.add([lm, gw, a, dominant](hipStream_t s) { return launch_gemm(lm, s, gw, a, dominant); }, (long)g.bytes);
+    lm->prog.add([lm, gw, a, dominant, lt](hipStream_t s) { return launch_gemm(lm, s, gw, a, dominant, lt); }, (long)g.bytes);
 }
 
 // The depth transformer's attention inside its out_proj (k_dep_attn_out_proj): ONE session at the 16-row tile (the real-time
@@ -677,7 +768,7 @@ void add_gemm(mmi_lm* lm, const GemmW& g, const uint16_t* x, uint16_t* out, int 
 // per step (a wave works through its 2 B pairs one after the other; profiles/r04_logs/call_o2_summary.txt), hence one session only.
 // knobs.no_dep_attn_fusion: the two launches (A/B and the bit-equality test)
 bool dep_attn_fusable(const mmi_lm* lm, const GemmW& g, int H, int Dh, int steps) {
-    if (g.T != 16 || lm->batch != 1 || lm->act8 || g.wq != 0 || lm->knobs.no_dep_attn_fusion) return false;
+    if (g.T != 16 || lm->batch != 1 || lm->act8 || g.wq != 0 || lm->knobs.no_dep_attn_fusion || lm->lora_on) return false;
     if (Dh % 8 || Dh > 64 || steps > 8 || g.KSTEPS * 32 != H * Dh) return false;
     const GemmPlan p = plan_gemm(lm->knobs, g, false);
     const int kper = mmi_cdiv(g.KSTEPS, p.waves);
@@ -724,8 +815,9 @@ Pending add_gemm_resid(mmi_lm* lm, const GemmW& g, const uint16_t* in, uint16_t*
     memset(&a, 0, sizeof(a));
     if (q8) { a.wq = q8->wq; a.sx = q8->sx; }
     a.xp = reinterpret_cast<const u32x4*>(in); a.epi = MMI_EPI_PARTIAL; a.partial = lm->partial; a.B = lm->batch;
+    const u32x4* lt = add_lora_shrink(lm, g, a.xp);
     GemmW gw = g;
-    lm->prog.add([lm, gw, a](hipStream_t s) { return launch_gemm(lm, s, gw, a, false); }, (long)g.bytes);
+    lm->prog.add([lm, gw, a, lt](hipStream_t s) { return launch_gemm(lm, s, gw, a, false, lt); }, (long)g.bytes);
     Pending pd;
     pd.P = p.ksplit;
     if (q8 && q8->wq == 3 && g.wq == 1) { pd.sx = q8->sx; pd.scb = g.scb; }
@@ -836,7 +928,8 @@ void add_norm_gemm(mmi_lm* lm, const GemmW& g, uint16_t* x, const uint16_t* alph
                    int out_features, bool out_packed, int epi, const DepKv* kv = nullptr) {
     const bool a8 = lm->act8 && g.wq == 1;
     const int wq = a8 ? 3 : g.wq;
-    const bool fuse = g.KSTEPS <= norm_fused_max(wq) && !lm->knobs.no_norm_fusion && mmi_cdiv(lm->batch, g.T) <= 2;   // k_gemm_rows has no fused norm
+    const bool fuse = g.KSTEPS <= norm_fused_max(wq) && !lm->knobs.no_norm_fusion && mmi_cdiv(lm->batch, g.T) <= 2 &&   // k_gemm_rows has no fused norm
+                      !lm->lora_on;                            // an adapter's shrink launch reads the materialised operand
     if (!fuse) {
         if (a8) {
             add_resid_rmsnorm(lm, x, Pending{}, alpha, xn_scratch, D, lm->dxnq, lm->sx_dxn, g.T);
@@ -1112,8 +1205,9 @@ int build_program(mmi_lm* lm) {
             if (a8) { ga.xp = reinterpret_cast<const u32x4*>(lm->xnq); ga.sx = lm->sx_xn; ga.wq = 3; }
             ga.qrot = a.qrot; ga.kc = a.kc; ga.vc = a.vc; ga.offsets = lm->offsets_m; ga.H = H; ga.Dh = Dh; ga.cap = c.context; ga.kv8 = kv8 ? 1 : 0;
             ga.max_period = c.max_period; ga.rope = lm->rope;
+            const u32x4* lt = add_lora_shrink(lm, L.in_proj, ga.xp);
             GemmW gw = L.in_proj;
-            P.add([lm, gw, ga](hipStream_t s) { return launch_gemm(lm, s, gw, ga, false); }, (long)gw.bytes);
+            P.add([lm, gw, ga, lt](hipStream_t s) { return launch_gemm(lm, s, gw, ga, false, lt); }, (long)gw.bytes);
         }
         P.site("L.attn");
         const bool wave = attn_wave_kernel(lm->knobs);
@@ -1193,7 +1287,7 @@ int build_program(mmi_lm* lm) {
     add_gemm(lm, lm->text_linear, tout_in, lm->text_logits, c.text_card_out, false, MMI_EPI_STORE, nullptr, nullptr, nullptr, 0, false, nullptr, qt);
     // depformer_in[k](transformer_out) for every micro-step in one launch; each sampler then adds its token's embedding row
     // and writes the next micro-step's input (lm.py:465-470) - 8 dependent launches less on the sequential chain
-    const bool grouped = lm->dep_in_grouped;
+    const bool grouped = lm->dep_in_grouped && !lm->lora_on;     // (an adapter handle: one depformer_in, one bank, per micro-step)
     lm->op_depformer = P.ops.size();
     P.site("dep.in_all");
     if (grouped) add_gemm(lm, lm->dep_in_all, tout_in, lm->dpre, lm->dep_nw * dd, false, MMI_EPI_STORE, nullptr, nullptr, nullptr, 0, false, nullptr, qt);
@@ -1697,6 +1791,7 @@ extern "C" void mmi_lm_destroy(mmi_lm* lm) {
     MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
     if (!lm) return;
     mmi_lm_streaming_stop(lm);
+    lm->lora_mem.release();
     lm->wts.release();
     for (auto& e : lm->ev_pool) { hipEventDestroy(e.a); hipEventDestroy(e.b); }
     for (auto& e : lm->site_ev) { if (e.ev) hipEventDestroy(e.ev); }
@@ -1835,7 +1930,21 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
         lm->tts_stride = MMI_TTS_HDR + 2 * lm->tts_max_tokens + 3 * lm->tts_max_entries + 1 + (1 + c.dep_q) * lm->tts_max_prefix;
         ok &= hipSuccess == A.alloc(&lm->tts, (size_t)G * lm->tts_stride);
     }
+    lm->row_slot = nullptr;
+    lm->lora_t = nullptr;
+    size_t lora_t_elems = 0;
+    if (lm->lora_on) {
+        const int SR = lm->lora_S * lm->lora_R;
+        lora_t_elems = (size_t)mmi_cdiv(B, lm->T) * (SR / mmi_kstep(lm->T)) * 512;
+        ok &= hipSuccess == A.alloc(&lm->row_slot, (size_t)G);
+        ok &= hipSuccess == A.alloc(&lm->lora_t, lora_t_elems);
+    }
     if (!ok) return fail(mmi_fail(MMI_ERR_HIP, "out of device memory (LM streaming state)"));
+    if (lm->lora_on) {      // every row without an adapter; the padding rows of t are never written and must read as zero
+        MMI_LAUNCH(k_fill_i32, mmi_cdiv(G, 256), 256, 0, s, lm->row_slot, -1, (long)G);
+        MMI_HIP_CHECK(hipMemsetAsync(lm->lora_t, 0, lora_t_elems * sizeof(uint16_t), s));
+        lm->row_slot_h.assign(G, -1);
+    }
     MMI_HIP_CHECK(hipMemsetAsync(lm->exec, 1, G, s));
     MMI_HIP_CHECK(hipMemsetAsync(lm->offsets, 0, G * sizeof(long), s));
     if (guided) MMI_HIP_CHECK(hipMemsetAsync(lm->offsets_m, 0, B * sizeof(long), s));
@@ -1931,6 +2040,9 @@ extern "C" int mmi_lm_streaming_stop(mmi_lm* lm) {
     lm->prog.clear();
     lm->st.release();
     lm->tts = nullptr;
+    lm->row_slot = nullptr;
+    lm->lora_t = nullptr;
+    lm->row_slot_h.clear();
     if (lm->tts_stage) { hipHostFree(lm->tts_stage); lm->tts_stage = nullptr; }
     for (hipEvent_t e : lm->tts_stage_ev) if (e) hipEventDestroy(e);
     lm->tts_stage_ev.clear();
@@ -2046,6 +2158,172 @@ extern "C" int mmi_lm_set_row_condition(mmi_lm* lm, int32_t session, const mmi_r
     MMI_LAUNCH(k_lm_set_row_cond, mmi_cdiv(c->condition_sum ? d : 1, 256), 256, 0, s, lm->xlen, lm->coefs, lm->cond, set);
     MMI_CHECK_LAUNCH();
     return MMI_OK;
+}
+
+// ---- per-row LoRA adapters (modules/lora.py, loaders.py:486-516) --------------------------------------------------
+extern "C" int mmi_lm_enable_adapters(mmi_lm* lm, int32_t max_adapters, int32_t max_rank) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (lm->streaming) return mmi_fail(MMI_ERR_UNSUPPORTED, "adapters add launches to the step's launch list: enable them before streaming_start");
+    if (max_adapters == 0 && max_rank == 0) {
+        lm->lora_on = false;
+        lm->lora_S = lm->lora_R = 0;
+        lm->lora_by_wp.clear();
+        lm->lora_by_name.clear();
+        lm->lora_mem.release();
+        lm->lora_bad = nullptr;
+        return MMI_OK;
+    }
+    if (max_adapters < 1 || max_adapters > 8) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_enable_adapters: max_adapters must be 1..8");
+    if (max_rank != 32 && max_rank != 64 && max_rank != 96 && max_rank != 128)
+        return mmi_fail(MMI_ERR_INVALID, "mmi_lm_enable_adapters: max_rank must be 32, 64, 96 or 128 (whole k-steps at both tiles)");
+    if (lm->lora_on) return mmi_fail(MMI_ERR_STATE, "mmi_lm_enable_adapters: already enabled (turn them off with (0, 0) first)");
+    const mmi_lm_cfg& c = lm->cfg;
+    if (lm->q8 > 0) return mmi_fail(MMI_ERR_UNSUPPORTED, "adapters on quantised linears (int8 / fp8 / MXFP4) are not supported: the tail runs on the bf16 MFMA of a bf16 linear");
+    if (lm->max_batch > 64) return mmi_fail(MMI_ERR_UNSUPPORTED, "adapters are not supported above 64 model rows (k_gemm_rows has no adapter tail)");
+    if (c.cross_attention) return mmi_fail(MMI_ERR_UNSUPPORTED, "adapters are not supported on models with cross-attention layers");
+    if (c.extra_heads_num_heads > 0) return mmi_fail(MMI_ERR_UNSUPPORTED, "adapters are not supported on models with extra heads (the reference wraps their linears too)");
+    if (lm->demux || lm->text_emb2 || lm->vector_by_name.count("depformer_text_emb.low_rank.weight"))
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "adapters are not supported with low-rank or demuxed embeddings (the reference wraps their linears too)");
+    if (lm->Td != lm->T) return mmi_fail(MMI_ERR_UNSUPPORTED, "adapters are not supported with the depth transformer on its own tile (MMI_DEP_TILE)");
+    const int S = max_adapters, R = max_rank, SR = S * R;
+    auto fail = [&](int code) { lm->lora_by_wp.clear(); lm->lora_by_name.clear(); lm->lora_mem.release(); lm->lora_bad = nullptr; return code; };
+    lm->lora_mem.poison = 0;
+    for (const auto& kv : lm->linear_by_name) {
+        const GemmW& g = kv.second;
+        if (lm->lora_by_wp.count(g.wp)) { lm->lora_by_name[kv.first] = g.wp; continue; }
+        LoraBank bk;
+        const size_t na = (size_t)(SR / g.T) * g.KSTEPS * 64, nb = (size_t)g.NT * (SR / mmi_kstep(g.T)) * 64;     // 16-byte entries
+        if (lm->lora_mem.alloc(&bk.a, na) != hipSuccess || lm->lora_mem.alloc(&bk.b, nb) != hipSuccess)
+            return fail(mmi_fail(MMI_ERR_HIP, "out of device memory (adapter banks)"));
+        if (hipMemset(bk.a, 0, na * 16) != hipSuccess || hipMemset(bk.b, 0, nb * 16) != hipSuccess) return fail(mmi_fail(MMI_ERR_HIP, "memset"));
+        lm->lora_by_wp[g.wp] = bk;
+        lm->lora_by_name[kv.first] = g.wp;
+    }
+    if (lm->lora_mem.alloc(&lm->lora_bad, (size_t)1) != hipSuccess) return fail(mmi_fail(MMI_ERR_HIP, "out of device memory (adapter banks)"));
+    lm->lora_S = S; lm->lora_R = R;
+    lm->lora_on = true;
+    return MMI_OK;
+}
+
+namespace {
+const GemmW* lora_linear(const mmi_lm* lm, const std::string& weight_name) {
+    auto it = lm->linear_by_name.find(weight_name);
+    return it == lm->linear_by_name.end() ? nullptr : &it->second;
+}
+int lora_slot_free(const mmi_lm* lm, int slot, const char* what) {
+    if (!lm->lora_on) return mmi_fail(MMI_ERR_STATE, std::string(what) + ": the handle has no adapters (mmi_lm_enable_adapters)");
+    if (slot < 0 || slot >= lm->lora_S) return mmi_fail(MMI_ERR_INVALID, std::string(what) + ": slot outside [0, max_adapters)");
+    if (lm->streaming)
+        for (int v : lm->row_slot_h)
+            if (v == slot) return mmi_fail(MMI_ERR_STATE, std::string(what) + ": a live session runs on this slot");
+    return MMI_OK;
+}
+// slot `slot` of every bank zeroed (stream ordered)
+int lora_zero_slot(mmi_lm* lm, int slot, hipStream_t s) {
+    const int R = lm->lora_R, SR = lm->lora_S * R;
+    for (const auto& kv : lm->linear_by_name) {
+        const GemmW& g = kv.second;
+        const LoraBank& bk = lm->lora_by_wp[g.wp];
+        const size_t na = (size_t)(R / g.T) * g.KSTEPS * 64;
+        MMI_HIP_CHECK(hipMemsetAsync(bk.a + (size_t)slot * na, 0, na * 16, s));
+        const int ksr = R / mmi_kstep(g.T);
+        const long n = (long)g.NT * ksr * 512;
+        MMI_LAUNCH(k_pack_lora_slot, (int)mmi_cdiv64((int64_t)n, 256), 256, 0, s, (const uint16_t*)nullptr, reinterpret_cast<uint16_t*>(bk.b), 0, 0,
+                   g.T, g.NT, ksr, 0, SR / mmi_kstep(g.T), slot * ksr, 1.f);
+    }
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+}  // namespace
+
+extern "C" int mmi_lm_load_adapter(mmi_lm* lm, int32_t slot, float scaling, const mmi_tensor_desc* descs, int32_t n, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm || (!descs && n > 0) || n < 0) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_load_adapter: bad argument");
+    int rc = lora_slot_free(lm, slot, "mmi_lm_load_adapter");
+    if (rc) return rc;
+    if (!std::isfinite(scaling)) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_load_adapter: scaling must be finite");
+    hipStream_t s = (hipStream_t)stream;
+    const int R = lm->lora_R, SR = lm->lora_S * R;
+    // ---- every check before anything is written
+    struct Pair { const mmi_tensor_desc* a = nullptr; const mmi_tensor_desc* b = nullptr; };
+    std::map<std::string, Pair> pairs;          // by `<linear>.weight`
+    const std::string sa = ".lora_A.weight", sb = ".lora_B.weight", sf = ".frozen_W.weight";
+    auto ends = [](const std::string& k, const std::string& suf) { return k.size() > suf.size() && k.compare(k.size() - suf.size(), suf.size(), suf) == 0; };
+    for (int i = 0; i < n; ++i) {
+        const std::string key = descs[i].name ? descs[i].name : "";
+        if (ends(key, sf)) continue;             // (the base weight under the name a LoRALinear gives it: not the adapter's)
+        const bool isa = ends(key, sa), isb = ends(key, sb);
+        const std::string stem = (isa || isb) ? key.substr(0, key.size() - sa.size()) : key;
+        if ((!isa && !isb) || !lora_linear(lm, stem + ".weight"))
+            return mmi_fail(MMI_ERR_INVALID, "unexpected_keys in the lora weights: " + key);          // loaders.py:508-511
+        if (descs[i].dtype != MMI_BF16 || descs[i].ndim != 2 || !descs[i].data) return mmi_fail(MMI_ERR_INVALID, "adapter tensors must be bf16 matrices: " + key);
+        (isa ? pairs[stem + ".weight"].a : pairs[stem + ".weight"].b) = &descs[i];
+    }
+    for (const auto& kv : pairs) {
+        const GemmW& g = *lora_linear(lm, kv.first);
+        const std::string stem = kv.first.substr(0, kv.first.size() - 7);
+        if (!kv.second.a || !kv.second.b) return mmi_fail(MMI_ERR_INVALID, "LoRA weights carry " + stem + (kv.second.a ? sa + " without " + stem + sb : sb + " without " + stem + sa));
+        const mmi_tensor_desc &A = *kv.second.a, &Bm = *kv.second.b;
+        const long r = A.shape[0], Nfull = g.gate ? 2L * g.N : g.N;
+        if (r < 8 || r % 8 != 0 || r > R) return mmi_fail(MMI_ERR_INVALID, "adapter rank must be a multiple of 8 and at most max_rank: " + stem);
+        if (A.shape[1] != g.K || Bm.shape[0] != Nfull || Bm.shape[1] != r) return mmi_fail(MMI_ERR_INVALID, "LoRA shapes do not fit " + kv.first);
+    }
+    MMI_HIP_CHECK(hipMemsetAsync(lm->lora_bad, 0, sizeof(int), s));
+    for (const auto& kv : pairs) {
+        const mmi_tensor_desc &A = *kv.second.a, &Bm = *kv.second.b;
+        const long na = (long)A.shape[0] * A.shape[1], nb = (long)Bm.shape[0] * Bm.shape[1];
+        MMI_LAUNCH(k_lora_check_finite, (int)mmi_cdiv64(na, 256), 256, 0, s, (const uint16_t*)A.data, na, 1.f, lm->lora_bad);
+        MMI_LAUNCH(k_lora_check_finite, (int)mmi_cdiv64(nb, 256), 256, 0, s, (const uint16_t*)Bm.data, nb, scaling, lm->lora_bad);
+    }
+    MMI_CHECK_LAUNCH();
+    int bad = 0;
+    MMI_HIP_CHECK(hipMemcpyAsync(&bad, lm->lora_bad, sizeof(int), hipMemcpyDeviceToHost, s));
+    MMI_HIP_CHECK(hipStreamSynchronize(s));
+    if (bad) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_load_adapter: the adapter (or scaling * lora_B in bf16) holds values that are not finite");
+    // ---- the slot: zero everywhere, then the linears the adapter mentions
+    if ((rc = lora_zero_slot(lm, slot, s))) return rc;
+    for (const auto& kv : pairs) {
+        const GemmW& g = *lora_linear(lm, kv.first);
+        const LoraBank& bk = lm->lora_by_wp[g.wp];
+        const mmi_tensor_desc &A = *kv.second.a, &Bm = *kv.second.b;
+        const int r = (int)A.shape[0], ksr = R / mmi_kstep(g.T);
+        const size_t na = (size_t)(R / g.T) * g.KSTEPS * 64;
+        const long ea = (long)(R / g.T) * g.KSTEPS * 512, eb = (long)g.NT * ksr * 512;
+        MMI_LAUNCH(k_pack_lora_slot, (int)mmi_cdiv64((int64_t)ea, 256), 256, 0, s, (const uint16_t*)A.data, reinterpret_cast<uint16_t*>(bk.a + (size_t)slot * na),
+                   r, g.K, g.T, R / g.T, g.KSTEPS, 0, g.KSTEPS, 0, 1.f);
+        MMI_LAUNCH(k_pack_lora_slot, (int)mmi_cdiv64((int64_t)eb, 256), 256, 0, s, (const uint16_t*)Bm.data, reinterpret_cast<uint16_t*>(bk.b),
+                   (int)Bm.shape[0], r, g.T, g.NT, ksr, g.gate ? g.N : 0, SR / mmi_kstep(g.T), slot * ksr, scaling);
+    }
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+
+extern "C" int mmi_lm_unload_adapter(mmi_lm* lm, int32_t slot, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    int rc = lora_slot_free(lm, slot, "mmi_lm_unload_adapter");
+    if (rc) return rc;
+    return lora_zero_slot(lm, slot, (hipStream_t)stream);
+}
+
+extern "C" int mmi_lm_set_row_adapter(mmi_lm* lm, int32_t session, int32_t slot, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (!lm->streaming || !lm->row_slot) return mmi_fail(MMI_ERR_STATE, "adapters are not enabled on a live stream (mmi_lm_enable_adapters, then streaming_start)");
+    if (session < 0 || session >= lm->gen_batch) return mmi_fail(MMI_ERR_INVALID, "session outside [0, batch)");
+    if (slot < -1 || slot >= lm->lora_S) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_set_row_adapter: slot must be -1 (none) or in [0, max_adapters)");
+    MMI_LAUNCH(k_fill_i32, 1, 64, 0, (hipStream_t)stream, lm->row_slot + session, (int)slot, 1L);
+    MMI_CHECK_LAUNCH();
+    lm->row_slot_h[session] = slot;
+    return MMI_OK;
+}
+
+int mmi_lm_adapter_slots(const mmi_lm* lm) { return lm && lm->lora_on ? lm->lora_S : 0; }      // (batcher.hip)
+
+extern "C" int32_t mmi_lm_row_adapter(const mmi_lm* lm, int32_t session) {
+    if (!lm || !lm->streaming || !lm->row_slot || session < 0 || session >= lm->gen_batch) return -1;
+    return lm->row_slot_h[session];
 }
 
 // ---- the TTS script machine ---------------------------------------------------------------------------------------------------
@@ -2400,6 +2678,8 @@ extern "C" int mmi_lm_state_load(mmi_lm* lm, const void* src, int64_t bytes, int
         std::vector<RowSamp> tab(lm->gen_batch);         // and the restored table says which rows have settings of their own
         MMI_HIP_CHECK(hipMemcpy(tab.data(), lm->rowtab, tab.size() * sizeof(RowSamp), hipMemcpyDeviceToHost));
         for (int b = 0; b < lm->gen_batch; ++b) lm->row_active[b] = tab[b].active ? 1 : 0;
+        if (lm->row_slot)                                 // and which adapter slots are in use
+            MMI_HIP_CHECK(hipMemcpy(lm->row_slot_h.data(), lm->row_slot, (size_t)lm->gen_batch * sizeof(int), hipMemcpyDeviceToHost));
     }
     lm->forced_armed = false;
     lm->noise_on = true;               // the snapshot carries its own use_noise word: the next step rewrites it
@@ -2466,10 +2746,19 @@ extern "C" int mmi_lm_seek(mmi_lm* lm, const int64_t* offsets, mmi_stream stream
         if (e_ != hipSuccess) return done(mmi_fail(MMI_ERR_HIP, std::string("kernel launch failed: ") + hipGetErrorString(e_))); \
     } while (0)
 
-extern "C" int mmi_lm_debug_linear(mmi_lm* lm, const char* weight_name, const char* alpha_name, int32_t path, const void* x_bf16,
-                                   int32_t rows, void* out_bf16, int8_t* codes, float* absmax, void* norm_out, mmi_stream stream) {
+// row_slots (mmi_lm_debug_linear_lora): the rows' adapter slots, a host array - the shrink launch, then the linear with its tail
+static int debug_linear_impl(mmi_lm* lm, const char* weight_name, const char* alpha_name, int32_t path, const void* x_bf16,
+                             int32_t rows, void* out_bf16, int8_t* codes, float* absmax, void* norm_out, const int32_t* row_slots,
+                             mmi_stream stream) {
     MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
     if (!lm || !weight_name || !x_bf16 || !out_bf16) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (row_slots) {
+        if (!lm->lora_on) return mmi_fail(MMI_ERR_STATE, "mmi_lm_debug_linear_lora: the handle has no adapters (mmi_lm_enable_adapters)");
+        if (path != MMI_DBG_PLAIN && path != MMI_DBG_SPLITK)
+            return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_linear_lora: an adapter handle runs the plain and the split-K path");
+        for (int b = 0; b < rows; ++b)
+            if (row_slots[b] < -1 || row_slots[b] >= lm->lora_S) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_linear_lora: slot must be -1 (none) or in [0, max_adapters)");
+    }
     if (rows <= 0 || rows > lm->max_batch) return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_linear: rows must be 1..max_batch");
     auto it = lm->linear_by_name.find(weight_name);
     if (it == lm->linear_by_name.end()) return mmi_fail(MMI_ERR_MISSING_WEIGHT, std::string("no packed linear named ") + weight_name);
@@ -2514,6 +2803,15 @@ extern "C" int mmi_lm_debug_linear(mmi_lm* lm, const char* weight_name, const ch
     MMI_DBG_HIP(hipMemsetAsync(zeros, 0, ((size_t)N + 8) * 2, s));
     MMI_LAUNCH(k_pack_rows, mmi_cdiv(rows * K, 256), 256, 0, s, (const uint16_t*)x_bf16, rows, K, xp, T, kin);
     MMI_DBG_LAUNCHED();
+    int* slots_dev = nullptr;
+    uint16_t* lora_t = nullptr;
+    if (row_slots) {
+        const size_t telems = (size_t)mt * (lm->lora_S * lm->lora_R / KS) * 512;
+        if (A.alloc(&slots_dev, (size_t)rows) != hipSuccess || A.alloc(&lora_t, telems) != hipSuccess)
+            return done(mmi_fail(MMI_ERR_HIP, "out of device memory (mmi_lm_debug_linear_lora)"));
+        MMI_DBG_HIP(hipMemcpyAsync(slots_dev, row_slots, (size_t)rows * sizeof(int), hipMemcpyHostToDevice, s));
+        MMI_DBG_HIP(hipMemsetAsync(lora_t, 0, telems * 2, s));
+    }
     const uint16_t* operand = xp;              // the packed bf16 rows the GEMM (or its quantiser) reads
     const bool gated = g.gate != 0;
     GemmArgs a;
@@ -2542,7 +2840,11 @@ extern "C" int mmi_lm_debug_linear(mmi_lm* lm, const char* weight_name, const ch
             pd.P = p.ksplit;
             if (a8) { pd.sx = sx; pd.scb = g.scb; }
         }
-        rc = launch_gemm(lm, s, g, a, false);
+        if (row_slots) {
+            rc = launch_lora_shrink(lm, s, g, a.xp, rows, slots_dev, rows, lora_t);
+            if (rc) return done(rc);
+        }
+        rc = launch_gemm(lm, s, g, a, false, reinterpret_cast<const u32x4*>(lora_t));
         if (rc) return done(rc);
         if (path == MMI_DBG_SPLITK) {          // the fold of the next norm launch: x (= 0) + bf16(sum of the partials)
             const int nthN = [&] { int n = mmi_cdiv(N / 8, 64) * 64; return n > 1024 ? 1024 : n; }();
@@ -2582,6 +2884,18 @@ extern "C" int mmi_lm_debug_linear(mmi_lm* lm, const char* weight_name, const ch
     if (hipStreamSynchronize(s) != hipSuccess) { A.release(); return mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_linear: the launches failed"); }
     A.release();
     return MMI_OK;
+}
+
+extern "C" int mmi_lm_debug_linear(mmi_lm* lm, const char* weight_name, const char* alpha_name, int32_t path, const void* x_bf16,
+                                   int32_t rows, void* out_bf16, int8_t* codes, float* absmax, void* norm_out, mmi_stream stream) {
+    return debug_linear_impl(lm, weight_name, alpha_name, path, x_bf16, rows, out_bf16, codes, absmax, norm_out, nullptr, stream);
+}
+
+extern "C" int mmi_lm_debug_linear_lora(mmi_lm* lm, const char* weight_name, const char* alpha_name, int32_t path, const void* x_bf16,
+                                        int32_t rows, void* out_bf16, int8_t* codes, float* absmax, void* norm_out, const int32_t* row_slots,
+                                        mmi_stream stream) {
+    if (!row_slots) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_linear_lora: null row_slots");
+    return debug_linear_impl(lm, weight_name, alpha_name, path, x_bf16, rows, out_bf16, codes, absmax, norm_out, row_slots, stream);
 }
 
 extern "C" int64_t mmi_lm_stat(const mmi_lm* lm, int32_t which) {

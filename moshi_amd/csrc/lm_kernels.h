@@ -68,6 +68,47 @@ __global__ void k_pack_w_bf16(const uint16_t* __restrict__ W, uint16_t* __restri
     P[idx] = v;
 }
 
+// One slot of an adapter bank (GemmArgs::lora_*): k_pack_w_bf16 of the [N][K] matrix W, scaled (bf16(scale * w): lora_B carries
+// the adapter's scaling, exact for powers of two; lora_A takes 1), into k-steps [ks0, ks0 + KSTEPS) of a packed weight whose
+// tiles hold KSTEPS_DST k-steps.  W == nullptr: the slot's entries are zeroed (unload).
+__global__ void k_pack_lora_slot(const uint16_t* __restrict__ W, uint16_t* __restrict__ P, int N, int K, int TN, int NT, int KSTEPS,
+                                 int gate_hidden, int KSTEPS_DST, int ks0, float scale) {
+    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    long total = (long)NT * KSTEPS * 512;
+    if (idx >= total) return;
+    int e = (int)(idx & 7);
+    int lane = (int)((idx >> 3) & 63);
+    long rest = idx >> 9;
+    int ks = (int)(rest % KSTEPS);
+    int nt = (int)(rest / KSTEPS);
+    int i, kq, kstep;
+    if (TN == 32) { i = lane & 31; kq = lane >> 5; kstep = 16; } else { i = lane & 15; kq = lane >> 4; kstep = 32; }
+    int k = ks * kstep + 8 * kq + e;
+    long row;
+    bool valid;
+    if (gate_hidden > 0) {
+        int half = TN / 2;
+        int r = nt * half + (i < half ? i : i - half);
+        valid = r < gate_hidden;
+        row = (i < half ? 0 : gate_hidden) + r;
+    } else {
+        row = (long)nt * TN + i;
+        valid = row < N;
+    }
+    uint16_t v = 0;
+    if (W && valid && k < K) v = mmi_f32_to_bf16(mmi_bf16_to_f32(W[row * K + k]) * scale);
+    P[(((long)nt * KSTEPS_DST + ks0 + ks) * 64 + lane) * 8 + e] = v;
+}
+
+// *bad = 1 when bf16(scale * w) is not finite for some w (adapter tensors are checked before anything is written: a zero
+// activation against an Inf weight is a NaN in rows that do not even use the slot)
+__global__ void k_lora_check_finite(const uint16_t* __restrict__ W, long n, float scale, int* __restrict__ bad) {
+    long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n) return;
+    const uint16_t v = mmi_f32_to_bf16(mmi_bf16_to_f32(W[idx]) * scale);
+    if ((v & 0x7f80u) == 0x7f80u) *bad = 1;
+}
+
 // int8 weights (bitsandbytes-style per-output-row absmax quantisation, utils/quantize.py:13-22: `weight` int8 CB +
 // `weight_scb` fp32 row absmax; W ~= CB * SCB / 127).  Same tile order as the bf16 packing with TWO k-steps per 16-byte
 // lane entry: Wq[nt][kp][lane][16], entries 0..7 = k-step 2kp, 8..15 = k-step 2kp+1 (zero padded to an even count).
@@ -223,7 +264,7 @@ __device__ __forceinline__ float mmi_i8_dequant(int out32, float sca, float scb)
 // fragments from L2.  The waves' partial tiles are summed through LDS in a fixed order (deterministic), and the
 // epilogue (bf16 rounding point of nn.Linear, residual add, SiLU gate, embedding add) writes 8 consecutive features
 // of one session as one 16-byte vector.
-enum { MMI_EPI_STORE = 0, MMI_EPI_RESID = 1, MMI_EPI_GATE = 2, MMI_EPI_EMB = 3, MMI_EPI_PARTIAL = 4, MMI_EPI_ROPE_KV = 5, MMI_EPI_DEP_QKV0 = 6 };
+enum { MMI_EPI_STORE = 0, MMI_EPI_RESID = 1, MMI_EPI_GATE = 2, MMI_EPI_EMB = 3, MMI_EPI_PARTIAL = 4, MMI_EPI_ROPE_KV = 5, MMI_EPI_DEP_QKV0 = 6, MMI_EPI_LORA_T = 7 };
 enum { MMI_OUT_ROWMAJOR = 0, MMI_OUT_PACKED = 1 };
 
 struct GemmArgs {
@@ -232,8 +273,14 @@ struct GemmArgs {
     uint16_t* out;          // row-major [B][out_ld] or packed [.][out_ksteps][64][8]
     const uint16_t* resid;  // EPI_RESID: same geometry as out
     const uint16_t* emb;    // EPI_EMB: embedding table [rows][N]
+    union {
     const int* tok;         // EPI_EMB: token per session, tok[(b % tok_rows) * tok_stride] (model rows beyond tok_rows are the
+    const int* row_slot;    // MMI_EPI_LORA_T: adapter slot of session b % tok_rows (guidance twins follow their session), -1 = none
+    };
+    union {
     int tok_stride;         // guidance twins of the sessions and take the same token)
+    int lora_rank;          // MMI_EPI_LORA_T: R, the columns of one slot (a multiple of 32: a task's 8 features share a slot)
+    };
     int tok_rows;
     int B, N, KSTEPS, NT;
     int out_mode, out_ld, out_ksteps;
@@ -244,7 +291,10 @@ struct GemmArgs {
     float xinv;             // fp8: 1 / input_scale, applied to the activations before the e4m3 conversion
     int wq;                 // host side only: 0 bf16, 1 int8 (widened to bf16), 2 fp8 (fp8 MFMA) weights, 3 int8 weights x int8 activations,
                             // 4 MXFP4 (widened to bf16)
+    union {
     const uint8_t* ws4;     // MXFP4 weights: the E8M0 scale bytes in entry order [NT][KSTEPS][64][TN == 32 ? 2 : 4] (k_pack_w_fp4); else null
+    const u32x4* lora_wp;   // LORA: packed bf16(scaling * B_all) [NT][lora_ksteps][64]
+    };
     const float* sx;        // WQ = 3 with pre-quantised activations: xp holds int8 entries Xq[mt][kp][lane][16] (k_quant_rows_i8 / the
                             // norm kernel) and sx[b] the row absmax they were scaled by (bitsandbytes' SCA); the epilogue multiplies
                             // the int32 sum by SCA[b] / 127 * SCB[n] / 127.  k_gemm_q8: written here for the epilogue (LDS)
@@ -263,15 +313,32 @@ struct GemmArgs {
     const float* rope;      // [B][Dh/2][2]: (cos, sin) of the new position's angles, filled once per step by k_lm_prepare
     int kv8;                // the ring holds e4m3 bytes instead of bf16 (fp8 KV cache: half the attention stream)
     // k_gemm_xp_norm: RMSNorm of the input rows fused in front of the GEMM (xp holds the un-normalised rows)
+    union {
     const uint16_t* alpha;  // [D]
+    const u32x4* lora_xp;   // LORA: packed t [MT][lora_ksteps][64]
+    };
+    union {
     int D;                  // features of a row (the mean is over D, not the padded K)
+    int lora_ksteps;        // LORA: S * R / k-step
+    };
+    union {
     float eps;
+    int lora_slot_ksteps;   // LORA: R / k-step, the k-steps of one slot
+    };
     int osplit;             // k_gemm_xp: > 1 = every n-tile is shared by `osplit` workgroups, each owning TN / 8 / osplit of its row octets
                             // (grid.x = NT * osplit).  For GEMMs with few n-tiles (N = 1024 of the depth transformer: 32 tiles on
                             // 256 CUs), where one CU cannot pull its 64-180 KB of weights faster than ~25 GB/s: a workgroup's lanes of
                             // octets it does not own repeat an owned lane's address (no extra HBM traffic; those MFMA rows are garbage
                             // that nobody writes), the epilogue writes only the owned 8-feature groups.  Not for gated epilogues.
+    // per-row LoRA adapters (modules/lora.py:116-118, unmerged).  The bank of a linear holds S slots of R columns:
+    // A_all [S * R][K] and bf16(scaling * B_all) [N][S * R], both packed like any weight.  A shrink launch (k_gemm_xp<.., LORA_T>,
+    // MMI_EPI_LORA_T) writes t = bf16(A_all x) as a packed operand of S * R features, zero outside the row's own slot; the
+    // linear itself (k_gemm_xp<.., LORA>) walks B_all against t behind its K slice, into the same accumulators.  Their
+    // arguments are the lora_* / row_slot members above: each shares its bytes with a member that those launches never read
+    // (bf16 linears have no ws4, k_gemm_xp no fused norm, a shrink launch no embedding), so the struct - the kernel argument of
+    // every GEMM launch - is what it was
 };
+static_assert(sizeof(GemmArgs) == 232, "GemmArgs is the kernel argument of every GEMM launch: new arguments share bytes, they are not appended");
 
 // The residual (or embedding) vector the thread's FIRST epilogue task will add, requested before the weight stream starts
 // so that its latency is hidden behind the main loop instead of extending the epilogue.
@@ -305,7 +372,8 @@ __device__ __forceinline__ u32x4 mmi_gemm_prefetch_addend(const GemmArgs& a, int
 // kernels that own all of the LDS themselves (k_gemm_xlds).
 // g_lo / g_hi: only the tile's 8-feature groups [g_lo, g_hi) are written (k_gemm_xlds hands a tile's row octets to two
 // workgroups when that balances the chip: 384 in_proj tiles over 256 CUs = 6 octets each); default = the whole tile.
-template <int TN, int MT, int NTW, int WAVES, bool EXT = false>
+// LORA_T: the shrink launch's epilogue (MMI_EPI_LORA_T) is compiled in - only into the shrink instantiations of k_gemm_xp.
+template <int TN, int MT, int NTW, int WAVES, bool EXT = false, bool LORA_T = false>
 __device__ __forceinline__ void mmi_gemm_epilogue(const GemmArgs& a, float (&accv)[NTW][MT][TN == 32 ? 16 : 4], int wave, int lane,
                                                   int nt0, u32x4 pre, float* red_ext = nullptr, int g_lo = 0, int g_hi = 4,
                                                   const float* sx_local = nullptr) {
@@ -497,6 +565,20 @@ __device__ __forceinline__ void mmi_gemm_epilogue(const GemmArgs& a, float (&acc
             *reinterpret_cast<u32x4*>(dst) = ov;
             continue;
         }
+        if constexpr (LORA_T) {
+            if (a.epi == MMI_EPI_LORA_T) {
+                // t = bf16(A x), the bf16 output of lora_A (modules/lora.py:117), for the columns of the row's own slot; 0 for
+                // every other slot's, so that the tail of the linear adds nothing of theirs
+                const int slot = a.row_slot[b % a.tok_rows];
+                u32x4 tv = {0u, 0u, 0u, 0u};
+                if (slot >= 0 && n0 / a.lora_rank == slot) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) tv[e] = mmi_pack_bf16x2(s[2 * e], s[2 * e + 1]);
+                }
+                *reinterpret_cast<u32x4*>(a.out + mmi_xp_index(TN, b, n0, a.out_ksteps)) = tv;
+                continue;
+            }
+        }
         uint16_t* dst = a.out_mode == MMI_OUT_PACKED ? a.out + mmi_xp_index(TN, b, n0, a.out_ksteps)
                                                      : a.out + (long)b * a.out_ld + n0;
         float o[8];
@@ -557,8 +639,15 @@ __device__ __forceinline__ uint32_t mmi_fp4_scale_of(uint32_t s, int j) { return
 // reduction + epilogue runs under the other's weight stream (136 registers unbounded; 8 spill, outside the loop).  Same-box at
 // 1 / 8 / 16 sessions: -0.12 / -0.14 / -0.12 ms per step (in_proj 20.9 -> 19.4 us, linear_in 38.4 -> 35.5, text head 48.9 ->
 // 44.2; profiles/r04_logs/call_m_summary.txt).
-template <int TN, int MT, int NTW, int WAVES, int U, int WQ = 0>
-__global__ __launch_bounds__(WAVES * 64, (TN == 16 && MT == 1 && NTW == 1 && WQ == 0 && WAVES == 8) ? 4 : 1) void k_gemm_xp(GemmArgs a) {
+// LORA (bf16 weights): behind its K slice the wave walks its share of the adapter bank's packed B tile against the packed t of
+// the shrink launch (GemmArgs::lora_*), same MFMA, same accumulators; where K is split over gridDim.y, workgroup row 0 alone.
+// The k-steps OF EACH SLOT are shared out over the waves by the main loop's rule (contiguous slices in wave order), so a wave
+// adds the same share of a row's adapter whichever slot holds it - every other slot's t is +0 and changes no sum: a session's
+// bits do not depend on its slot.  Everything behind the accumulators is as without it.
+// LORA_T: a shrink launch (A_all against the linear's operand): the plain kernel with MMI_EPI_LORA_T compiled into its epilogue.
+template <int TN, int MT, int NTW, int WAVES, int U, int WQ = 0, bool LORA = false, bool LORA_T = false>
+__global__ __launch_bounds__(WAVES * 64, (TN == 16 && MT == 1 && NTW == 1 && WQ == 0 && WAVES == 8 && !LORA && !LORA_T) ? 4 : 1) void k_gemm_xp(GemmArgs a) {
+    static_assert(!(LORA || LORA_T) || (WQ == 0 && NTW == 1), "adapters run on bf16 linears, one n-tile per workgroup");
     constexpr bool W8 = WQ == 1;
     constexpr int R = TN == 32 ? 16 : 4;          // accumulator registers per MFMA tile
     constexpr int XS = WQ == 4 ? 4 : ((WQ == 1 || WQ == 2) ? 2 : 1);   // activation fragments per weight entry
@@ -708,6 +797,33 @@ __global__ __launch_bounds__(WAVES * 64, (TN == 16 && MT == 1 && NTW == 1 && WQ 
         for (int u = 0; u < U - 1; ++u)
             if (u < rem) { MMI_G_MMA1(wA, xA, sA, u) }
     }
+    if constexpr (LORA) {
+        if (blockIdx.y == 0) {
+            const int lks = a.lora_ksteps, rks = a.lora_slot_ksteps;
+            const int lper = (rks + WAVES - 1) / WAVES;
+            const int l0 = min(rks, wave * lper), lsl = min(rks, l0 + lper) - l0;     // the wave's k-steps [l0, l0 + lsl) of every slot
+            const int ln = lsl * (lks / rks);
+            const u32x4* lw = a.lora_wp + ((long)min(nt0, a.NT - 1) * lks + l0) * 64 + wlane;
+            const u32x4* lx = a.lora_xp + l0 * 64 + lane;
+            for (int g = 0; g < ln; g += U) {
+                // up to U k-steps requested together, from clamped (valid) entries; only the live ones meet the matrix core
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int i = min(g + u, ln - 1);
+                    const int ks = (i / lsl) * rks + i % lsl;
+                    wA[u][0] = mmi_load_nt(lw + ks * 64);
+#pragma unroll
+                    for (int m = 0; m < MT; ++m) xA[u][m][0] = lx[((long)m * lks + ks) * 64];
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (g + u < ln) {
+#pragma unroll
+                        for (int m = 0; m < MT; ++m) { MMI_G_MFMA(wA[u][0], xA[u][m][0], acc[0][m]) }
+                    }
+            }
+        }
+    }
 #undef MMI_G_LOAD
 #undef MMI_G_MMA
 #undef MMI_G_MMA1
@@ -723,7 +839,7 @@ __global__ __launch_bounds__(WAVES * 64, (TN == 16 && MT == 1 && NTW == 1 && WQ 
             for (int r = 0; r < R; ++r) {
                 accv[t][m][r] = acc[t][m][r];      // WQ == 3: the wave's int32 sum, as its bit pattern (summed as integers by the epilogue)
             }
-    mmi_gemm_epilogue<TN, MT, NTW, WAVES>(a, accv, wave, lane, nt0, pre, nullptr, g_lo, g_hi);
+    mmi_gemm_epilogue<TN, MT, NTW, WAVES, false, LORA_T>(a, accv, wave, lane, nt0, pre, nullptr, g_lo, g_hi);
 }
 
 // k_gemm_xp for GEMMs that are a LATENCY chain, not a stream (the depth transformer's linear_out: 5.8 MB behind 128 workgroups,

@@ -120,12 +120,16 @@ class LMModel:
             "mxfp4" converts them to OCP MXFP4 (`weight` uint8 code pairs + `weight_scale_e8m0`; weight-only, widened to bf16 in
             the GEMM - exactly the bf16 engine on `dequantize_lm_state_dict_mxfp4`); in_features must be multiples of 32;
             a state dict that already carries int8 / fp8 / MXFP4 weights is used as is.
+        adapters: (max_adapters, max_rank) - room for up to 8 LoRA adapters of rank <= 32 / 64 / 96 / 128 NEXT TO this base model,
+            chosen per session (`load_adapter`, `LMGen.set_session_adapter`; modules/lora.py, unmerged).  bf16 linears, at most 64
+            model rows, no cross-attention layers, no extra heads.  None: a plain handle.
     """
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], config: Optional[LMConfig] = None,
                  device: torch.device | str = "cuda", max_batch: int = 32, lib: Optional[_capi.Lib] = None,
                  quantize: bool | str = False, fuser: Optional[ConditionFuser] = None, kv_cache: Optional[str] = None,
-                 cross_capacity: Optional[int] = None, max_rows: Optional[int] = None):
+                 cross_capacity: Optional[int] = None, max_rows: Optional[int] = None,
+                 adapters: Optional[Tuple[int, int]] = None):
         if max_rows is not None:
             if max_batch > 64:
                 raise ValueError("max_rows and max_batch > 64 are mutually exclusive: max_rows alone sizes the handle")
@@ -190,6 +194,11 @@ class LMModel:
         self.training = False
         if cross_capacity is not None:
             self.set_cross_capacity(cross_capacity)
+        self.adapters = None
+        if adapters is not None:
+            max_adapters, max_rank = adapters
+            lib.check(lib.mmi_lm_enable_adapters(self._handle, int(max_adapters), int(max_rank)))
+            self.adapters = (int(max_adapters), int(max_rank))
 
     def __del__(self):
         try:
@@ -206,6 +215,39 @@ class LMModel:
         room for `LMGen.set_session_condition` / `SessionBatcher.open(condition=)` to bring a longer source than the one the
         stream starts with.  None or 0 = the length of the start's source.  Not while streaming."""
         self._lib.check(self._lib.mmi_lm_set_cross_capacity(self._handle, int(positions or 0)))
+
+    # ---- LoRA adapters next to the base model (mmi_lm_enable_adapters) ---------------------------------
+    def load_adapter(self, slot: int, lora_state_dict: Dict[str, torch.Tensor], scaling: float = 2.0) -> None:
+        """Adapter `slot` = `<linear>.lora_A.weight` [r, in] / `<linear>.lora_B.weight` [out, r] of `lora_state_dict` (the keys of a
+        reference LoRA checkpoint; fused multi-step projections are split like the base weights'), run unmerged as
+        `frozen_W(x) + lora_B(lora_A(x)) * scaling` (modules/lora.py:116-118) for the sessions that select it.  Allowed while
+        streaming; refused while a live session runs on the slot.  Unknown keys, shapes that do not fit, a rank above the
+        handle's or values that are not finite raise ValueError and leave the slot as it was."""
+        from .weights import normalize_lm_state_dict
+        sd = normalize_lm_state_dict(dict(lora_state_dict), self.config)
+        sd = {k: v.detach().to(device=self.device, dtype=torch.bfloat16).contiguous() for k, v in sd.items()}
+        descs, keep = _capi.tensor_descs(sd)
+        self._lib.check(self._lib.mmi_lm_load_adapter(self._handle, int(slot), float(scaling), descs, len(sd), _capi.stream_ptr(self.device)))
+        if self.device.type == "cuda":          # the packing launches read the tensors: keep them until it has run
+            torch.cuda.current_stream(self.device).synchronize()
+        del keep, sd
+
+    def unload_adapter(self, slot: int) -> None:
+        """Zeroes adapter `slot` (refused while a live session runs on it)."""
+        self._lib.check(self._lib.mmi_lm_unload_adapter(self._handle, int(slot), _capi.stream_ptr(self.device)))
+
+    def debug_linear_lora(self, weight_name: str, x: torch.Tensor, row_slots: Sequence[int], path: str = "plain") -> dict:
+        """`debug_linear` on an adapter handle (tests; `mmi_lm_debug_linear_lora`): the shrink launch plus the GEMM of that linear as
+        the step runs them, row b on adapter slot `row_slots[b]` (-1 = none).  Paths "plain" and "splitk"."""
+        x = x.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        rows, K = x.shape
+        assert K == self._linear_in_features(weight_name), f"{weight_name} takes rows of {self._linear_in_features(weight_name)} features, got {K}"
+        assert len(row_slots) == rows, "one adapter slot per row"
+        out = torch.empty(rows, self._linear_out_features(weight_name), dtype=torch.bfloat16, device=self.device)
+        slots = (C.c_int32 * rows)(*[int(v) for v in row_slots])
+        self._lib.check(self._lib.mmi_lm_debug_linear_lora(self._handle, weight_name.encode(), None, self.DEBUG_PATHS[path], x.data_ptr(), rows,
+                                                           out.data_ptr(), None, None, None, slots, _capi.stream_ptr(self.device)))
+        return {"out": out}
 
     def enable_hidden_taps(self, on: bool = True) -> None:
         """Parity tap (tests): every step of the NEXT `LMGen.streaming()` also keeps the residual stream after the first and
@@ -682,6 +724,20 @@ class LMGen:
                 rc.cross_len = int(cx.shape[1])
         self._lib.check(self._lib.mmi_lm_set_row_condition(lm._handle, int(session), C.byref(rc), self._stream()))
         self._cond_keep.append(keep)         # alive until the next step has been enqueued behind the call
+
+    # ---- per-session adapters (mmi_lm_set_row_adapter) ------------------------------------------------
+    def set_session_adapter(self, session: int, slot: Optional[int]) -> None:
+        """Session `session` (both model rows of a guided one) runs on adapter `slot` of `LMModel(adapters=...)` from the next step
+        on; None = the base model alone.  Stream-ordered; the launch list and a captured step graph stay as they are, and no other
+        session changes.  `reset_streaming` keeps it; `streaming()` starts every session without an adapter."""
+        assert self.is_streaming
+        self._lib.check(self._lib.mmi_lm_set_row_adapter(self.lm_model._handle, int(session), -1 if slot is None else int(slot), self._stream()))
+
+    def session_adapter(self, session: int) -> Optional[int]:
+        """The adapter slot session `session` runs on, or None."""
+        assert self.is_streaming
+        slot = int(self._lib.mmi_lm_row_adapter(self.lm_model._handle, int(session)))
+        return None if slot < 0 else slot
 
     # ---- per-session TTS scripts (mmi_lm_set_row_script) ---------------------------------------------
     def set_session_script(self, session: int, script: Optional[TTSScript]) -> None:

@@ -152,11 +152,12 @@ def get_condition_fuser(cfg: dict) -> ConditionFuser:    # loaders.py:476-483
 def get_moshi_lm(filename: str | Path | None, lm_kwargs: Optional[Dict[str, Any]] = None, device: torch.device | str = "cuda",
                  dtype: torch.dtype = torch.bfloat16, lora_weights: str | Path | None = None, fuse_lora: bool = False,
                  lm_kwargs_overrides: Optional[dict] = None, max_batch: int = 32, lib=None, state_patch=None,
-                 quantize: Optional[bool | str] = None, max_rows: Optional[int] = None) -> LMModel:
+                 quantize: Optional[bool | str] = None, max_rows: Optional[int] = None, adapters=None) -> LMModel:
     """loaders.get_moshi_lm (loaders.py:366-446): bf16 weights; `quantize` in the config (a `.q8` checkpoint carrying int8
     `weight` + `weight_scb`, fp8 `weight` + `weight_scale`, or MXFP4 `weight` + `weight_scale_e8m0`) is taken from the tensors
     themselves; `quantize="mxfp4"` converts a bf16 checkpoint at load.  `max_rows`: a handle of
-    up to 128 model rows instead of `max_batch` sessions (LMModel)."""
+    up to 128 model rows instead of `max_batch` sessions (LMModel).  `adapters=(max_adapters, max_rank)`: room for LoRA adapters
+    next to the base, chosen per session (`load_lora_adapter`); `lora_weights=` keeps merging one adapter at load."""
     assert dtype == torch.bfloat16, "the engine computes the LM in bf16 (fp32 accumulation), like the reference's default"
     kw = dict(lm_kwargs) if lm_kwargs is not None else None
     if kw is not None:
@@ -165,6 +166,7 @@ def get_moshi_lm(filename: str | Path | None, lm_kwargs: Optional[Dict[str, Any]
         lora = kw.pop("lora", False)
         kw.pop("lora_rank", None)
         lora_scaling = kw.pop("lora_scaling", 2.0)
+        cfg_lora_scaling = float(lora_scaling)
         if lora_weights is not None and not lora:
             raise AssertionError("`lora` is False, but received some lora_weights to load.")     # loaders.py:442-445
         if lora and kw.get("quantize"):
@@ -173,7 +175,7 @@ def get_moshi_lm(filename: str | Path | None, lm_kwargs: Optional[Dict[str, Any]
             raise NotImplementedError("condition providers (text / tensor conditioners) run outside the engine: pass their "
                                       "output as LMGen(condition_tensors=...)")
     if kw is None:
-        lora, lora_scaling = False, 2.0
+        lora, lora_scaling, cfg_lora_scaling = False, 2.0, 2.0
         if lora_weights is not None:
             raise AssertionError("`lora` is False, but received some lora_weights to load.")
     fuser = get_condition_fuser(kw) if kw is not None and kw.get("fuser") is not None else None
@@ -189,7 +191,7 @@ def get_moshi_lm(filename: str | Path | None, lm_kwargs: Optional[Dict[str, Any]
         state = _load_state(filename, ("fsdp_best_state", "model"))
         state = {k: v for k, v in state.items() if not (k.startswith("condition_provider.") or k.startswith("fuser."))}
     if kw is not None and lora and lora_weights is not None:
-        # loaders.py:486-516: the adapter is merged into the base weights (the engine has no unfused LoRA path)
+        # loaders.py:486-516: this adapter is merged into the base weights (unmerged, per session: `adapters=` / load_lora_adapter)
         assert _is_safetensors(lora_weights), "LoRA weights must be a safetensors file."
         from .weights import fuse_lora_state_dict, normalize_lm_state_dict
         state = fuse_lora_state_dict(normalize_lm_state_dict(state, cfg), _load_state(lora_weights), float(lora_scaling))
@@ -197,8 +199,19 @@ def get_moshi_lm(filename: str | Path | None, lm_kwargs: Optional[Dict[str, Any]
         state_patch(state)
     from .weights import is_mxfp4_state_dict
     already = any(v.dtype in (torch.int8, torch.float8_e4m3fn) for v in state.values()) or is_mxfp4_state_dict(state)
-    return LMModel(state, cfg, device=device, max_batch=max_batch, lib=lib, quantize=False if already else quantize, fuser=fuser,
-                   max_rows=max_rows)
+    lm = LMModel(state, cfg, device=device, max_batch=max_batch, lib=lib, quantize=False if already else quantize, fuser=fuser,
+                 max_rows=max_rows, adapters=adapters)
+    lm.lora_scaling = cfg_lora_scaling                  # the config's `lora_scaling`: load_lora_adapter's default
+    return lm
+
+
+def load_lora_adapter(lm: LMModel, slot: int, path: str | Path, scaling: Optional[float] = None) -> None:
+    """A reference LoRA checkpoint (safetensors, loaders.py:486-516) into adapter `slot` of `get_moshi_lm(..., adapters=...)`, run
+    unmerged for the sessions that select it.  `scaling` defaults to the config's `lora_scaling`."""
+    assert _is_safetensors(path), "LoRA weights must be a safetensors file."
+    if scaling is None:
+        scaling = getattr(lm, "lora_scaling", 2.0)
+    lm.load_adapter(int(slot), _load_state(path), float(scaling))
 
 
 def lm_size_kwargs(slots: int, rows_per_session: int = 1) -> Dict[str, int]:

@@ -10,6 +10,10 @@
 // `native_selftest <dir> --rows 65,128`: the LM alone on handles of that many model rows (mmi_lm_create_rows, the many-row GEMM): row r
 // replays the fixture's session r % B against the same recorded values, and a snapshot taken mid-stream resumes bit for bit.
 //
+// `native_selftest <dir> --adapters`: the LM alone on an adapter handle (mmi_lm_enable_adapters): enable, load an adapter
+// this program generates, every row without an adapter against the recorded values, one row on the adapter (it alone changes),
+// the refusals while the row is live, unload, destroy.
+//
 // The same source builds against the CPU simulator (-DMMI_SELFTEST_SIM, tests/test_native_selftest.py), which is how the expected
 // values and this program are checked where there is no GPU.  The checker side (oracle) never runs here: only its recorded output.
 //
@@ -21,7 +25,8 @@
 //         moshi_amd/csrc/{api_common,mimi_engine,lm_engine,batcher,duplex}.hip tests/hipsim/hipsim.cpp scripts/native_selftest.cpp \
 //         -o build/native_selftest_san
 //   export MMI_NO_GRAPH=1 ASAN_OPTIONS=detect_leaks=0:detect_stack_use_after_return=0 UBSAN_OPTIONS=print_stacktrace=1
-//   build/native_selftest_san tests/golden/native_selftest && build/native_selftest_san tests/golden/native_selftest --rows 65,128
+//   build/native_selftest_san tests/golden/native_selftest && build/native_selftest_san tests/golden/native_selftest --rows 65,128 &&
+//   build/native_selftest_san tests/golden/native_selftest --adapters
 #include "moshi_mi.h"
 #ifdef MMI_SELFTEST_SIM
 #include "hipsim.h"
@@ -61,6 +66,8 @@ int main(int argc, char** argv) {
     for (int i = 1; i + 1 < argc; ++i)
         if (!strcmp(argv[i], "--rows"))
             for (const char* q = argv[i + 1]; *q; q = strchr(q, ',') ? strchr(q, ',') + 1 : q + strlen(q)) many_rows.push_back(atoi(q));
+    bool adapters = false;
+    for (int i = 1; i < argc; ++i) adapters |= !strcmp(argv[i], "--adapters");
     FILE* mf = fopen((dir + "/manifest.txt").c_str(), "r");
     if (!mf) { printf("cannot open %s/manifest.txt\n", dir.c_str()); return 2; }
     mmi_mimi_cfg mc; mmi_lm_cfg lc;
@@ -132,7 +139,7 @@ int main(int argc, char** argv) {
     int failures = 0;
 
     // ---- Mimi: encode FR frames, decode the oracle's codes
-    if (many_rows.empty()) {
+    if (many_rows.empty() && !adapters) {
         mmi_mimi* m = nullptr;
         MCK(mmi_mimi_create(&mc, md.data(), (int32_t)md.size(), B, &m));
         MCK(mmi_mimi_set_num_codebooks(m, K));
@@ -171,7 +178,7 @@ int main(int argc, char** argv) {
         mmi_mimi_destroy(m);
     }
     // ---- LM: greedy steps, teacher-forced with the oracle's tokens
-    if (many_rows.empty()) {
+    if (many_rows.empty() && !adapters) {
         mmi_lm* lm = nullptr;
         MCK(mmi_lm_create(&lc, ld.data(), (int32_t)ld.size(), B, &lm));
         mmi_sampling sp; memset(&sp, 0, sizeof(sp));
@@ -286,6 +293,97 @@ int main(int argc, char** argv) {
         MCK(mmi_lm_streaming_stop(lm));
         mmi_lm_destroy(lm);
         hipFree(duc); hipFree(dforced); hipFree(dout); hipFree(dtl); hipFree(dal); hipFree(dsnap);
+    }
+    if (adapters) {
+        // every nn.Linear of the LM (the set the reference's replace_all_linear_with_lora wraps) gets lora_A [8, in], lora_B [out, 8]
+        const int rank = 8;
+        std::vector<std::string> names; std::vector<void*> bufs; std::vector<mmi_tensor_desc> ad;
+        for (auto& t : tensors) {
+            const std::string& n = t.name;
+            const bool lin = t.model != "mimi" && t.ndim == 2 && n.size() > 7 && n.compare(n.size() - 7, 7, ".weight") == 0 &&
+                             (n.find(".self_attn.in_projs.") != std::string::npos || n.find(".self_attn.out_projs.") != std::string::npos ||
+                              n.find(".linear_in.weight") != std::string::npos || n.find(".linear_out.weight") != std::string::npos ||
+                              n.compare(0, 13, "depformer_in.") == 0 || n.compare(0, 8, "linears.") == 0 || n == "text_linear.weight");
+            if (!lin) continue;
+            const std::string stem = n.substr(0, n.size() - 7);
+            for (int which = 0; which < 2; ++which) {
+                const long rows = which ? t.d[0] : rank, cols = which ? rank : t.d[1];
+                std::vector<uint16_t> h((size_t)rows * cols);
+                for (size_t i = 0; i < h.size(); ++i) h[i] = bf16_rne((which ? 0.25f : 2.0f / sqrtf((float)cols)) * u_of(t.seed + 17u + which, (uint32_t)i));
+                void* dev; HCK(hipMalloc(&dev, h.size() * 2)); HCK(hipMemcpy(dev, h.data(), h.size() * 2, hipMemcpyHostToDevice));
+                names.push_back(stem + (which ? ".lora_B.weight" : ".lora_A.weight")); bufs.push_back(dev);
+                mmi_tensor_desc d; memset(&d, 0, sizeof(d));
+                d.data = dev; d.dtype = MMI_BF16; d.ndim = 2; d.shape[0] = rows; d.shape[1] = cols;
+                ad.push_back(d);
+            }
+        }
+        for (size_t i = 0; i < ad.size(); ++i) ad[i].name = names[i].c_str();
+        mmi_lm* lm = nullptr;
+        MCK(mmi_lm_create(&lc, ld.data(), (int32_t)ld.size(), B, &lm));
+        MCK(mmi_lm_enable_adapters(lm, 2, 32));
+        MCK(mmi_lm_load_adapter(lm, 1, 2.0f, ad.data(), (int32_t)ad.size(), nullptr));
+        mmi_sampling sp; memset(&sp, 0, sizeof(sp));
+        sp.use_sampling = 0; sp.temp = 0.8f; sp.temp_text = 0.7f; sp.top_k = 250; sp.top_k_text = 25; sp.seed = 0;
+        const int NT = dep_q + 1;
+        const int64_t* eforced = (const int64_t*)expect("lm_forced");
+        const int64_t* eout = (const int64_t*)expect("lm_out");
+        const float* etl = (const float*)expect("lm_text_logits");
+        int64_t *duc, *dforced, *dout; float *dtl, *dal;
+        HCK(hipMalloc((void**)&duc, (size_t)B * n_user * 8)); HCK(hipMalloc((void**)&dforced, (size_t)B * NT * 8));
+        HCK(hipMalloc((void**)&dout, (size_t)B * NT * 8));
+        HCK(hipMalloc((void**)&dtl, (size_t)B * text_card * 4)); HCK(hipMalloc((void**)&dal, (size_t)B * dep_q * card * 4));
+        std::vector<std::vector<float>> tls[2];
+        long tok_diffs = 0; double worst_max = 0;
+        int refused = 0;
+        for (int pass = 0; pass < 2; ++pass) {            // pass 0: every row at -1; pass 1: row 0 on slot 1
+            MCK(mmi_lm_streaming_start(lm, B, &sp, nullptr));
+            if (pass) {
+                MCK(mmi_lm_set_row_adapter(lm, 0, 1, nullptr));
+                refused += mmi_lm_unload_adapter(lm, 1, nullptr) == MMI_ERR_STATE;
+                refused += mmi_lm_load_adapter(lm, 1, 2.0f, ad.data(), (int32_t)ad.size(), nullptr) == MMI_ERR_STATE;
+                refused += mmi_lm_row_adapter(lm, 0) == 1 && mmi_lm_row_adapter(lm, B - 1) == (B > 1 ? -1 : 1);
+            }
+            for (int s = 0; s < ST; ++s) {
+                std::vector<int64_t> uc((size_t)B * n_user);
+                for (size_t i = 0; i < uc.size(); ++i) uc[i] = (int64_t)((u_of(9000u + s, (uint32_t)i) + 1.0f) * 32768.0f) % card;
+                HCK(hipMemcpy(duc, uc.data(), uc.size() * 8, hipMemcpyHostToDevice));
+                HCK(hipMemcpy(dforced, eforced + (size_t)s * B * NT, (size_t)B * NT * 8, hipMemcpyHostToDevice));
+                MCK(mmi_lm_force_next_tokens(lm, dforced, nullptr));
+                int32_t valid = 0;
+                MCK(mmi_lm_step(lm, duc, n_user, dout, dtl, dal, nullptr, B, &valid, nullptr));
+                HCK(hipDeviceSynchronize());
+                std::vector<int64_t> o((size_t)B * NT); std::vector<float> tl((size_t)B * text_card);
+                HCK(hipMemcpy(o.data(), dout, o.size() * 8, hipMemcpyDeviceToHost));
+                HCK(hipMemcpy(tl.data(), dtl, tl.size() * 4, hipMemcpyDeviceToHost));
+                if (!pass) {
+                    for (size_t i = 0; i < o.size(); ++i) tok_diffs += o[i] != eout[(size_t)s * B * NT + i];
+                    for (int b = 0; b < B; ++b) {
+                        double mx = 1e-6, dmax = 0;
+                        for (int i = 0; i < text_card; ++i) {
+                            const float r = etl[((size_t)s * B + b) * text_card + i];
+                            mx = fmax(mx, fabs(r)); dmax = fmax(dmax, fabs(tl[(size_t)b * text_card + i] - r));
+                        }
+                        worst_max = fmax(worst_max, dmax / mx);
+                    }
+                }
+                tls[pass].push_back(tl);
+            }
+            if (pass) { MCK(mmi_lm_set_row_adapter(lm, 0, -1, nullptr)); MCK(mmi_lm_unload_adapter(lm, 1, nullptr)); }
+            MCK(mmi_lm_streaming_stop(lm));
+        }
+        long others_changed = 0, row0_changed = 0;
+        for (int s = 0; s < ST; ++s) {
+            row0_changed += memcmp(tls[0][s].data(), tls[1][s].data(), (size_t)text_card * 4) != 0;
+            if (B > 1) others_changed += memcmp(tls[0][s].data() + text_card, tls[1][s].data() + text_card, (size_t)(B - 1) * text_card * 4) != 0;
+        }
+        printf("lm with adapters: rows at -1: %ld of %d token-ring outputs differ from the oracle (must be 0), text logits worst max %.4f (<= 0.05); "
+               "row 0 on slot 1: its text logits changed in %ld of %d steps (must be all), the other rows' in %ld (must be 0); %d of 3 live-slot checks held\n",
+               tok_diffs, ST * B * NT, worst_max, row0_changed, ST, others_changed, refused);
+        failures += tok_diffs != 0 || !(worst_max <= 0.05) || row0_changed != ST || others_changed != 0 || refused != 3;
+        MCK(mmi_lm_enable_adapters(lm, 0, 0));
+        mmi_lm_destroy(lm);
+        hipFree(duc); hipFree(dforced); hipFree(dout); hipFree(dtl); hipFree(dal);
+        for (void* p : bufs) hipFree(p);
     }
     printf(failures ? "SELFTEST FAILED\n" : "SELFTEST PASSED\n");
     return failures ? 1 : 0;
