@@ -415,6 +415,39 @@ int mmi_lm_set_row_adapter(mmi_lm* lm, int32_t session, int32_t slot_or_minus1, 
 /* The session's slot; -1: none (also without adapters, outside a stream or for a session outside the batch). */
 int32_t mmi_lm_row_adapter(const mmi_lm* lm, int32_t session);
 
+/* ---- nucleus (top-p) sampling, per handle and per session (utils/sampling.py:67-83, 97-98) ----------------------
+ * A sampling site whose effective top_p is p, 0 < p <= 1, draws from the nucleus of its final bf16 logit row (behind the
+ * guidance mix, an on_text_logits hook, the TTS padding bonus, the repetition penalty and the pad bias): with the entries ordered
+ * by (logit descending, index ascending) and P = softmax(logits / temp) in fp32, the entry of rank r is in iff the mass of the
+ * ranks before it is <= p (the reference's `probs_sum - probs_sort > p` mask; equality keeps the entry; rank 0 is always in).
+ * top_p > 0 overrides the site's top_k, as in the reference; greedy rows and rows with temp <= 0 ignore it; p = 1 is the whole
+ * vocabulary; p = 0 is off (exactly the bits of before).  The winner is drawn as the top-k path draws it: member i scores
+ * logit_i / temp - log(-log u_i), u_i from the session's (or the handle's) Philox stream at (step, site, i); the largest score
+ * wins, ties to the lower index - so a nucleus of n <= 256 members yields the token top_k = n yields on the same stream.  The
+ * masses are fp32 sums in a fixed order: the same set on every run.  The set may differ from a sequential fp32 cumsum's only
+ * where a prefix mass lies within summation error of p.
+ *
+ * mmi_lm_enable_nucleus: the next streaming_start builds its launch list on the nucleus forms of the three samplers (any kind of
+ * handle).  MMI_ERR_STATE while streaming, or when turning it off while the handle's top_p is positive.  A handle that never
+ * calls it is unchanged: same launch list, same device code, same mmi_lm_state_bytes.  An enabled stream's snapshot grows by
+ * 8 bytes per session, rounded up to 48. */
+int mmi_lm_enable_nucleus(mmi_lm* lm, int32_t on);
+/* The handle-wide (audio sites, text site) values; they stay until changed and every session of the next streaming_start begins
+ * with them.  MMI_ERR_STATE while streaming, and for a non-zero value on a handle without the nucleus samplers; values outside
+ * [0, 1] or non-finite MMI_ERR_INVALID.  A refused call changes nothing. */
+int mmi_lm_set_top_p(mmi_lm* lm, float top_p, float top_p_text);
+int mmi_lm_top_p(const mmi_lm* lm, float* top_p, float* top_p_text);
+/* 1: the live stream runs the nucleus samplers (not streaming: the next one will); 0: not; a negative status for a NULL handle. */
+int32_t mmi_lm_nucleus_enabled(const mmi_lm* lm);
+/* Session `session` samples with its own (top_p, top_p_text) from the next step on / returns to the handle's.  Stream ordered (the
+ * values travel as kernel arguments), legal between any two steps; neither the launch list nor a captured graph changes.  Under
+ * guidance they address sessions.  Independent of whether the session has an mmi_row_sampling entry.  mmi_lm_reset keeps the
+ * values; a state snapshot carries them.  MMI_ERR_STATE when not streaming or on a stream started without the nucleus samplers;
+ * session outside [0, batch) or a value outside [0, 1] MMI_ERR_INVALID.  While the handle's or any session's value is positive,
+ * mmi_lm_step refuses opt_noise (MMI_ERR_UNSUPPORTED; nothing is enqueued): rank-indexed draws over a nucleus are not built. */
+int mmi_lm_set_row_top_p(mmi_lm* lm, int32_t session, float top_p, float top_p_text, mmi_stream stream);
+int mmi_lm_clear_row_top_p(mmi_lm* lm, int32_t session, mmi_stream stream);
+
 /* The TTS script machine on the device: what TTSModel.generate's three host hooks do on every frame
  * (models/tts.py:553-583) - StateMachine.process per row (tts.py:160-252), the zeroed / prefixed audio codebooks, the padding
  * bonus - as part of the launch list, so that a TTS step stays one captured graph.  The fields are StateMachine's and
@@ -713,6 +746,10 @@ int mmi_batcher_open_cond(mmi_batcher* b, const mmi_row_sampling* settings_or_nu
  * refused here with the same status, and no slot is claimed. */
 int mmi_batcher_open_lora(mmi_batcher* b, const mmi_row_sampling* settings_or_null, const mmi_batcher_condition* cond_or_null,
                           int32_t adapter_slot, int64_t* channel_id);
+/* The channel's row samples with its own (top_p, top_p_text) from the next step on, for the channel's life (a batcher on a handle
+ * with mmi_lm_enable_nucleus before mmi_batcher_create); the row returns to the handle's values at the step after the close, as an
+ * adapter slot does.  What mmi_lm_set_row_top_p would refuse is refused here with the same status. */
+int mmi_batcher_set_channel_top_p(mmi_batcher* b, int64_t channel_id, float top_p, float top_p_text);
 int mmi_batcher_close(mmi_batcher* b, int64_t channel_id);
 /* Append 24 kHz mono PCM (host f32) to the channel's FIFO (batched_asr.rs:77-90 extend_data). */
 int mmi_batcher_push_pcm(mmi_batcher* b, int64_t channel_id, const float* pcm, int32_t n_samples);

@@ -210,6 +210,13 @@ SIGNATURES = {
     "mmi_lm_set_row_adapter": (C.c_int, [_P, C.c_int32, C.c_int32, _P]),
     "mmi_lm_row_adapter": (C.c_int32, [_P, C.c_int32]),
     "mmi_batcher_open_lora": (C.c_int, [_P, C.POINTER(RowSampling), C.POINTER(BatcherCondition), C.c_int32, C.POINTER(C.c_int64)]),
+    "mmi_lm_enable_nucleus": (C.c_int, [_P, C.c_int32]),
+    "mmi_lm_set_top_p": (C.c_int, [_P, C.c_float, C.c_float]),
+    "mmi_lm_top_p": (C.c_int, [_P, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "mmi_lm_nucleus_enabled": (C.c_int32, [_P]),
+    "mmi_lm_set_row_top_p": (C.c_int, [_P, C.c_int32, C.c_float, C.c_float, _P]),
+    "mmi_lm_clear_row_top_p": (C.c_int, [_P, C.c_int32, _P]),
+    "mmi_batcher_set_channel_top_p": (C.c_int, [_P, C.c_int64, C.c_float, C.c_float]),
     "mmi_lm_launch_list": (C.c_int64, [_P, _P, C.c_int64]),
     "mmi_mimi_launch_list": (C.c_int64, [_P, C.c_int32, _P, C.c_int64]),
     "mmi_lm_seek": (C.c_int, [_P, _P, _P]),
@@ -227,10 +234,13 @@ _SINCE_TTS_MACHINE = ("mmi_lm_enable_tts_machine", "mmi_lm_set_row_script", "mmi
 _SINCE_MANY_ROWS = ("mmi_lm_create_rows",)
 _SINCE_ADAPTERS = ("mmi_lm_debug_linear_lora", "mmi_lm_enable_adapters", "mmi_lm_load_adapter", "mmi_lm_unload_adapter",
                    "mmi_lm_set_row_adapter", "mmi_lm_row_adapter", "mmi_batcher_open_lora")
+_SINCE_NUCLEUS = ("mmi_lm_enable_nucleus", "mmi_lm_set_top_p", "mmi_lm_top_p", "mmi_lm_nucleus_enabled", "mmi_lm_set_row_top_p",
+                  "mmi_lm_clear_row_top_p", "mmi_batcher_set_channel_top_p")
 
 
 def _missing(name, path):
-    what = ("per-session adapters" if name in _SINCE_ADAPTERS else
+    what = ("nucleus sampling" if name in _SINCE_NUCLEUS else
+            "per-session adapters" if name in _SINCE_ADAPTERS else
             "handles above 64 model rows" if name in _SINCE_MANY_ROWS else
             "the TTS script machine" if name in _SINCE_TTS_MACHINE else
             "per-session conditions" if name in _SINCE_ROW_CONDITION else "per-session sampling")
@@ -247,7 +257,7 @@ class Lib:
         self.path = Path(path)
         self.cdll = C.CDLL(str(self.path))
         for name, (res, args) in SIGNATURES.items():
-            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION + _SINCE_TTS_MACHINE + _SINCE_MANY_ROWS + _SINCE_ADAPTERS and not hasattr(self.cdll, name):
+            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION + _SINCE_TTS_MACHINE + _SINCE_MANY_ROWS + _SINCE_ADAPTERS + _SINCE_NUCLEUS and not hasattr(self.cdll, name):
                 # an older build of the engine (MMI_LIB_PATH, A/B runs against a parent build): everything else works, these refuse
                 setattr(self, name, _missing(name, self.path))
                 continue

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _capi
 from .errors import UnknownChannel  # noqa: F401  (re-exported: callers catch it from here)
-from .lm import LMModel
+from .lm import LMModel, _apply_nucleus, check_top_p
 from .mimi import MimiModel
 
 
@@ -37,7 +37,8 @@ class SessionBatcher:
     def __init__(self, mimi: MimiModel, lm_model: LMModel, slots: int, use_sampling: bool = True, temp: float = 0.8,
                  temp_text: float = 0.7, top_k: int = 250, top_k_text: int = 25, seed: int = 0,
                  reset_codec_after_first_frame: bool = True, max_buffered_frames: int = 250, cfg_coef: float = 1.0,
-                 cfg_is_no_text: bool = False, cfg_is_masked_until=None, condition_tensors=None):
+                 cfg_is_no_text: bool = False, cfg_is_masked_until=None, condition_tensors=None, top_p: float = 0.0,
+                 top_p_text: float = 0.0, session_top_p: bool = False):
         assert mimi._lib is lm_model._lib, "both models must live in the same engine library"
         assert not mimi.is_streaming, "the batcher puts the models into streaming mode itself"
         _require_duplex_model(lm_model.config, "SessionBatcher")
@@ -82,8 +83,16 @@ class SessionBatcher:
                 cfg.guidance.cross_len = int(cx.shape[1])
         assert mimi.device == lm_model.device, "the codec and the LM of a batcher must live on the same GPU"
         self._handle = C.c_void_p()
+        # nucleus sampling: the batcher's own values, and whether channels may bring theirs (SessionSampling.top_p, set_channel_top_p)
+        check_top_p(top_p, top_p_text)
+        self._nucleus = _apply_nucleus(self._lib, lm_model._handle, float(top_p), float(top_p_text), bool(session_top_p))
         mimi._sync()
         self._lib.check(self._lib.mmi_batcher_create(mimi._handle, lm_model._handle, C.byref(cfg), C.byref(self._handle)))
+
+    @property
+    def nucleus(self) -> bool:
+        """Whether the batcher's stream runs the nucleus samplers, i.e. whether channels may bring their own top_p."""
+        return self._nucleus
 
     def close_all(self) -> None:
         """Tear the batcher down (both models leave streaming mode)."""
@@ -112,6 +121,11 @@ class SessionBatcher:
         batcher's own condition for that slot.  `adapter`: the slot of `LMModel(adapters=...)` the channel runs on for its life
         (`close` returns the row to the base model); None = no adapter.  What the engine refuses raises here and claims no slot."""
         ch = C.c_int64(0)
+        own_p = sampling is not None and (sampling.top_p > 0 or sampling.top_p_text > 0)
+        if sampling is not None:
+            check_top_p(sampling.top_p, sampling.top_p_text)
+        if own_p and not self._nucleus:
+            raise RuntimeError("SessionSampling.top_p > 0 needs a batcher with the nucleus samplers: SessionBatcher(session_top_p=True)")
         if adapter is not None and condition is None:
             sp = C.byref(sampling.to_c()) if sampling is not None else None
             self._lib.check(self._lib.mmi_batcher_open_lora(self._handle, sp, None, int(adapter), C.byref(ch)))
@@ -146,7 +160,18 @@ class SessionBatcher:
                 self._lib.check(self._lib.mmi_batcher_open_lora(self._handle, sp, C.byref(bc), int(adapter), C.byref(ch)))
             else:
                 self._lib.check(self._lib.mmi_batcher_open_cond(self._handle, sp, C.byref(bc), C.byref(ch)))
+        if sampling is not None and self._nucleus:      # the channel's own nucleus values (0 = off for it), before its first step
+            try:
+                self.set_channel_top_p(int(ch.value), sampling.top_p, sampling.top_p_text)
+            except BaseException:
+                self._lib.mmi_batcher_close(self._handle, int(ch.value))     # a refused nucleus part leaves no channel open
+                raise
         return int(ch.value)
+
+    def set_channel_top_p(self, channel: int, top_p: float, top_p_text: float) -> None:
+        """The channel samples with its own nucleus values from the next step on, for its life; `close` returns the row to the
+        batcher's values at the following step."""
+        self._lib.check(self._lib.mmi_batcher_set_channel_top_p(self._handle, int(channel), float(top_p), float(top_p_text)))
 
     def close(self, channel: int) -> None:
         self._lib.check(self._lib.mmi_batcher_close(self._handle, int(channel)))

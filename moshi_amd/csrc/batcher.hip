@@ -33,6 +33,8 @@ struct Channel {                 // batched_asr.rs:61-69
     int cross_len = 0;
     std::vector<uint16_t> cond_sum, cond_cross;   // bf16 [R][dim] / [R][cross_len][dim], copied at open; empty = keep
     int adapter = -1;            // mmi_batcher_open_lora: the row runs on this adapter slot for the channel's life
+    bool own_top_p = false, top_p_dirty = false;   // mmi_batcher_set_channel_top_p: the row samples with these for the channel's life
+    float top_p = 0.f, top_p_text = 0.f;
     long frames = 0;             // input frames consumed
     std::deque<float> in;        // PCM FIFO
     std::deque<OutFrame> out;
@@ -122,6 +124,9 @@ struct mmi_batcher {
     std::vector<CondPlan> cond_plan;
     std::vector<uint8_t> row_has_cond;   // the slot's rows currently hold a channel's own condition
     std::vector<int> row_adapter, adapter_plan;   // the adapter slot each row holds / takes at this step (-2: stays as it is)
+    std::vector<uint8_t> row_has_top_p;  // the row currently holds a channel's own top_p
+    struct TopPPlan { int what; float top_p, top_p_text; };   // what: 0 nothing, 1 the channel's values, 2 the handle's again
+    std::vector<TopPPlan> top_p_plan;
     int64_t next_id = 1;
     mmi_batcher_stats stats;
 };
@@ -218,6 +223,8 @@ int create_impl(mmi_batcher* b) {
     b->row_has_cond.assign(B, 0);
     b->row_adapter.assign(B, -1);
     b->adapter_plan.assign(B, -2);
+    b->row_has_top_p.assign(B, 0);
+    b->top_p_plan.assign(B, mmi_batcher::TopPPlan{0, 0.f, 0.f});
     if (b->has_sum || b->has_cross) {
         const size_t bytes = (size_t)B * b->cond_slot * sizeof(uint16_t), D = (size_t)b->dim;
         MMI_HIP_CHECK(hipHostMalloc((void**)&b->h_cond, bytes, 0));
@@ -329,6 +336,24 @@ extern "C" int mmi_batcher_open_lora(mmi_batcher* b, const mmi_row_sampling* set
     return mmi_fail(MMI_ERR_BUSY, "no free slot");   // py_module.rs:443-470: `channels()` yields None
 }
 
+int32_t mmi_lm_nucleus_enabled(const mmi_lm* lm);
+
+extern "C" int mmi_batcher_set_channel_top_p(mmi_batcher* b, int64_t channel_id, float top_p, float top_p_text) {
+    MmiDeviceGuard dev_guard_(b ? mmi_lm_device(b->lm) : -1);
+    if (!b) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    // what mmi_lm_set_row_top_p would refuse at the step, refused now
+    if (mmi_lm_nucleus_enabled(b->lm) <= 0) return mmi_fail(MMI_ERR_STATE, "the stream was started without the nucleus samplers (mmi_lm_enable_nucleus before mmi_batcher_create)");
+    for (float v : {top_p, top_p_text})
+        if (!std::isfinite(v) || v < 0.f || v > 1.f) return mmi_fail(MMI_ERR_INVALID, "top_p and top_p_text must lie in [0, 1] (0 = off)");
+    std::lock_guard<std::mutex> g(b->mu);
+    Channel* c = find_channel(b, channel_id);
+    if (!c) return mmi_fail(MMI_ERR_NO_CHANNEL, "unknown channel");
+    c->own_top_p = c->top_p_dirty = true;
+    c->top_p = top_p;
+    c->top_p_text = top_p_text;
+    return MMI_OK;
+}
+
 extern "C" int mmi_batcher_close(mmi_batcher* b, int64_t channel_id) {
     MmiDeviceGuard dev_guard_(b ? mmi_lm_device(b->lm) : -1);
     if (!b) return mmi_fail(MMI_ERR_INVALID, "null handle");
@@ -358,7 +383,7 @@ extern "C" int mmi_batcher_step(mmi_batcher* b, int32_t* n_active) {
     const int B = b->B, F = b->F;
     Staging& h = b->host;
     Staging& d = b->dev;
-    int active = 0, resets = 0, firsts = 0, sets = 0, adapts = 0;
+    int active = 0, resets = 0, firsts = 0, sets = 0, adapts = 0, tops = 0;
     {   // ---- pre_process (batched_asr.rs:279-374)
         std::lock_guard<std::mutex> g(b->mu);
         for (int r = 0; r < B; ++r) {
@@ -370,6 +395,13 @@ extern "C" int mmi_batcher_step(mmi_batcher* b, int32_t* n_active) {
                 const int want = c.live ? c.adapter : -1;
                 b->adapter_plan[r] = want != b->row_adapter[r] ? want : -2;
                 if (b->adapter_plan[r] != -2) ++adapts;
+            }
+            {   // and so does its top_p: the owner's for the channel's life, the handle's again at the step after close
+                mmi_batcher::TopPPlan& tp = b->top_p_plan[r];
+                tp.what = 0;
+                if (c.live && c.own_top_p && c.top_p_dirty) tp = mmi_batcher::TopPPlan{1, c.top_p, c.top_p_text};
+                else if (!(c.live && c.own_top_p) && b->row_has_top_p[r]) tp.what = 2;
+                if (tp.what) ++tops;
             }
             if (c.live && c.pending_reset) {
                 h.reset[r] = 1;
@@ -407,7 +439,7 @@ extern "C" int mmi_batcher_step(mmi_batcher* b, int32_t* n_active) {
         }
     }
     if (n_active) *n_active = active;
-    if (active == 0 && resets == 0 && adapts == 0) return MMI_OK;
+    if (active == 0 && resets == 0 && adapts == 0 && tops == 0) return MMI_OK;
     hipStream_t s = b->stream;
     int rc;
     MMI_HIP_CHECK(hipEventRecord(b->ev_begin, s));
@@ -416,6 +448,17 @@ extern "C" int mmi_batcher_step(mmi_batcher* b, int32_t* n_active) {
         if (b->adapter_plan[r] == -2) continue;
         if ((rc = mmi_lm_set_row_adapter(b->lm, r, b->adapter_plan[r], s))) return rc;
         b->row_adapter[r] = b->adapter_plan[r];
+    }
+    for (int r = 0; tops && r < B; ++r) {
+        const mmi_batcher::TopPPlan& tp = b->top_p_plan[r];
+        if (!tp.what) continue;
+        if ((rc = tp.what == 1 ? mmi_lm_set_row_top_p(b->lm, r, tp.top_p, tp.top_p_text, s) : mmi_lm_clear_row_top_p(b->lm, r, s))) return rc;
+        b->row_has_top_p[r] = tp.what == 1 ? 1 : 0;
+        if (tp.what == 1) {
+            std::lock_guard<std::mutex> g(b->mu);
+            Channel& c = b->channels[r];
+            if (c.live && c.id == b->row_owner[r] && c.top_p == tp.top_p && c.top_p_text == tp.top_p_text) c.top_p_dirty = false;
+        }
     }
     if (resets) {   // handle_chat: mimi.reset_streaming(); lm_gen.reset_streaming() (server.py:163-164), for the new rows only
         if ((rc = mmi_mimi_reset(b->mimi, d.reset, s))) return rc;

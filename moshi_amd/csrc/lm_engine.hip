@@ -150,7 +150,12 @@ struct mmi_lm {
     RowSamp* rowtab = nullptr;                      // [gen_batch]
     int* thist = nullptr;                           // [gen_batch][MMI_TEXT_HIST]
     std::vector<uint8_t> row_active;
-    int text_eop = 0;                               // LMModel.end_of_text_padding_id (mmi_lm_set_text_end_padding_id)
+    // nucleus sampling (mmi_lm_enable_nucleus): the handle's values, whether this stream runs k_sample_nucleus, and
+    // the host's mirror of the sessions' effective values behind rowtab (supplied noise is refused while any is positive)
+    bool nucleus_on = false, nucleus_live = false;
+    float top_p = 0.f, top_p_text = 0.f;
+    std::vector<RowTopP> row_top_p;
+    int text_eop = 0;                              // LMModel.end_of_text_padding_id (mmi_lm_set_text_end_padding_id)
     // per-step host hooks (mmi_lm_set_hooks): the step is cut at these ops of the launch list
     mmi_lm_hooks hooks{nullptr, nullptr, nullptr, nullptr};
     bool in_hook = false;
@@ -1048,6 +1053,16 @@ void add_sample(mmi_lm* lm, uint16_t* logits, int ld, int V, bool text, int site
         lm->op_after_text_sample = lm->op_text_sample + 1;
         lm->text_sample_args = sa;
     }
+    if (lm->nucleus_on) {           // the nucleus forms of the same three geometries (mmi_lm_enable_nucleus)
+        lm->prog.add([=](hipStream_t s) {
+            if (V <= 2048) MMI_LAUNCH((k_sample_nucleus<256, 8>), B, 256, 0, s, sa);
+            else if (V <= 8192) MMI_LAUNCH((k_sample_nucleus<1024, 8>), B, 1024, 0, s, sa);
+            else MMI_LAUNCH((k_sample_nucleus<1024, 32>), B, 1024, 0, s, sa);
+            MMI_CHECK_LAUNCH();
+            return (int)MMI_OK;
+        });
+        return;
+    }
     lm->prog.add([=](hipStream_t s) {
         if (V <= 2048) MMI_LAUNCH((k_sample<256, 8, true>), B, 256, 0, s, sa);
         else if (V <= 8192) MMI_LAUNCH((k_sample<1024, 8, true>), B, 1024, 0, s, sa);
@@ -1922,7 +1937,10 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
     ok &= hipSuccess == A.alloc(&lm->forced, (size_t)G * (1 + c.dep_q));
     ok &= hipSuccess == A.alloc(&lm->use_forced, (size_t)1);
     ok &= hipSuccess == A.alloc(&lm->rng, (size_t)2);
-    ok &= hipSuccess == A.alloc(&lm->rowtab, (size_t)G);
+    // the nucleus table rides behind the row table (k_sample_nucleus finds it at rows + G): whole RowSamp entries, so that the
+    // snapshot of a stream without the nucleus kernels keeps its size
+    const size_t top_p_entries = lm->nucleus_on ? ((size_t)G * sizeof(RowTopP) + sizeof(RowSamp) - 1) / sizeof(RowSamp) : 0;
+    ok &= hipSuccess == A.alloc(&lm->rowtab, (size_t)G + top_p_entries);
     ok &= hipSuccess == A.alloc(&lm->thist, (size_t)G * MMI_TEXT_HIST);
     lm->tts = nullptr;
     lm->tts_stride = 0;
@@ -1964,7 +1982,11 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
     lm->noise_on = false;
     MMI_HIP_CHECK(hipMemsetAsync(lm->use_forced, 0, sizeof(int), s));
     lm->forced_armed = false;
-    MMI_HIP_CHECK(hipMemsetAsync(lm->rowtab, 0, (size_t)G * sizeof(RowSamp), s));          // every row inactive
+    MMI_HIP_CHECK(hipMemsetAsync(lm->rowtab, 0, ((size_t)G + top_p_entries) * sizeof(RowSamp), s));   // every row inactive
+    lm->nucleus_live = lm->nucleus_on;
+    lm->row_top_p.assign(lm->nucleus_live ? G : 0, RowTopP{lm->top_p, lm->top_p_text});   // every session starts with the handle's values
+    if (lm->nucleus_live)
+        MMI_HIP_CHECK(hipMemcpyAsync(lm->rowtab + G, lm->row_top_p.data(), (size_t)G * sizeof(RowTopP), hipMemcpyHostToDevice, s));
     MMI_HIP_CHECK(hipMemsetAsync(lm->thist, 0, (size_t)G * MMI_TEXT_HIST * sizeof(int), s));
     lm->row_active.assign(G, 0);
     if (lm->tts) {          // no session has a script: every header word 0
@@ -2043,6 +2065,8 @@ extern "C" int mmi_lm_streaming_stop(mmi_lm* lm) {
     lm->row_slot = nullptr;
     lm->lora_t = nullptr;
     lm->row_slot_h.clear();
+    lm->row_top_p.clear();
+    lm->nucleus_live = false;
     if (lm->tts_stage) { hipHostFree(lm->tts_stage); lm->tts_stage = nullptr; }
     for (hipEvent_t e : lm->tts_stage_ev) if (e) hipEventDestroy(e);
     lm->tts_stage_ev.clear();
@@ -2441,6 +2465,73 @@ extern "C" int mmi_lm_set_text_end_padding_id(mmi_lm* lm, int32_t id) {
     return MMI_OK;
 }
 
+// ---- nucleus (top-p) sampling, DESIGN.md 8.17 ---------------------------------------------------------------------------------
+static int top_p_check(float top_p, float top_p_text) {
+    for (float v : {top_p, top_p_text})
+        if (!std::isfinite(v) || v < 0.f || v > 1.f) return mmi_fail(MMI_ERR_INVALID, "top_p and top_p_text must lie in [0, 1] (0 = off)");
+    return MMI_OK;
+}
+
+extern "C" int mmi_lm_enable_nucleus(mmi_lm* lm, int32_t on) {
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (lm->streaming) return mmi_fail(MMI_ERR_STATE, "the nucleus samplers are part of the step's launch list: enable them before streaming_start");
+    if (!on && (lm->top_p > 0.f || lm->top_p_text > 0.f))
+        return mmi_fail(MMI_ERR_STATE, "the handle's top_p is positive: set it to 0 (mmi_lm_set_top_p) before disabling the nucleus samplers");
+    lm->nucleus_on = on != 0;
+    return MMI_OK;
+}
+
+extern "C" int mmi_lm_set_top_p(mmi_lm* lm, float top_p, float top_p_text) {
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (lm->streaming) return mmi_fail(MMI_ERR_STATE, "the handle's top_p applies from streaming_start: set it before (a live session: mmi_lm_set_row_top_p)");
+    int rc = top_p_check(top_p, top_p_text);
+    if (rc) return rc;
+    if ((top_p > 0.f || top_p_text > 0.f) && !lm->nucleus_on)
+        return mmi_fail(MMI_ERR_STATE, "top_p > 0 needs the nucleus samplers (mmi_lm_enable_nucleus)");
+    lm->top_p = top_p;
+    lm->top_p_text = top_p_text;
+    return MMI_OK;
+}
+
+extern "C" int mmi_lm_top_p(const mmi_lm* lm, float* top_p, float* top_p_text) {
+    if (!lm || !top_p || !top_p_text) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    *top_p = lm->top_p;
+    *top_p_text = lm->top_p_text;
+    return MMI_OK;
+}
+
+extern "C" int32_t mmi_lm_nucleus_enabled(const mmi_lm* lm) {
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    return (lm->streaming ? lm->nucleus_live : lm->nucleus_on) ? 1 : 0;
+}
+
+static int write_row_top_p(mmi_lm* lm, int32_t session, RowTopP v, hipStream_t s) {
+    MMI_LAUNCH(k_lm_set_row_top_p, 1, 64, 0, s, lm->rowtab, lm->gen_batch, (int)session, v.top_p, v.top_p_text);
+    MMI_CHECK_LAUNCH();
+    lm->row_top_p[session] = v;
+    return MMI_OK;
+}
+
+extern "C" int mmi_lm_set_row_top_p(mmi_lm* lm, int32_t session, float top_p, float top_p_text, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (!lm->streaming) return mmi_fail(MMI_ERR_STATE, "not streaming");
+    if (!lm->nucleus_live) return mmi_fail(MMI_ERR_STATE, "the stream was started without the nucleus samplers (mmi_lm_enable_nucleus before streaming_start)");
+    if (session < 0 || session >= lm->gen_batch) return mmi_fail(MMI_ERR_INVALID, "session outside [0, batch)");
+    int rc = top_p_check(top_p, top_p_text);
+    if (rc) return rc;
+    return write_row_top_p(lm, session, RowTopP{top_p, top_p_text}, (hipStream_t)stream);
+}
+
+extern "C" int mmi_lm_clear_row_top_p(mmi_lm* lm, int32_t session, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (!lm->streaming) return mmi_fail(MMI_ERR_STATE, "not streaming");
+    if (!lm->nucleus_live) return mmi_fail(MMI_ERR_STATE, "the stream was started without the nucleus samplers (mmi_lm_enable_nucleus before streaming_start)");
+    if (session < 0 || session >= lm->gen_batch) return mmi_fail(MMI_ERR_INVALID, "session outside [0, batch)");
+    return write_row_top_p(lm, session, RowTopP{lm->top_p, lm->top_p_text}, (hipStream_t)stream);
+}
+
 extern "C" int mmi_lm_clear_row_sampling(mmi_lm* lm, const uint8_t* mask, mmi_stream stream) {
     MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
     if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
@@ -2465,6 +2556,9 @@ extern "C" int mmi_lm_step(mmi_lm* lm, const int64_t* user_codes, int32_t n_user
     if (opt_noise)
         for (uint8_t on : lm->row_active)
             if (on) return mmi_fail(MMI_ERR_UNSUPPORTED, "supplied noise is a parity aid of the handle's own sampling settings: not available while a session has settings of its own (mmi_lm_set_row_sampling)");
+    if (opt_noise)
+        for (const RowTopP& t : lm->row_top_p)
+            if (t.top_p > 0.f || t.top_p_text > 0.f) return mmi_fail(MMI_ERR_UNSUPPORTED, "supplied noise is indexed by rank in the top-k: not available while a top_p is positive (mmi_lm_set_top_p, mmi_lm_set_row_top_p)");
     if (opt_noise && lm->samp.use_sampling && (lm->samp.top_k == 0 || lm->samp.top_k_text == 0))
         return mmi_fail(MMI_ERR_UNSUPPORTED, "supplied noise is indexed by rank in the top-k: not available with top_k = 0");
     if (need_user > 0)
@@ -2678,6 +2772,8 @@ extern "C" int mmi_lm_state_load(mmi_lm* lm, const void* src, int64_t bytes, int
         std::vector<RowSamp> tab(lm->gen_batch);         // and the restored table says which rows have settings of their own
         MMI_HIP_CHECK(hipMemcpy(tab.data(), lm->rowtab, tab.size() * sizeof(RowSamp), hipMemcpyDeviceToHost));
         for (int b = 0; b < lm->gen_batch; ++b) lm->row_active[b] = tab[b].active ? 1 : 0;
+        if (lm->nucleus_live)                             // and the sessions' top_p (supplied noise is refused by the mirror)
+            MMI_HIP_CHECK(hipMemcpy(lm->row_top_p.data(), lm->rowtab + lm->gen_batch, lm->row_top_p.size() * sizeof(RowTopP), hipMemcpyDeviceToHost));
         if (lm->row_slot)                                 // and which adapter slots are in use
             MMI_HIP_CHECK(hipMemcpy(lm->row_slot_h.data(), lm->row_slot, (size_t)lm->gen_batch * sizeof(int), hipMemcpyDeviceToHost));
     }

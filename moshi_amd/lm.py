@@ -410,6 +410,12 @@ class SessionSampling:
     pad_mult: float = 0.0
     repetition_penalty: float = 1.0
     repetition_context: int = 0
+    # The session's own nucleus (0 = off; > 0 overrides its top_k): applied through mmi_lm_set_row_top_p, not part of to_c().  Like
+    # every field here they are the SESSION's values: a SessionSampling with the defaults gives the session top_p = 0 even where the
+    # stream's own top_p is positive (on a nucleus stream; the C calls keep the two tables apart - use set_session_top_p for the
+    # nucleus alone)
+    top_p: float = 0.0
+    top_p_text: float = 0.0
 
     def to_c(self) -> "_capi.RowSampling":
         r = _capi.RowSampling()
@@ -435,6 +441,15 @@ class SessionSampling:
             raise ValueError("per-session sampling settings must be finite")
         if not self.repetition_penalty > 0:
             raise ValueError("repetition_penalty must be > 0 (1 = off)")
+        check_top_p(self.top_p, self.top_p_text)
+
+
+def check_top_p(top_p: float, top_p_text: float) -> None:
+    """The domain of the two nucleus values (mmi_lm_set_top_p): [0, 1], 0 = off."""
+    import math
+    for v in (top_p, top_p_text):
+        if not (math.isfinite(float(v)) and 0.0 <= float(v) <= 1.0):
+            raise ValueError("top_p and top_p_text must lie in [0, 1] (0 = off)")
 
 
 @dataclass
@@ -495,6 +510,19 @@ class TTSScriptStatus:
     consumption_times: list
 
 
+def _apply_nucleus(lib, handle, top_p: float, top_p_text: float, session_top_p: bool) -> bool:
+    """The handle's nucleus settings for the stream about to start (the handle is shared by every LMGen / SessionBatcher built on the
+    model, so each start states them).  Returns whether the stream runs the nucleus samplers."""
+    on = top_p > 0 or top_p_text > 0 or session_top_p
+    if on:
+        lib.check(lib.mmi_lm_enable_nucleus(handle, 1))
+        lib.check(lib.mmi_lm_set_top_p(handle, float(top_p), float(top_p_text)))
+    elif hasattr(lib.cdll, "mmi_lm_enable_nucleus"):       # (an older build of the engine has no nucleus to switch off)
+        lib.check(lib.mmi_lm_set_top_p(handle, 0.0, 0.0))
+        lib.check(lib.mmi_lm_enable_nucleus(handle, 0))
+    return on
+
+
 class LMGen:
     """Streaming generation (reference: lm.py:556-850), including classifier-free guidance (`cfg_coef`,
     `cfg_is_masked_until`, `cfg_is_no_text`), `sum` condition tensors through `lm_model.fuser` and the per-step hooks
@@ -505,8 +533,16 @@ class LMGen:
                  top_k: int = 250, top_k_text: int = 25, cfg_coef: float = 1.0, check: bool = False,
                  condition_tensors=None, on_text_hook=None, on_text_logits_hook=None, on_audio_hook=None,
                  support_out_of_sync: bool = False, cfg_is_masked_until=None, cfg_is_no_text: bool = False,
-                 seed: int = 0, tts_machine: Optional[TTSMachine] = None):
+                 seed: int = 0, tts_machine: Optional[TTSMachine] = None, top_p: float = 0.0, top_p_text: float = 0.0,
+                 session_top_p: bool = False):
         assert not lm_model.training, "generation shouldn't be used in training mode."
+        # nucleus sampling (sampling.py:97-98: top_p > 0 overrides top_k): the stream runs the nucleus samplers iff a value is
+        # positive or `session_top_p` asks for them (sessions then get their own values with `set_session_top_p`)
+        check_top_p(top_p, top_p_text)
+        self.top_p = float(top_p)
+        self.top_p_text = float(top_p_text)
+        self.session_top_p = bool(session_top_p)
+        self._nucleus = False                             # the live stream runs the nucleus samplers
         if cfg_coef != 1.:                                # lm.py:600-603
             if not cfg_is_no_text and not cfg_is_masked_until:
                 assert lm_model.fuser is not None, "Model has no fuser, cannot do CFG."
@@ -599,6 +635,7 @@ class LMGen:
                                                                 int(m.max_prefix)))
         elif hasattr(self._lib.cdll, "mmi_lm_enable_tts_machine"):       # (an older build of the engine has no machine to switch off)
             self._lib.check(self._lib.mmi_lm_enable_tts_machine(lm._handle, None, 0, 0, 0))
+        self._nucleus = _apply_nucleus(self._lib, lm._handle, self.top_p, self.top_p_text, self.session_top_p)
         if self.device.type == "cuda":
             torch.cuda.current_stream(self.device).synchronize()
         self._lib.check(self._lib.mmi_lm_streaming_start_guided(lm._handle, int(batch_size), C.byref(s), C.byref(g), self._stream()))
@@ -679,20 +716,50 @@ class LMGen:
     def set_session_sampling(self, settings, mask=None) -> None:
         """The masked sessions (all without a mask) sample with their own `SessionSampling` from the next step on: `settings` is
         one for all of them or a sequence with one per session.  Their text history (repetition penalty) starts empty.  Stream
-        ordered; the launch list and a captured step graph stay as they are."""
+        ordered; the launch list and a captured step graph stay as they are.  On a stream with the nucleus samplers the settings'
+        `top_p` / `top_p_text` become the sessions' own as well - 0, the default, turns a session's nucleus OFF whatever this
+        LMGen's `top_p` is; a session that should keep the stream's nucleus passes those values (or gets them back with
+        `clear_session_top_p`)."""
         assert self.is_streaming
         if isinstance(settings, SessionSampling):
             settings = [settings] * self._batch
         assert len(settings) == self._batch, "one SessionSampling, or one per session"
         rows = (_capi.RowSampling * self._batch)(*[x.to_c() for x in settings])
         keep, ptr = self._host_mask(mask)
+        # the nucleus part first, so that a refusal changes nothing: the domain, and a positive value on a stream without the samplers
+        picked = [b for b in range(self._batch) if keep is None or keep[b]]
+        for b in picked:
+            check_top_p(settings[b].top_p, settings[b].top_p_text)
+            if (settings[b].top_p > 0 or settings[b].top_p_text > 0) and not self._nucleus:
+                raise RuntimeError("SessionSampling.top_p > 0 needs a stream with the nucleus samplers: LMGen(session_top_p=True)")
         self._lib.check(self._lib.mmi_lm_set_row_sampling(self.lm_model._handle, ptr, rows, self._stream()))
+        if self._nucleus:
+            for b in picked:
+                self.set_session_top_p(b, settings[b].top_p, settings[b].top_p_text)
 
     def clear_session_sampling(self, mask=None) -> None:
-        """The masked sessions (all without a mask) sample with this LMGen's own settings and counter again."""
+        """The masked sessions (all without a mask) sample with this LMGen's own settings and counter again - its `top_p` /
+        `top_p_text` included: on a stream with the nucleus samplers this also undoes a `set_session_top_p` of those sessions."""
         assert self.is_streaming
         keep, ptr = self._host_mask(mask)
         self._lib.check(self._lib.mmi_lm_clear_row_sampling(self.lm_model._handle, ptr, self._stream()))
+        if self._nucleus:
+            for b in range(self._batch):
+                if keep is None or keep[b]:
+                    self.clear_session_top_p(b)
+
+    # ---- per-session nucleus (mmi_lm_set_row_top_p) ---------------------------------------------------
+    def set_session_top_p(self, session: int, top_p: float, top_p_text: float) -> None:
+        """Session `session` samples with its own nucleus values from the next step on (0 = off for that session: its top_k).
+        Needs a stream with the nucleus samplers (`top_p` / `top_p_text` > 0 or `session_top_p=True`).  Stream-ordered; the launch
+        list and a captured step graph stay as they are, and no other session changes.  `reset_streaming` keeps it."""
+        assert self.is_streaming
+        self._lib.check(self._lib.mmi_lm_set_row_top_p(self.lm_model._handle, int(session), float(top_p), float(top_p_text), self._stream()))
+
+    def clear_session_top_p(self, session: int) -> None:
+        """Session `session` returns to this LMGen's own `top_p` / `top_p_text`."""
+        assert self.is_streaming
+        self._lib.check(self._lib.mmi_lm_clear_row_top_p(self.lm_model._handle, int(session), self._stream()))
 
     # ---- per-session conditions (mmi_lm_set_row_condition) ---------------------------------------
     def set_session_condition(self, session: int, cond: SessionCondition) -> None:

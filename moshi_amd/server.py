@@ -143,7 +143,8 @@ class _Session:
 # engine has ONE seed per session: `seed` (`text_seed` is accepted as a synonym, `audio_seed` is read and ignored).
 _QUERY_FIELDS = {"text_temperature": ("temp_text", float), "text_topk": ("top_k_text", int), "audio_temperature": ("temp", float),
                  "audio_topk": ("top_k", int), "pad_mult": ("pad_mult", float), "repetition_penalty": ("repetition_penalty", float),
-                 "repetition_penalty_context": ("repetition_context", int), "seed": ("seed", int), "text_seed": ("seed", int)}
+                 "repetition_penalty_context": ("repetition_context", int), "seed": ("seed", int), "text_seed": ("seed", int),
+                 "text_topp": ("top_p_text", float), "audio_topp": ("top_p", float)}
 
 
 def parse_session_query(query):
@@ -253,8 +254,9 @@ class BatchedServer:
         finds every slot taken gets an Error message (MT=5) and is closed - the Rust server's behaviour; the reference's Python
         server would make it wait on the lock.  `query`: the connection URL's query mapping - text_temperature, text_topk,
         audio_temperature, audio_topk, pad_mult, repetition_penalty, repetition_penalty_context, seed (stream_both.rs:95-105;
-        one seed per session: text_seed is a synonym, audio_seed is ignored) give the session its own sampling settings; a value
-        the engine would refuse closes the connection with an Error message before a slot is claimed."""
+        one seed per session: text_seed is a synonym, audio_seed is ignored), text_topp, audio_topp give the session its own
+        sampling settings; a value the engine would refuse - a positive text_topp / audio_topp on a batcher without the nucleus
+        samplers included - closes the connection with an Error message before a slot is claimed."""
         import aiohttp
         if self.errors:                               # the model loop is gone: a new connection would get a slot and no frames
             await ws.send_bytes(encode_error(f"model loop failed: {self.errors[0]!r}"))
@@ -264,6 +266,12 @@ class BatchedServer:
             sampling = parse_session_query(query)
         except (ValueError, NotImplementedError) as e:
             await ws.send_bytes(encode_error(f"bad sampling parameters: {e}"))
+            await ws.close()
+            return
+        if sampling is not None and (sampling.top_p > 0 or sampling.top_p_text > 0) and not getattr(self.batcher, "nucleus", False):
+            # text_topp / audio_topp on a batcher built without the nucleus samplers: refused like any other value the engine refuses
+            await ws.send_bytes(encode_error("bad sampling parameters: text_topp / audio_topp need a batcher with the nucleus samplers "
+                                             "(SessionBatcher(session_top_p=True))"))
             await ws.close()
             return
         open_channel = self.batcher.open if sampling is None else (lambda: self.batcher.open(sampling=sampling))
@@ -374,6 +382,8 @@ def main(argv=None):                                  # pragma: no cover - needs
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--cfg-coef", type=float, default=1.0)
     ap.add_argument("--codec", default="pcm", choices=["pcm", "opus"])
+    ap.add_argument("--no-session-top-p", action="store_true",
+                    help="build the batcher without the nucleus samplers: connections that send text_topp / audio_topp are refused")
     args = ap.parse_args(argv)
     info = CheckpointInfo.from_local(args.checkpoint)
     mimi = info.get_mimi(device=args.device, max_batch=args.slots)
@@ -382,7 +392,9 @@ def main(argv=None):                                  # pragma: no cover - needs
     if info.tokenizer is not None and info.tokenizer.exists():
         import sentencepiece
         text_piece = BatchedServer.sentencepiece_text(sentencepiece.SentencePieceProcessor(str(info.tokenizer)))
-    batcher = SessionBatcher(mimi, lm, args.slots, cfg_coef=args.cfg_coef, **info.lm_gen_config)
+    gen_kwargs = dict(info.lm_gen_config)
+    gen_kwargs.setdefault("session_top_p", not args.no_session_top_p)    # connections may bring text_topp / audio_topp
+    batcher = SessionBatcher(mimi, lm, args.slots, cfg_coef=args.cfg_coef, **gen_kwargs)
     server = BatchedServer(batcher, OpusCodec() if args.codec == "opus" else PcmCodec(), text_piece)
     server.start()
     try:

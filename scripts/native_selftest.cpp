@@ -14,6 +14,10 @@
 // this program generates, every row without an adapter against the recorded values, one row on the adapter (it alone changes),
 // the refusals while the row is live, unload, destroy.
 //
+// `native_selftest <dir> --nucleus`: the LM alone with the nucleus samplers (mmi_lm_enable_nucleus): a free-running
+// sampling stream with top_p = top_p_text = 1e-6 must equal the greedy stream (the nucleus is the argmax alone), and the entry points'
+// refusals must hold.
+//
 // The same source builds against the CPU simulator (-DMMI_SELFTEST_SIM, tests/test_native_selftest.py), which is how the expected
 // values and this program are checked where there is no GPU.  The checker side (oracle) never runs here: only its recorded output.
 //
@@ -26,7 +30,7 @@
 //         -o build/native_selftest_san
 //   export MMI_NO_GRAPH=1 ASAN_OPTIONS=detect_leaks=0:detect_stack_use_after_return=0 UBSAN_OPTIONS=print_stacktrace=1
 //   build/native_selftest_san tests/golden/native_selftest && build/native_selftest_san tests/golden/native_selftest --rows 65,128 &&
-//   build/native_selftest_san tests/golden/native_selftest --adapters
+//   build/native_selftest_san tests/golden/native_selftest --adapters && build/native_selftest_san tests/golden/native_selftest --nucleus
 #include "moshi_mi.h"
 #ifdef MMI_SELFTEST_SIM
 #include "hipsim.h"
@@ -68,6 +72,8 @@ int main(int argc, char** argv) {
             for (const char* q = argv[i + 1]; *q; q = strchr(q, ',') ? strchr(q, ',') + 1 : q + strlen(q)) many_rows.push_back(atoi(q));
     bool adapters = false;
     for (int i = 1; i < argc; ++i) adapters |= !strcmp(argv[i], "--adapters");
+    bool nucleus = false;
+    for (int i = 1; i < argc; ++i) nucleus |= !strcmp(argv[i], "--nucleus");
     FILE* mf = fopen((dir + "/manifest.txt").c_str(), "r");
     if (!mf) { printf("cannot open %s/manifest.txt\n", dir.c_str()); return 2; }
     mmi_mimi_cfg mc; mmi_lm_cfg lc;
@@ -139,7 +145,7 @@ int main(int argc, char** argv) {
     int failures = 0;
 
     // ---- Mimi: encode FR frames, decode the oracle's codes
-    if (many_rows.empty() && !adapters) {
+    if (many_rows.empty() && !adapters && !nucleus) {
         mmi_mimi* m = nullptr;
         MCK(mmi_mimi_create(&mc, md.data(), (int32_t)md.size(), B, &m));
         MCK(mmi_mimi_set_num_codebooks(m, K));
@@ -178,7 +184,7 @@ int main(int argc, char** argv) {
         mmi_mimi_destroy(m);
     }
     // ---- LM: greedy steps, teacher-forced with the oracle's tokens
-    if (many_rows.empty() && !adapters) {
+    if (many_rows.empty() && !adapters && !nucleus) {
         mmi_lm* lm = nullptr;
         MCK(mmi_lm_create(&lc, ld.data(), (int32_t)ld.size(), B, &lm));
         mmi_sampling sp; memset(&sp, 0, sizeof(sp));
@@ -384,6 +390,82 @@ int main(int argc, char** argv) {
         mmi_lm_destroy(lm);
         hipFree(duc); hipFree(dforced); hipFree(dout); hipFree(dtl); hipFree(dal);
         for (void* p : bufs) hipFree(p);
+    }
+    if (nucleus) {
+        // Free-running (nothing forced): a sampling stream with top_p = top_p_text = 1e-6 on the nucleus samplers must give the greedy
+        // stream's tokens - the nucleus is then the argmax alone, at every site - and the refusals of the entry points must hold.
+        mmi_lm* lm = nullptr;
+        MCK(mmi_lm_create(&lc, ld.data(), (int32_t)ld.size(), B, &lm));
+        const int NT = dep_q + 1;
+        int64_t *duc, *dout; float* dnoise;
+        HCK(hipMalloc((void**)&duc, (size_t)B * n_user * 8)); HCK(hipMalloc((void**)&dout, (size_t)B * NT * 8));
+        HCK(hipMalloc((void**)&dnoise, (size_t)B * NT * 250 * 4));
+        {
+            std::vector<float> ones((size_t)B * NT * 250, 1.0f);
+            HCK(hipMemcpy(dnoise, ones.data(), ones.size() * 4, hipMemcpyHostToDevice));
+        }
+        int held = 0, checks = 0;
+        auto holds = [&](int rc, int want) { ++checks; held += rc == want; if (rc != want) printf("  refusal check %d: status %d, expected %d\n", checks, rc, want); };
+        float a = -1.f, t = -1.f;
+        holds(mmi_lm_set_top_p(lm, 0.5f, 0.5f), MMI_ERR_STATE);                 // not enabled
+        MCK(mmi_lm_enable_nucleus(lm, 1));
+        holds(mmi_lm_set_top_p(lm, 1.5f, 0.f), MMI_ERR_INVALID);
+        holds(mmi_lm_set_top_p(lm, 0.f, -0.5f), MMI_ERR_INVALID);
+        holds(mmi_lm_set_top_p(lm, NAN, 0.f), MMI_ERR_INVALID);
+        MCK(mmi_lm_top_p(lm, &a, &t));
+        holds(a == 0.f && t == 0.f ? 0 : 1, 0);                                // the refused calls changed nothing
+        holds(mmi_lm_set_row_top_p(lm, 0, 0.5f, 0.5f, nullptr), MMI_ERR_STATE); // not streaming
+        std::vector<std::vector<int64_t>> toks[3];
+        for (int pass = 0; pass < 3; ++pass) {            // 0: greedy; 1: sampling, top_p = 1e-6; 2: sampling, top-k (the control)
+            mmi_sampling sp; memset(&sp, 0, sizeof(sp));
+            sp.use_sampling = pass != 0; sp.temp = 0.8f; sp.temp_text = 0.7f; sp.top_k = 250; sp.top_k_text = 25; sp.seed = 5;
+            MCK(mmi_lm_set_top_p(lm, pass == 1 ? 1e-6f : 0.f, pass == 1 ? 1e-6f : 0.f));
+            MCK(mmi_lm_streaming_start(lm, B, &sp, nullptr));
+            if (pass == 1) {
+                holds(mmi_lm_enable_nucleus(lm, 0), MMI_ERR_STATE);             // while streaming
+                holds(mmi_lm_set_top_p(lm, 0.f, 0.f), MMI_ERR_STATE);
+                holds(mmi_lm_set_row_top_p(lm, B, 0.5f, 0.5f, nullptr), MMI_ERR_INVALID);
+                holds(mmi_lm_set_row_top_p(lm, 0, 2.f, 0.5f, nullptr), MMI_ERR_INVALID);
+            }
+            for (int s = 0; s < ST; ++s) {
+                std::vector<int64_t> uc((size_t)B * n_user);
+                for (size_t i = 0; i < uc.size(); ++i) uc[i] = (int64_t)((u_of(9000u + s, (uint32_t)i) + 1.0f) * 32768.0f) % card;
+                HCK(hipMemcpy(duc, uc.data(), uc.size() * 8, hipMemcpyHostToDevice));
+                int32_t valid = 0;
+                if (pass == 1 && s == 0) holds(mmi_lm_step(lm, duc, n_user, dout, nullptr, nullptr, dnoise, B, &valid, nullptr), MMI_ERR_UNSUPPORTED);
+                if (pass == 2 && s == 1) {                // a session's own value refuses the noise too; cleared, the noise is accepted
+                    MCK(mmi_lm_set_row_top_p(lm, B - 1, 0.f, 0.9f, nullptr));
+                    holds(mmi_lm_step(lm, duc, n_user, dout, nullptr, nullptr, dnoise, B, &valid, nullptr), MMI_ERR_UNSUPPORTED);
+                    MCK(mmi_lm_clear_row_top_p(lm, B - 1, nullptr));
+                }
+                MCK(mmi_lm_step(lm, duc, n_user, dout, nullptr, nullptr, nullptr, B, &valid, nullptr));
+                HCK(hipDeviceSynchronize());
+                std::vector<int64_t> o((size_t)B * NT);
+                HCK(hipMemcpy(o.data(), dout, o.size() * 8, hipMemcpyDeviceToHost));
+                toks[pass].push_back(o);
+            }
+            MCK(mmi_lm_streaming_stop(lm));
+        }
+        MCK(mmi_lm_set_top_p(lm, 0.f, 0.f));
+        MCK(mmi_lm_enable_nucleus(lm, 0));
+        mmi_sampling sp; memset(&sp, 0, sizeof(sp));
+        sp.use_sampling = 1; sp.temp = 0.8f; sp.temp_text = 0.7f; sp.top_k = 250; sp.top_k_text = 25; sp.seed = 5;
+        MCK(mmi_lm_streaming_start(lm, B, &sp, nullptr));
+        holds(mmi_lm_set_row_top_p(lm, 0, 0.5f, 0.5f, nullptr), MMI_ERR_STATE);   // a stream without the nucleus samplers
+        holds(mmi_lm_clear_row_top_p(lm, 0, nullptr), MMI_ERR_STATE);
+        MCK(mmi_lm_streaming_stop(lm));
+        long differ = 0, control = 0, produced = 0;
+        for (int s = 0; s < ST; ++s)
+            for (size_t i = 0; i < toks[0][s].size(); ++i) {
+                differ += toks[0][s][i] != toks[1][s][i];
+                control += toks[0][s][i] != toks[2][s][i];
+                produced += toks[0][s][i] >= 0;
+            }
+        printf("lm with the nucleus samplers: top_p = 1e-6 differs from the greedy stream in %ld of %ld tokens (must be 0; the top-k stream "
+               "differs in %ld: must be > 0); %d of %d refusal checks held\n", differ, produced, control, held, checks);
+        failures += differ != 0 || control == 0 || produced == 0 || held != checks;
+        mmi_lm_destroy(lm);
+        hipFree(duc); hipFree(dout); hipFree(dnoise);
     }
     printf(failures ? "SELFTEST FAILED\n" : "SELFTEST PASSED\n");
     return failures ? 1 : 0;
