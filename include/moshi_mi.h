@@ -183,7 +183,16 @@ typedef struct mmi_lm_cfg {
     int32_t extra_heads_num_heads;    /* 0: nn.Linear(dim, extra_heads_dim) heads on the transformer output (lm.py:101-102, 224-226) */
     int32_t extra_heads_dim;          /* 6 */
     int32_t kv_cache_dtype;           /* 0 / MMI_BF16: the reference's bf16 ring (transformer.py:453-455); MMI_F8E4M3: e4m3 ring -
-                                         half the attention stream and half the per-session state (SURVEY.md 8d C5 "fp8 KV") */
+                                         half the attention stream and half the per-session state (SURVEY.md 8d C5 "fp8 KV");
+                                         MMI_F4E2M1X2: 4-bit ring, 0.5625 bytes per element: E2M1 codes (bit 3 sign,
+                                         bits 2..0 the magnitude of {0, .5, 1, 1.5, 2, 3, 4, 6}; two per byte, element 2i in the low
+                                         nibble) under one E8M0 scale byte 2^(s - 127) per block of 16 consecutive head-dim elements of
+                                         one (row, head, position).  Quantised: what the bf16 ring would hold (k after RoPE).  s = E - 2
+                                         (E: biased exponent of the block's absmax), at most 253; E < 3: s = 0 and all codes 0; round to
+                                         nearest, ties to the even code, saturating at +-6; Inf and NaN become +-6 under their sign.  Per
+                                         layer, for keys and for values: a codes plane [B][H][cap][Dh/2] bytes, then a scale plane
+                                         [B][H][cap][Dh/16] bytes (the layer padded to a multiple of 256 bytes).  Needs a head dim multiple of 32 (else MMI_ERR_UNSUPPORTED).  The
+                                         depth transformer's cache and the cross-attention K/V stay bf16 */
     int32_t cross_attention;          /* 1: every temporal layer has a cross-attention block (`cross_attention.{in,out}_projs.0`,
                                          `norm_cross.{weight,bias}`; transformer.py:727-732, 779-786) fed by mmi_guidance.condition_cross */
 } mmi_lm_cfg;
@@ -592,6 +601,18 @@ int mmi_lm_debug_linear(mmi_lm* lm, const char* weight_name, const char* alpha_n
 int mmi_lm_debug_linear_lora(mmi_lm* lm, const char* weight_name, const char* alpha_name_or_null, int32_t path, const void* x_bf16,
                              int32_t rows, void* out_bf16, int8_t* codes_or_null, float* absmax_or_null, void* norm_out_or_null,
                              const int32_t* row_slots, mmi_stream stream);
+
+/* Test aids of the KV ring (no reference counterpart).
+ * mmi_lm_debug_kv4_quantize: the device quantiser of the 4-bit ring (mmi_lm_cfg.kv_cache_dtype = MMI_F4E2M1X2) on caller-supplied
+ *   rows: x device bf16 [n][16 * m] -> codes device u8 [n][8 * m] and scales device u8 [n][m], block j of a row = its elements
+ *   16 j .. 16 j + 15.  x must be 16-byte aligned and codes 8-byte aligned (vector loads and stores).  Works on any handle (it
+ *   touches no state); synchronises `stream`.
+ * mmi_lm_debug_kv_ring: the raw ring bytes of temporal layer `layer` (which = 0 keys, 1 values) of a live stream, copied to the
+ *   device buffer `dst` of exactly mmi_lm_debug_kv_ring(.., dst = NULL, ..) bytes - that call returns the size and copies nothing.
+ *   bf16 ring: [rows][H][cap][Dh] bf16; e4m3: the same in bytes; 4-bit: the codes plane [rows][H][cap][Dh/2], then the scale plane
+ *   [rows][H][cap][Dh/16] (rows = model rows: sessions, then their guidance twins).  Returns the bytes copied, or a negative mmi_status. */
+int mmi_lm_debug_kv4_quantize(mmi_lm* lm, const void* x_bf16, int32_t n, int32_t m, void* codes_u8, void* scales_u8, mmi_stream stream);
+int64_t mmi_lm_debug_kv_ring(mmi_lm* lm, int32_t layer, int32_t which, void* dst, int64_t nbytes, mmi_stream stream);
 
 /* The launch list of one frame step, recorded while the step ran for the first time: one line "site<TAB>kernel[<TAB>weight bytes]" per kernel
  * launch in launch order (sites: "L.in_proj", "L.ffn_in", "dep.out_proj", "text_linear", ...).  scripts/rocpd_sites.py joins

@@ -112,7 +112,7 @@ class LMConfig:
     delays: List[int] = field(default_factory=lambda: [0, 0, 1, 1, 1, 1, 1, 1, 1, 0, 1, 1, 1, 1, 1, 1, 1])
     extra_heads_num_heads: int = 0      # lm.py:101-102: linear heads on the transformer output (step_with_extra_heads)
     extra_heads_dim: int = 6
-    kv_cache_dtype: str = "bf16"        # "fp8": e4m3 ring for the temporal transformer's keys / values (engine option)
+    kv_cache_dtype: str = "bf16"        # "fp8": e4m3 ring for the temporal transformer's keys / values; "fp4": E2M1 under block scales (engine options)
     cross_attention: bool = False       # every temporal layer attends to the fuser's `cross` condition (transformer.py:727-731, 779-786)
     # TTS family (lm.py:58-127, 174-208; lm_utils.py:66-124): micro-step k runs depformer weight set schedule[k] (dep_q entries,
     # values 0..max without gaps); low-rank depformer embeddings of this rank (a multiple of 8) + a `low_rank` linear; text tokens

@@ -389,9 +389,11 @@ GemmPlan plan_gemm(const MmiKnobs& k, const GemmW& g, bool may_split) {
 // Octet sharing of k_gemm_xp (GemmArgs::osplit): GEMMs with so few n-tiles that most CUs would idle while each busy one is
 // bound by what a single CU can pull (~25 GB/s) - the depth transformer's N = 1024 linears: 32 tiles of 64-180 KB.
 // knobs.gemm_osplit: 0 = off, 2 / 4 = force (test hook / A-B), default = as many parts as bring the launch to >= 128 workgroups.
-int plan_osplit(const MmiKnobs& k, const GemmW& g, const GemmPlan& p, int epi, int T) {
+// pairs: the in_proj of a 4-bit ring - a part must own whole octet PAIRS (a ring block is 16 features: mmi_epi_kv_feats), so
+// two parts at the 32-row tile at most, none at the 16-row tile.
+int plan_osplit(const MmiKnobs& k, const GemmW& g, const GemmPlan& p, int epi, int T, bool pairs = false) {
     if (epi == MMI_EPI_GATE || g.wq != 0 || p.ntw != 1 || (T != 32 && T != 16)) return 1;
-    const int octs = T / 8;
+    const int octs = pairs ? T / 16 : T / 8;
     int os = 1;
     if (k.gemm_osplit != MmiKnobs::UNSET) {
         if (k.gemm_osplit <= 1) return 1;
@@ -403,13 +405,13 @@ int plan_osplit(const MmiKnobs& k, const GemmW& g, const GemmPlan& p, int epi, i
     return (long)g.NT * p.ksplit <= 64 ? os : 1;
 }
 
-template <int TN, int MT, int NTW, int WQ>
+template <int TN, int MT, int NTW, int WQ, bool KV4 = false>
 int launch_gemm_q(hipStream_t s, dim3 groups, int waves, const GemmArgs& a) {
     if constexpr (MT * NTW <= 2) {
-        if (waves == 8) MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 8, 2, WQ>), groups, 512, 0, s, a);
-        else MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 4, 2, WQ>), groups, 256, 0, s, a);
+        if (waves == 8) MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 8, 2, WQ, false, false, KV4>), groups, 512, 0, s, a);
+        else MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 4, 2, WQ, false, false, KV4>), groups, 256, 0, s, a);
     } else {
-        MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 4, 2, WQ>), groups, 256, 0, s, a);
+        MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 4, 2, WQ, false, false, KV4>), groups, 256, 0, s, a);
     }
     MMI_CHECK_LAUNCH();
     return MMI_OK;
@@ -417,68 +419,68 @@ int launch_gemm_q(hipStream_t s, dim3 groups, int waves, const GemmArgs& a) {
 
 // MXFP4 entries (four k-steps each): two entries per register buffer at one batch tile, one at two (8 activation fragments per
 // entry there); no instantiation carries scratch (profiles/mxfp4/kernel_resources.csv)
-template <int TN, int MT, int NTW>
+template <int TN, int MT, int NTW, bool KV4 = false>
 int launch_gemm_f4(hipStream_t s, dim3 groups, int waves, const GemmArgs& a) {
     constexpr int U = MT == 1 ? 2 : 1;
     if constexpr (MT * NTW <= 2) {
-        if (waves == 8) MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 8, U, 4>), groups, 512, 0, s, a);
-        else MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 4, U, 4>), groups, 256, 0, s, a);
+        if (waves == 8) MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 8, U, 4, false, false, KV4>), groups, 512, 0, s, a);
+        else MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 4, U, 4, false, false, KV4>), groups, 256, 0, s, a);
         MMI_CHECK_LAUNCH();
         return MMI_OK;
     }
     return mmi_fail(MMI_ERR_UNSUPPORTED, "MXFP4 linears run one n-tile and at most two batch tiles per workgroup");
 }
 
-template <int TN, int MT, int NTW>
+template <int TN, int MT, int NTW, bool KV4 = false>
 int launch_gemm_w(hipStream_t s, dim3 groups, int waves, int u, int wq, bool q8_u2, const GemmArgs& a) {
-    if (wq == 4) return launch_gemm_f4<TN, MT, NTW>(s, groups, waves, a);
-    if (wq == 1) return launch_gemm_q<TN, MT, NTW, 1>(s, groups, waves, a);
-    if (wq == 2) return launch_gemm_q<TN, MT, NTW, 2>(s, groups, waves, a);
+    if (wq == 4) return launch_gemm_f4<TN, MT, NTW, KV4>(s, groups, waves, a);
+    if (wq == 1) return launch_gemm_q<TN, MT, NTW, 1, KV4>(s, groups, waves, a);
+    if (wq == 2) return launch_gemm_q<TN, MT, NTW, 2, KV4>(s, groups, waves, a);
     if (wq == 3) {
         // int8 x int8 has no conversion to hold in registers: four entries per register buffer instead of two (q8_u2: the
         // weight-only depth, same-box A/B)
         if (!q8_u2 && waves == 8) {
             if constexpr (MT * NTW <= 2) {
-                MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 8, 4, 3>), groups, 512, 0, s, a);
+                MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 8, 4, 3, false, false, KV4>), groups, 512, 0, s, a);
                 MMI_CHECK_LAUNCH();
                 return MMI_OK;
             }
         }
-        return launch_gemm_q<TN, MT, NTW, 3>(s, groups, waves, a);
+        return launch_gemm_q<TN, MT, NTW, 3, KV4>(s, groups, waves, a);
     }
     if (waves == 8 && u == 2 && MT * NTW == 1) {
-        if constexpr (MT * NTW == 1) MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 8, 2>), groups, 512, 0, s, a);
+        if constexpr (MT * NTW == 1) MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 8, 2, 0, false, false, KV4>), groups, 512, 0, s, a);
         MMI_CHECK_LAUNCH();
         return MMI_OK;
     }
     switch (waves) {
-        case 4: MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 4, 4>), groups, 256, 0, s, a); break;
+        case 4: MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 4, 4, 0, false, false, KV4>), groups, 256, 0, s, a); break;
         case 8:
-            if constexpr (MT * NTW <= 2) { MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 8, 4>), groups, 512, 0, s, a); break; }
-            MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 4, 4>), groups, 256, 0, s, a); break;
+            if constexpr (MT * NTW <= 2) { MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 8, 4, 0, false, false, KV4>), groups, 512, 0, s, a); break; }
+            MMI_LAUNCH((k_gemm_xp<TN, MT, NTW, 4, 4, 0, false, false, KV4>), groups, 256, 0, s, a); break;
         default: return mmi_fail(MMI_ERR_UNSUPPORTED, "unsupported waves per GEMM workgroup");
     }
     MMI_CHECK_LAUNCH();
     return MMI_OK;
 }
 
-template <int TN>
+template <int TN, bool KV4 = false>
 int launch_gemm_t(hipStream_t s, const GemmPlan& p, int NT, int mt, bool q8_u2, const GemmArgs& a) {
     const dim3 groups(mmi_cdiv(NT, p.ntw) * (a.osplit > 1 ? a.osplit : 1), p.ksplit);
     const int w8 = a.wq;
-    if (mt == 1) return launch_gemm_w<TN, 1, 1>(s, groups, p.waves, p.u, w8, q8_u2, a);     // one n-tile per workgroup (two measured slower
-    if (mt == 2) return launch_gemm_w<TN, 2, 1>(s, groups, p.waves, p.u, w8, q8_u2, a);     // in the step, DESIGN 9e: not instantiated)
+    if (mt == 1) return launch_gemm_w<TN, 1, 1, KV4>(s, groups, p.waves, p.u, w8, q8_u2, a);     // one n-tile per workgroup (two measured slower
+    if (mt == 2) return launch_gemm_w<TN, 2, 1, KV4>(s, groups, p.waves, p.u, w8, q8_u2, a);     // in the step, DESIGN 9e: not instantiated)
     return mmi_fail(MMI_ERR_UNSUPPORTED, "batch too large for the skinny GEMM");
 }
 
 // Adapter handles (mmi_lm_enable_adapters): the LORA forms of k_gemm_xp - bf16, one n-tile per workgroup, at most two batch
 // tiles - under launch_gemm_w's choice of waves and fragments in flight
-template <int TN, int MT>
+template <int TN, int MT, bool KV4 = false>
 int launch_gemm_lora(hipStream_t s, dim3 groups, int waves, int u, const GemmArgs& a) {
     if (waves == 8 && u == 2 && MT == 1) {
-        if constexpr (MT == 1) MMI_LAUNCH((k_gemm_xp<TN, MT, 1, 8, 2, 0, true>), groups, 512, 0, s, a);
-    } else if (waves == 8) MMI_LAUNCH((k_gemm_xp<TN, MT, 1, 8, 4, 0, true>), groups, 512, 0, s, a);
-    else if (waves == 4) MMI_LAUNCH((k_gemm_xp<TN, MT, 1, 4, 4, 0, true>), groups, 256, 0, s, a);
+        if constexpr (MT == 1) MMI_LAUNCH((k_gemm_xp<TN, MT, 1, 8, 2, 0, true, false, KV4>), groups, 512, 0, s, a);
+    } else if (waves == 8) MMI_LAUNCH((k_gemm_xp<TN, MT, 1, 8, 4, 0, true, false, KV4>), groups, 512, 0, s, a);
+    else if (waves == 4) MMI_LAUNCH((k_gemm_xp<TN, MT, 1, 4, 4, 0, true, false, KV4>), groups, 256, 0, s, a);
     else return mmi_fail(MMI_ERR_UNSUPPORTED, "unsupported waves per GEMM workgroup");
     MMI_CHECK_LAUNCH();
     return MMI_OK;
@@ -518,6 +520,9 @@ XldsPlan plan_xlds(const mmi_lm* lm, const GemmW& g, const GemmArgs& a, int mt) 
         for (long b = 0; b < p.grid; ++b) {
             const long u0 = b * 4L * g.NT / p.grid, u1 = (b + 1) * 4L * g.NT / p.grid;
             if (u1 > u0 && ((u1 + 3) >> 2) - (u0 >> 2) > 3) return p;
+            // a 4-bit ring's block is an octet PAIR (mmi_epi_kv_feats): every share must start on an even octet (the production
+            // in_proj does: 6 octets each), else the GEMM stays on k_gemm_xp
+            if (a.epi == MMI_EPI_ROPE_KV && a.kv8 == 2 && (u0 & 1)) return p;
         }
     }
     p.stagger = mode == '2' && g.wq == 0;                     // per-tile epilogues under the last chunk's stream (bf16)
@@ -528,32 +533,32 @@ XldsPlan plan_xlds(const mmi_lm* lm, const GemmW& g, const GemmArgs& a, int mt) 
     return p;
 }
 
-template <int MT, int KC, bool STAGGER, int WQ>
+template <int MT, int KC, bool STAGGER, int WQ, bool KV4>
 int launch_xlds_v(hipStream_t s, const XldsPlan& p, const GemmArgs& a) {
     static bool attr_set = false;
     if (!attr_set) {
-        MMI_HIP_CHECK(hipFuncSetAttribute((const void*)k_gemm_xlds<MT, KC, 3, STAGGER, WQ>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
+        MMI_HIP_CHECK(hipFuncSetAttribute((const void*)k_gemm_xlds<MT, KC, 3, STAGGER, WQ, KV4>, hipFuncAttributeMaxDynamicSharedMemorySize, 131072));
         attr_set = true;
     }
-    MMI_LAUNCH((k_gemm_xlds<MT, KC, 3, STAGGER, WQ>), p.grid, 512, p.smem, s, a);
+    MMI_LAUNCH((k_gemm_xlds<MT, KC, 3, STAGGER, WQ, KV4>), p.grid, 512, p.smem, s, a);
     MMI_CHECK_LAUNCH();
     return MMI_OK;
 }
 // production chunk (64 / MT k-steps, or 32 / MT two-step entries) or one of the short test chunks
-template <int MT, bool STAGGER, int WQ>
+template <int MT, bool STAGGER, int WQ, bool KV4>
 int launch_xlds_kc(hipStream_t s, const XldsPlan& p, const GemmArgs& a) {
     constexpr int BIG = ((WQ == 1 || WQ == 2) ? 32 : 64) / MT;
-    if (p.kc == BIG) return launch_xlds_v<MT, BIG, STAGGER, WQ>(s, p, a);
-    if (p.kc == 8) return launch_xlds_v<MT, 8, STAGGER, WQ>(s, p, a);
-    if (p.kc == 4) return launch_xlds_v<MT, 4, STAGGER, WQ>(s, p, a);
+    if (p.kc == BIG) return launch_xlds_v<MT, BIG, STAGGER, WQ, KV4>(s, p, a);
+    if (p.kc == 8) return launch_xlds_v<MT, 8, STAGGER, WQ, KV4>(s, p, a);
+    if (p.kc == 4) return launch_xlds_v<MT, 4, STAGGER, WQ, KV4>(s, p, a);
     return mmi_fail(MMI_ERR_UNSUPPORTED, "k_gemm_xlds: unsupported chunk");
 }
-template <int MT>
+template <int MT, bool KV4 = false>
 int launch_xlds(hipStream_t s, const XldsPlan& p, const GemmArgs& a) {
-    if (a.wq == 1) return launch_xlds_kc<MT, false, 1>(s, p, a);
-    if (a.wq == 2) return launch_xlds_kc<MT, false, 2>(s, p, a);
-    if (a.wq == 3) return launch_xlds_kc<MT, false, 3>(s, p, a);
-    return p.stagger ? launch_xlds_kc<MT, true, 0>(s, p, a) : launch_xlds_kc<MT, false, 0>(s, p, a);
+    if (a.wq == 1) return launch_xlds_kc<MT, false, 1, KV4>(s, p, a);
+    if (a.wq == 2) return launch_xlds_kc<MT, false, 2, KV4>(s, p, a);
+    if (a.wq == 3) return launch_xlds_kc<MT, false, 3, KV4>(s, p, a);
+    return p.stagger ? launch_xlds_kc<MT, true, 0, KV4>(s, p, a) : launch_xlds_kc<MT, false, 0, KV4>(s, p, a);
 }
 
 // k_gemm_xp_once (a wave's whole K-slice requested before its first MFMA) for the GEMMs k_gemm_xp would walk in three or more
@@ -575,11 +580,12 @@ int once_kmax(char gemm_once, const GemmW& g, const GemmPlan& p, int mt, const G
     if (g.T == 16 && mt <= 2) return kper <= 11 ? 11 : 0;
     return 0;
 }
+template <bool KV4 = false>
 int launch_once(hipStream_t s, int T, int mt, int kmax, dim3 groups, const GemmArgs& a) {
-    if (T == 32 && kmax == 11) MMI_LAUNCH((k_gemm_xp_once<32, 1, 8, 11>), groups, 512, 0, s, a);
-    else if (T == 32) MMI_LAUNCH((k_gemm_xp_once<32, 1, 8, 22>), groups, 512, 0, s, a);
-    else if (mt == 1) MMI_LAUNCH((k_gemm_xp_once<16, 1, 8, 11>), groups, 512, 0, s, a);
-    else MMI_LAUNCH((k_gemm_xp_once<16, 2, 8, 11>), groups, 512, 0, s, a);
+    if (T == 32 && kmax == 11) MMI_LAUNCH((k_gemm_xp_once<32, 1, 8, 11, KV4>), groups, 512, 0, s, a);
+    else if (T == 32) MMI_LAUNCH((k_gemm_xp_once<32, 1, 8, 22, KV4>), groups, 512, 0, s, a);
+    else if (mt == 1) MMI_LAUNCH((k_gemm_xp_once<16, 1, 8, 11, KV4>), groups, 512, 0, s, a);
+    else MMI_LAUNCH((k_gemm_xp_once<16, 2, 8, 11, KV4>), groups, 512, 0, s, a);
     MMI_CHECK_LAUNCH();
     return MMI_OK;
 }
@@ -587,20 +593,21 @@ int launch_once(hipStream_t s, int T, int mt, int kmax, dim3 groups, const GemmA
 // k_gemm_rows: more than two batch tiles of 32 (a handle of mmi_lm_create_rows, 65..128 model rows; bf16 linears).  Two n-tiles
 // per workgroup once that still leaves every CU a workgroup (halves the activation bytes read from L2), else one.
 // knobs.rows_ntw = 1 / 2 forces either (same-box A/B; bit-identical).
-template <int MT>
+template <int MT, bool KV4>
 int launch_rows_mt(hipStream_t s, int ntw, int NT, int ksplit, const GemmArgs& a) {
     const dim3 groups(mmi_cdiv(NT, ntw), ksplit);
-    if (ntw == 2) MMI_LAUNCH((k_gemm_rows<32, MT, 2, 1>), groups, 256, 0, s, a);
-    else MMI_LAUNCH((k_gemm_rows<32, MT, 1, 2>), groups, 256, 0, s, a);
+    if (ntw == 2) MMI_LAUNCH((k_gemm_rows<32, MT, 2, 1, KV4>), groups, 256, 0, s, a);
+    else MMI_LAUNCH((k_gemm_rows<32, MT, 1, 2, KV4>), groups, 256, 0, s, a);
     MMI_CHECK_LAUNCH();
     return MMI_OK;
 }
+template <bool KV4 = false>
 int launch_rows(const MmiKnobs& k, hipStream_t s, const GemmW& g, const GemmPlan& p, int mt, const GemmArgs& a) {
     if (g.T != 32 || g.wq != 0 || a.wq != 0) return mmi_fail(MMI_ERR_UNSUPPORTED, "more than 64 rows need bf16 linears at the 32-row tile");
     int ntw = (long)g.NT * p.ksplit >= 512 ? 2 : 1;
     if (k.rows_ntw) ntw = k.rows_ntw;
-    if (mt == 3) return launch_rows_mt<3>(s, ntw, g.NT, p.ksplit, a);
-    if (mt == 4) return launch_rows_mt<4>(s, ntw, g.NT, p.ksplit, a);
+    if (mt == 3) return launch_rows_mt<3, KV4>(s, ntw, g.NT, p.ksplit, a);
+    if (mt == 4) return launch_rows_mt<4, KV4>(s, ntw, g.NT, p.ksplit, a);
     return mmi_fail(MMI_ERR_UNSUPPORTED, "batch too large for the many-row GEMM");
 }
 
@@ -614,7 +621,11 @@ GemmArgs rows_group_view(const GemmArgs& a_in, int r0, int rows) {
     const long oshift = a.out_mode == MMI_OUT_PACKED ? (long)(r0 / 32) * a.out_ksteps * 512 : (long)r0 * a.out_ld;
     if (a.out) a.out += oshift;
     if (a.epi == MMI_EPI_ROPE_KV) {
-        const long ring = (long)r0 * a.H * a.cap * a.Dh / (a.kv8 ? 2 : 1);      // uint16 units: an fp8 ring holds bytes
+        // uint16 units: an fp8 ring holds bytes, a 4-bit ring's codes plane nibbles - and its scale plane, kv_soff bytes behind the
+        // codes, moves by rows of Dh / 16 bytes
+        const long rows_el = (long)r0 * a.H * a.cap * a.Dh;
+        const long ring = a.kv8 == 2 ? rows_el / 4 : rows_el / (a.kv8 ? 2 : 1);
+        if (a.kv8 == 2) a.kv_soff += rows_el / 16 - rows_el / 2;
         a.qrot += (long)r0 * a.H * a.Dh; a.kc += ring; a.vc += ring;
         a.offsets += r0; a.rope += (long)r0 * a.Dh;
     }
@@ -666,7 +677,9 @@ int launch_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, GemmArgs a, bool is_d
     const int mt = mmi_cdiv(a.B, g.T);
     const MmiKnobs& k = lm->knobs;
     const GemmPlan p = plan_gemm(k, g, a.epi == MMI_EPI_PARTIAL);
-    a.osplit = plan_osplit(k, g, p, a.epi, g.T);
+    // the in_proj of a 4-bit ring: the instantiations whose epilogue holds that ring form (every other launch runs the kernels it always ran)
+    const bool kv4 = a.epi == MMI_EPI_ROPE_KV && a.kv8 == 2;
+    a.osplit = plan_osplit(k, g, p, a.epi, g.T, kv4);
     const XldsPlan xl = plan_xlds(lm, g, a, mt);
     EvPair* ev = nullptr;
     if (lm->profiling && is_dominant) {
@@ -693,18 +706,24 @@ int launch_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, GemmArgs a, bool is_d
         a.lora_ksteps = lm->lora_S * lm->lora_R / mmi_kstep(g.T);
         a.lora_slot_ksteps = lm->lora_R / mmi_kstep(g.T);
         const dim3 groups(g.NT * (a.osplit > 1 ? a.osplit : 1), p.ksplit);
-        if (mt == 1) rc = g.T == 32 ? launch_gemm_lora<32, 1>(s, groups, p.waves, p.u, a) : launch_gemm_lora<16, 1>(s, groups, p.waves, p.u, a);
+        if (kv4 && mt == 1) rc = g.T == 32 ? launch_gemm_lora<32, 1, true>(s, groups, p.waves, p.u, a) : launch_gemm_lora<16, 1, true>(s, groups, p.waves, p.u, a);
+        else if (kv4 && mt == 2) rc = g.T == 32 ? launch_gemm_lora<32, 2, true>(s, groups, p.waves, p.u, a) : launch_gemm_lora<16, 2, true>(s, groups, p.waves, p.u, a);
+        else if (mt == 1) rc = g.T == 32 ? launch_gemm_lora<32, 1>(s, groups, p.waves, p.u, a) : launch_gemm_lora<16, 1>(s, groups, p.waves, p.u, a);
         else if (mt == 2) rc = g.T == 32 ? launch_gemm_lora<32, 2>(s, groups, p.waves, p.u, a) : launch_gemm_lora<16, 2>(s, groups, p.waves, p.u, a);
         else rc = mmi_fail(MMI_ERR_UNSUPPORTED, "adapters run at most two batch tiles per linear");
     } else if (mt > 2) {
         lm->rows_launches += 1;
         a.osplit = 1;
-        rc = launch_rows(k, s, g, p, mt, a);
+        rc = kv4 ? launch_rows<true>(k, s, g, p, mt, a) : launch_rows(k, s, g, p, mt, a);
     } else if (xl.on) {
         lm->xlds_launches += 1;
-        rc = mt == 1 ? launch_xlds<1>(s, xl, a) : launch_xlds<2>(s, xl, a);
+        if (kv4) rc = mt == 1 ? launch_xlds<1, true>(s, xl, a) : launch_xlds<2, true>(s, xl, a);
+        else rc = mt == 1 ? launch_xlds<1>(s, xl, a) : launch_xlds<2>(s, xl, a);
     } else if (const int kmax = once_kmax(k.gemm_once, g, p, mt, a)) {
-        rc = launch_once(s, g.T, mt, kmax, dim3(g.NT * (a.osplit > 1 ? a.osplit : 1), p.ksplit), a);
+        const dim3 og(g.NT * (a.osplit > 1 ? a.osplit : 1), p.ksplit);
+        rc = kv4 ? launch_once<true>(s, g.T, mt, kmax, og, a) : launch_once(s, g.T, mt, kmax, og, a);
+    } else if (kv4) {
+        rc = g.T == 32 ? launch_gemm_t<32, true>(s, p, g.NT, mt, k.q8_u2, a) : launch_gemm_t<16, true>(s, p, g.NT, mt, k.q8_u2, a);
     } else {
         rc = g.T == 32 ? launch_gemm_t<32>(s, p, g.NT, mt, k.q8_u2, a) : launch_gemm_t<16>(s, p, g.NT, mt, k.q8_u2, a);
     }
@@ -1109,8 +1128,37 @@ static int attn_variant(const mmi_lm* lm, int NS) {
     return lm->depth_bound + 1 > (long)attn_solo_rows(lm->knobs, lm->batch * lm->cfg.num_heads) ? 1 : 0;
 }
 
-int launch_attn_split(hipStream_t s, const LmAttnArgs& a, bool kv8, bool wave) {
+// One layer's ring in uint16 units, keys or values.  bf16: an element each; e4m3: a byte each; 4-bit (MMI_F4E2M1X2): the codes
+// plane [B][H][cap][Dh/2] bytes, then the scale plane [B][H][cap][Dh/16] bytes - 9/16 of a byte per element (Dh % 32 == 0).
+static int kv_form(int32_t kv_cache_dtype) { return kv_cache_dtype == MMI_F8E4M3 ? 1 : (kv_cache_dtype == MMI_F4E2M1X2 ? 2 : 0); }
+// The 4-bit layer is padded to a multiple of 256 bytes, so that the next layer's codes plane starts 16-byte aligned whatever the
+// capacity (the scale plane is a multiple of 2 bytes only); the other rings are as they were.
+static size_t kv_layer_u16(int kvf, size_t elems) { return kvf == 2 ? (elems / 4 + elems / 32 + 127) / 128 * 128 : elems / (kvf ? 2 : 1); }
+
+// kvf: the ring form (kv_form).  The bf16 and e4m3 launches are spelled as they always were: the spelling is the kernel's name in
+// mmi_lm_launch_list
+int launch_attn_split(hipStream_t s, const LmAttnArgs& a, int kvf, bool wave) {
     dim3 grid(a.B * a.H, a.NS);
+    const bool kv8 = kvf == 1;
+    if (kvf == 2) {
+        if (wave) {
+            switch (a.Dh) {
+                case 128: MMI_LAUNCH((k_lm_attn_wave<128, 2>), grid, 256, 0, s, a); break;
+                case 64: MMI_LAUNCH((k_lm_attn_wave<64, 2>), grid, 256, 0, s, a); break;
+                case 32: MMI_LAUNCH((k_lm_attn_wave<32, 2>), grid, 256, 0, s, a); break;
+                default: return mmi_fail(MMI_ERR_UNSUPPORTED, "head dim must be 32, 64 or 128");
+            }
+        } else {
+            switch (a.Dh) {
+                case 128: MMI_LAUNCH((k_lm_attn_split<128, 2>), grid, 256, 0, s, a); break;
+                case 64: MMI_LAUNCH((k_lm_attn_split<64, 2>), grid, 256, 0, s, a); break;
+                case 32: MMI_LAUNCH((k_lm_attn_split<32, 2>), grid, 256, 0, s, a); break;
+                default: return mmi_fail(MMI_ERR_UNSUPPORTED, "head dim must be 32, 64 or 128");
+            }
+        }
+        MMI_CHECK_LAUNCH();
+        return MMI_OK;
+    }
     if (wave) {
         if (kv8) {
             switch (a.Dh) {
@@ -1198,8 +1246,8 @@ int build_program(mmi_lm* lm) {
     // ---- temporal transformer
     const int NS = attn_splits(lm->knobs, c, B);
     lm->attn_ns = NS;
-    const bool kv8 = c.kv_cache_dtype == MMI_F8E4M3;
-    const size_t kv_layer = (size_t)B * H * c.context * Dh / (kv8 ? 2 : 1);     // in uint16 units: an fp8 ring is half as large
+    const int kvf = kv_form(c.kv_cache_dtype);
+    const size_t kv_layer = kv_layer_u16(kvf, (size_t)B * H * c.context * Dh);  // in uint16 units: an fp8 ring is half as large
     Pending pending;   // split-K partials of the previous linear_out still to be folded into x
     for (int l = 0; l < c.num_layers; ++l) {
         const LayerW& L = lm->layers[l];
@@ -1212,14 +1260,16 @@ int build_program(mmi_lm* lm) {
         a.B = B; a.H = H; a.Dh = Dh; a.cap = c.context; a.context = c.context; a.NS = NS; a.max_period = c.max_period;
         a.T = lm->T; a.out_ksteps = packed_ksteps(lm, d);
         a.done = lm->attn_done; a.solo_rows = attn_solo_rows(lm->knobs, B * H);
+        a.kv_soff = kvf == 2 ? (long)B * H * c.context * Dh / 2 : 0;
         P.site("L.in_proj");
         {   // in_proj with RoPE + ring-KV write in its epilogue
             GemmArgs ga;
             memset(&ga, 0, sizeof(ga));
             ga.xp = reinterpret_cast<const u32x4*>(lm->xn); ga.epi = MMI_EPI_ROPE_KV; ga.B = B;
             if (a8) { ga.xp = reinterpret_cast<const u32x4*>(lm->xnq); ga.sx = lm->sx_xn; ga.wq = 3; }
-            ga.qrot = a.qrot; ga.kc = a.kc; ga.vc = a.vc; ga.offsets = lm->offsets_m; ga.H = H; ga.Dh = Dh; ga.cap = c.context; ga.kv8 = kv8 ? 1 : 0;
+            ga.qrot = a.qrot; ga.kc = a.kc; ga.vc = a.vc; ga.offsets = lm->offsets_m; ga.H = H; ga.Dh = Dh; ga.cap = c.context; ga.kv8 = kvf;
             ga.max_period = c.max_period; ga.rope = lm->rope;
+            if (kvf == 2) ga.kv_soff = a.kv_soff;
             const u32x4* lt = add_lora_shrink(lm, L.in_proj, ga.xp);
             GemmW gw = L.in_proj;
             P.add([lm, gw, ga, lt](hipStream_t s) { return launch_gemm(lm, s, gw, ga, false, lt); }, (long)gw.bytes);
@@ -1230,7 +1280,7 @@ int build_program(mmi_lm* lm) {
             LmAttnArgs aa = a;
             const bool merge_launch = a.NS > 1 && (!wave || lm->prog.variant == 1);
             if (merge_launch) { aa.solo_rows = -1; aa.done = nullptr; }     // every workgroup leaves its partial (m, l, O)
-            int rc = launch_attn_split(s, aa, kv8, wave);
+            int rc = launch_attn_split(s, aa, kvf, wave);
             if (rc) return rc;
             if (merge_launch) MMI_LAUNCH(k_lm_attn_combine, B * H, Dh < 64 ? 64 : Dh, 0, s, aa);
             MMI_CHECK_LAUNCH();
@@ -1458,10 +1508,12 @@ int project_cross_source(mmi_lm* lm, const uint16_t* src, size_t slot0, int ncol
 int check_cfg(const mmi_lm_cfg& c) {
     if (c.dim % c.num_heads || c.depformer_dim % c.depformer_num_heads) return mmi_fail(MMI_ERR_UNSUPPORTED, "dim % heads != 0");
     const int Dh = c.dim / c.num_heads, Dhd = c.depformer_dim / c.depformer_num_heads;
+    if (c.kv_cache_dtype == MMI_F4E2M1X2 && Dh % 32)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "4-bit KV needs a head dim multiple of 32 (a 16-byte load of the ring is two blocks of 16)");
     if (Dh != 32 && Dh != 64 && Dh != 128) return mmi_fail(MMI_ERR_UNSUPPORTED, "temporal head dim must be 32/64/128");
     if (Dhd > 64 || Dhd < 1) return mmi_fail(MMI_ERR_UNSUPPORTED, "depformer head dim must be <= 64");
-    if (c.kv_cache_dtype != 0 && c.kv_cache_dtype != MMI_BF16 && c.kv_cache_dtype != MMI_F8E4M3)
-        return mmi_fail(MMI_ERR_UNSUPPORTED, "kv_cache_dtype must be MMI_BF16 or MMI_F8E4M3");
+    if (c.kv_cache_dtype != 0 && c.kv_cache_dtype != MMI_BF16 && c.kv_cache_dtype != MMI_F8E4M3 && c.kv_cache_dtype != MMI_F4E2M1X2)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "kv_cache_dtype must be MMI_BF16, MMI_F8E4M3 or MMI_F4E2M1X2");
     if (c.kv_cache_dtype == MMI_F8E4M3 && (c.dim / c.num_heads) % 16) return mmi_fail(MMI_ERR_UNSUPPORTED, "fp8 KV needs a head dim multiple of 16");
     if (c.card % 8 || c.text_card_out % 8 || c.card > 32768 || c.text_card_out > 32768)
         return mmi_fail(MMI_ERR_UNSUPPORTED, "vocabulary sizes must be multiples of 8 and at most 32768");
@@ -1856,7 +1908,7 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
     const int NS = attn_splits(lm->knobs, c, B);
     auto fail = [&](int code) { lm->streaming = true; mmi_lm_streaming_stop(lm); return code; };
     MmiArena& A = lm->st;
-    const size_t kvn = (size_t)c.num_layers * B * H * c.context * Dh / (c.kv_cache_dtype == MMI_F8E4M3 ? 2 : 1);   // uint16 units
+    const size_t kvn = (size_t)c.num_layers * kv_layer_u16(kv_form(c.kv_cache_dtype), (size_t)B * H * c.context * Dh);   // uint16 units
     const size_t dkvn = (size_t)c.depformer_num_layers * B * Hd * c.dep_q * Dhd;
     bool ok = true;
     ok &= hipSuccess == A.alloc(&lm->exec, (size_t)G);
@@ -1973,6 +2025,9 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
     }
     if (lm->cond) MMI_HIP_CHECK(hipMemcpyAsync(lm->cond, guide->condition_sum, (size_t)B * d * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
     MMI_LAUNCH(k_fill_i32, mmi_cdiv(G * lm->NC * lm->CT, 256), 256, 0, s, lm->cache, -2, (long)G * lm->NC * lm->CT);   // lm.py:608-613
+    // every plane of the ring, a 4-bit ring's scale planes included: the attention reads rows past the valid length with p = 0, so
+    // they must decode to finite values - scale byte 0 is the factor 0.0f, 255 would be Inf (Inf * 0 = NaN).  A snapshot
+    // (mmi_lm_state_save / load) is the whole arena and so carries both planes.
     MMI_HIP_CHECK(hipMemsetAsync(lm->kc, 0, kvn * sizeof(uint16_t), s));
     MMI_HIP_CHECK(hipMemsetAsync(lm->vc, 0, kvn * sizeof(uint16_t), s));
     MMI_HIP_CHECK(hipMemsetAsync(lm->attn_done, 0, (size_t)B * H * sizeof(unsigned), s));
@@ -2826,6 +2881,41 @@ extern "C" int mmi_lm_seek(mmi_lm* lm, const int64_t* offsets, mmi_stream stream
     lm->offset_cpu = mx;
     lm->depth_bound = mx;
     return MMI_OK;
+}
+
+// Test aids of the KV ring (include/moshi_mi.h)
+extern "C" int mmi_lm_debug_kv4_quantize(mmi_lm* lm, const void* x_bf16, int32_t n, int32_t m, void* codes_u8, void* scales_u8, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm || !x_bf16 || !codes_u8 || !scales_u8) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (n <= 0 || m <= 0) return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_kv4_quantize: n and m must be positive");
+    hipStream_t s = (hipStream_t)stream;
+    const long nblocks = (long)n * m;
+    MMI_LAUNCH(k_kv4_quantize, (int)mmi_cdiv(nblocks, 256L), 256, 0, s, (const uint16_t*)x_bf16, nblocks, (uint8_t*)codes_u8, (uint8_t*)scales_u8);
+    MMI_CHECK_LAUNCH();
+    MMI_HIP_CHECK(hipStreamSynchronize(s));
+    return MMI_OK;
+}
+
+extern "C" int64_t mmi_lm_debug_kv_ring(mmi_lm* lm, int32_t layer, int32_t which, void* dst, int64_t nbytes, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm) return (int64_t)mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (!lm->streaming) return (int64_t)mmi_fail(MMI_ERR_STATE, "not streaming");
+    const mmi_lm_cfg& c = lm->cfg;
+    if (layer < 0 || layer >= c.num_layers || (which != 0 && which != 1))
+        return (int64_t)mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_kv_ring: layer must be a temporal layer, which 0 (keys) or 1 (values)");
+    const int kvf = kv_form(c.kv_cache_dtype);
+    const size_t elems = (size_t)lm->batch * c.num_heads * c.context * (c.dim / c.num_heads);
+    const size_t layer_u16 = kv_layer_u16(kvf, elems);
+    const int64_t want = kvf == 2 ? (int64_t)(elems / 2 + elems / 16) : (int64_t)(layer_u16 * sizeof(uint16_t));   // without the layer's padding
+    if (!dst) return want;
+    if (nbytes != want)
+        return (int64_t)mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_kv_ring: the buffer holds " + std::to_string(nbytes) + " bytes, the layer's ring " + std::to_string(want));
+    hipStream_t s = (hipStream_t)stream;
+    const uint16_t* src = (which == 0 ? lm->kc : lm->vc) + (size_t)layer * layer_u16;
+    hipError_t e = hipMemcpyAsync(dst, src, (size_t)want, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return (int64_t)mmi_fail(MMI_ERR_HIP, std::string("mmi_lm_debug_kv_ring: ") + hipGetErrorString(e));
+    return want;
 }
 
 // Parity tap: ONE linear of the model on caller-supplied rows, through the kernels the step uses for it (include/moshi_mi.h).

@@ -299,8 +299,11 @@ struct GemmArgs {
                             // norm kernel) and sx[b] the row absmax they were scaled by (bitsandbytes' SCA); the epilogue multiplies
                             // the int32 sum by SCA[b] / 127 * SCB[n] / 127.  k_gemm_q8: written here for the epilogue (LDS)
     int gate_rows;          // H of a gated linear_in (value row of feature n is H + n)
+    union {
     float* partial;         // EPI_PARTIAL: fp32 partial sums [gridDim.y][B][N] (K split over gridDim.y workgroups so that
                             // GEMMs with few n-tiles still cover every CU); summed by k_resid_rmsnorm
+    long kv_soff;           // EPI_ROPE_KV, 4-bit ring (kv8 == 2): bytes from a ring's codes plane (kc / vc) to its scale plane
+    };
     // EPI_ROPE_KV (temporal in_proj): features [q | k | v], each H heads x Dh.  RoPE (rope.py:11-82, interleaved, fp32) on
     // q and k for the single new position offsets[b]; q -> qrot [B][H][Dh]; k, v -> ring slot offsets[b] % cap of
     // [B][H][cap][Dh] (RingKVCache scatter, transformer.py:243-250: written for every row, exec mask or not)
@@ -311,7 +314,8 @@ struct GemmArgs {
     int H, Dh, cap;
     float max_period;
     const float* rope;      // [B][Dh/2][2]: (cos, sin) of the new position's angles, filled once per step by k_lm_prepare
-    int kv8;                // the ring holds e4m3 bytes instead of bf16 (fp8 KV cache: half the attention stream)
+    int kv8;                // 1: the ring holds e4m3 bytes instead of bf16 (fp8 KV cache: half the attention stream); 2: E2M1 codes
+                            // [B][H][cap][Dh/2] and, kv_soff bytes behind them, E8M0 scale bytes [B][H][cap][Dh/16] (mmi_fp4.h)
     // k_gemm_xp_norm: RMSNorm of the input rows fused in front of the GEMM (xp holds the un-normalised rows)
     union {
     const uint16_t* alpha;  // [D]
@@ -366,6 +370,72 @@ __device__ __forceinline__ u32x4 mmi_gemm_prefetch_addend(const GemmArgs& a, int
     return pre;
 }
 
+// EPI_ROPE_KV, 4-bit ring: the eight bf16 ring values (k after RoPE, v as is) of the task (b, 8-feature group gi) of tile (t, m),
+// re-summed from the reduction scratch exactly as that task's own thread sums them below - same wave order, same dequantisation,
+// same rotation, every operation rounded on its own.  A 16-element block of the ring spans two tasks (gi, gi ^ 1): each of the
+// two threads derives the partner's values itself, so both hold the same block absmax without exchanging anything - no cross-lane
+// operation under the divergent `continue`s of the task loop.  The partner's sums must be real sums: the forms that hand a
+// workgroup only some of a tile's row octets (GemmArgs::osplit, k_gemm_xlds) leave the other octets' accumulators meaningless,
+// so the host gives a 4-bit in_proj only windows of whole octet PAIRS (plan_osplit, plan_xlds in lm_engine.hip).
+template <int TN, int WAVES, int LS, int NE>
+__device__ __forceinline__ void mmi_epi_kv_feats(const GemmArgs& a, const float* rb, int gi, int bl, int b, int row, int n0, bool iacc,
+                                                 const float* sx_local, float* v8) {
+    int off_lo, off_hi;
+    if constexpr (TN == 32) { off_lo = bl * LS + 4 * gi; off_hi = (bl + 32) * LS + 4 * gi; }
+    else { off_lo = (bl + 32 * gi) * LS; off_hi = (bl + 32 * gi + 16) * LS; }
+    float s[8];
+    if (iacc) {
+        int si[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) si[e] = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+            const i32x4 lo = *reinterpret_cast<const i32x4*>(rb + w * NE + off_lo);
+            const i32x4 hi = *reinterpret_cast<const i32x4*>(rb + w * NE + off_hi);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { si[e] += lo[e]; si[4 + e] += hi[e]; }
+        }
+        const float sca = sx_local ? sx_local[row] : a.sx[b];
+        const f32x4 c0 = *reinterpret_cast<const f32x4*>(a.wscb + n0), c1 = *reinterpret_cast<const f32x4*>(a.wscb + n0 + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            s[e] = mmi_i8_dequant(si[e], sca, c0[e]);
+            s[4 + e] = mmi_i8_dequant(si[4 + e], sca, c1[e]);
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) s[e] = 0.f;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) {
+            const f32x4 lo = *reinterpret_cast<const f32x4*>(rb + w * NE + off_lo);
+            const f32x4 hi = *reinterpret_cast<const f32x4*>(rb + w * NE + off_hi);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { s[e] += lo[e]; s[4 + e] += hi[e]; }
+        }
+        if (a.wscale) {
+            const f32x4 c0 = *reinterpret_cast<const f32x4*>(a.wscale + n0), c1 = *reinterpret_cast<const f32x4*>(a.wscale + n0 + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) { s[e] *= c0[e]; s[4 + e] *= c1[e]; }
+        }
+    }
+    const int HD = a.H * a.Dh;
+    const int sec = n0 / HD, hn = n0 - sec * HD, d0 = hn % a.Dh;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v8[e] = mmi_round_bf16(s[e]);
+    if (sec < 2) {
+        const float* cs = a.rope + ((long)b * (a.Dh / 2) + d0 / 2) * 2;
+        const f32x4 cs0 = *reinterpret_cast<const f32x4*>(cs), cs1 = *reinterpret_cast<const f32x4*>(cs + 4);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float c = j < 2 ? cs0[2 * j] : cs1[2 * j - 4], sn = j < 2 ? cs0[2 * j + 1] : cs1[2 * j - 3];
+            const float re = v8[2 * j], im = v8[2 * j + 1];
+            mmi_rope_rotate(re, im, c, sn, v8[2 * j], v8[2 * j + 1]);
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v8[e] = mmi_round_bf16(v8[e]);
+}
+
 // Split-K reduction across the workgroup's waves (fixed order -> deterministic) and the epilogue shared by the GEMM
 // kernels: one task = 8 consecutive output features of one session, written as one 16-byte vector.
 // EXT: the reduction scratch is handed in (`red_ext`, WAVES * NTW * MT * 64 * LS floats) instead of a static LDS array - for
@@ -373,7 +443,9 @@ __device__ __forceinline__ u32x4 mmi_gemm_prefetch_addend(const GemmArgs& a, int
 // g_lo / g_hi: only the tile's 8-feature groups [g_lo, g_hi) are written (k_gemm_xlds hands a tile's row octets to two
 // workgroups when that balances the chip: 384 in_proj tiles over 256 CUs = 6 octets each); default = the whole tile.
 // LORA_T: the shrink launch's epilogue (MMI_EPI_LORA_T) is compiled in - only into the shrink instantiations of k_gemm_xp.
-template <int TN, int MT, int NTW, int WAVES, bool EXT = false, bool LORA_T = false>
+// KV4: the 4-bit ring form of MMI_EPI_ROPE_KV is compiled in - only into the instantiations launch_gemm picks for the in_proj of a
+// 4-bit handle (GemmArgs::kv8 == 2); every other instantiation is the code it was without that form.
+template <int TN, int MT, int NTW, int WAVES, bool EXT = false, bool LORA_T = false, bool KV4 = false>
 __device__ __forceinline__ void mmi_gemm_epilogue(const GemmArgs& a, float (&accv)[NTW][MT][TN == 32 ? 16 : 4], int wave, int lane,
                                                   int nt0, u32x4 pre, float* red_ext = nullptr, int g_lo = 0, int g_hi = 4,
                                                   const float* sx_local = nullptr) {
@@ -548,6 +620,25 @@ __device__ __forceinline__ void mmi_gemm_epilogue(const GemmArgs& a, float (&acc
                     mmi_rope_rotate(re, im, c, sn, v8[2 * j], v8[2 * j + 1]);
                 }
             }
+            if constexpr (KV4) {
+            if (sec != 0 && a.kv8 == 2) {
+                // 4-bit ring: this task's eight values are half of a 16-element block; the other half is the task gi ^ 1 of the
+                // same row (the lane bl ^ TN of this wave) - see mmi_epi_kv_feats.  Both threads quantise under the same scale
+                // byte; each stores its own four code bytes, the even one the scale byte.  Vector stores.
+                float mine[8], other[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) mine[e] = mmi_round_bf16(v8[e]);
+                mmi_epi_kv_feats<TN, WAVES, LS, NE>(a, rb, gi ^ 1, bl, b, m * TN + bl, n0 ^ 8, iacc, sx_local, other);
+                const uint32_t am0 = mmi_kv4_absmax8(mine), am1 = mmi_kv4_absmax8(other);
+                const uint32_t sb = mmi_kv4_scale_byte(am0 > am1 ? am0 : am1);
+                const uint32_t codes = sb ? mmi_kv4_quant8(mine, sb) : 0u;
+                uint8_t* plane = reinterpret_cast<uint8_t*>(sec == 1 ? a.kc : a.vc);
+                const long rowi = ((long)b * a.H + h) * a.cap + (int)(off % a.cap);
+                *reinterpret_cast<uint32_t*>(plane + rowi * (a.Dh / 2) + d0 / 2) = codes;
+                if (!(gi & 1)) plane[a.kv_soff + rowi * (a.Dh / 16) + d0 / 16] = (uint8_t)sb;
+                continue;
+            }
+            }
             if (sec != 0 && a.kv8) {   // fp8 ring: the bf16 k / v values (k after RoPE, as the bf16 ring would hold them) -> e4m3
                 uint8_t* d8 = reinterpret_cast<uint8_t*>(sec == 1 ? a.kc : a.vc) + (((long)b * a.H + h) * a.cap + (int)(off % a.cap)) * a.Dh + d0;
                 u32x2 o8;
@@ -645,8 +736,8 @@ __device__ __forceinline__ uint32_t mmi_fp4_scale_of(uint32_t s, int j) { return
 // adds the same share of a row's adapter whichever slot holds it - every other slot's t is +0 and changes no sum: a session's
 // bits do not depend on its slot.  Everything behind the accumulators is as without it.
 // LORA_T: a shrink launch (A_all against the linear's operand): the plain kernel with MMI_EPI_LORA_T compiled into its epilogue.
-template <int TN, int MT, int NTW, int WAVES, int U, int WQ = 0, bool LORA = false, bool LORA_T = false>
-__global__ __launch_bounds__(WAVES * 64, (TN == 16 && MT == 1 && NTW == 1 && WQ == 0 && WAVES == 8 && !LORA && !LORA_T) ? 4 : 1) void k_gemm_xp(GemmArgs a) {
+template <int TN, int MT, int NTW, int WAVES, int U, int WQ = 0, bool LORA = false, bool LORA_T = false, bool KV4 = false>
+__global__ __launch_bounds__(WAVES * 64, (TN == 16 && MT == 1 && NTW == 1 && WQ == 0 && WAVES == 8 && !LORA && !LORA_T && !KV4) ? 4 : 1) void k_gemm_xp(GemmArgs a) {
     static_assert(!(LORA || LORA_T) || (WQ == 0 && NTW == 1), "adapters run on bf16 linears, one n-tile per workgroup");
     constexpr bool W8 = WQ == 1;
     constexpr int R = TN == 32 ? 16 : 4;          // accumulator registers per MFMA tile
@@ -839,7 +930,7 @@ __global__ __launch_bounds__(WAVES * 64, (TN == 16 && MT == 1 && NTW == 1 && WQ 
             for (int r = 0; r < R; ++r) {
                 accv[t][m][r] = acc[t][m][r];      // WQ == 3: the wave's int32 sum, as its bit pattern (summed as integers by the epilogue)
             }
-    mmi_gemm_epilogue<TN, MT, NTW, WAVES, false, LORA_T>(a, accv, wave, lane, nt0, pre, nullptr, g_lo, g_hi);
+    mmi_gemm_epilogue<TN, MT, NTW, WAVES, false, LORA_T, KV4>(a, accv, wave, lane, nt0, pre, nullptr, g_lo, g_hi);
 }
 
 // k_gemm_xp for GEMMs that are a LATENCY chain, not a stream (the depth transformer's linear_out: 5.8 MB behind 128 workgroups,
@@ -848,7 +939,7 @@ __global__ __launch_bounds__(WAVES * 64, (TN == 16 && MT == 1 && NTW == 1 && WQ 
 // flight, 22 to fetch).  Same K partition over waves / workgroups, same k order inside a wave, same reduction and epilogue:
 // bit-identical to k_gemm_xp<TN, MT, 1, WAVES, U>.  bf16 weights, one n-tile per workgroup, octet sharing and split-K over
 // gridDim.y as in k_gemm_xp.  Registers: KMAX * (1 + MT) fragments of 4 (TN = 32, KMAX = 22: 176).
-template <int TN, int MT, int WAVES, int KMAX>
+template <int TN, int MT, int WAVES, int KMAX, bool KV4 = false>
 __global__ __launch_bounds__(WAVES * 64) void k_gemm_xp_once(GemmArgs a) {
     constexpr int R = TN == 32 ? 16 : 4;
     typedef float acc_t __attribute__((ext_vector_type(R)));
@@ -895,7 +986,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemm_xp_once(GemmArgs a) {
     for (int m = 0; m < MT; ++m)
 #pragma unroll
         for (int r = 0; r < R; ++r) accv[0][m][r] = acc[m][r];
-    mmi_gemm_epilogue<TN, MT, 1, WAVES>(a, accv, wave, lane, nt0, pre, nullptr, g_lo, g_hi);
+    mmi_gemm_epilogue<TN, MT, 1, WAVES, false, false, KV4>(a, accv, wave, lane, nt0, pre, nullptr, g_lo, g_hi);
 }
 
 // The many-row GEMM: 65..128 model rows = MT = 3 or 4 batch tiles of 32 against bf16 weights (a handle of mmi_lm_create_rows).
@@ -911,7 +1002,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemm_xp_once(GemmArgs a) {
 // Reduction scratch: WAVES * MT * 64 * LS floats for ONE n-tile = 64 KiB at 4 waves, MT = 4 (LS = 16) - the static array of
 // mmi_gemm_epilogue.  Fewer waves (4, not 8) is what makes it fit; with NTW = 2 the tiles go through the same scratch one
 // after the other (a barrier between them), not side by side.
-template <int TN, int MT, int NTW, int U>
+template <int TN, int MT, int NTW, int U, bool KV4 = false>
 __global__ __launch_bounds__(256, 2) void k_gemm_rows(GemmArgs a) {
     static_assert(TN == 32 && MT >= 3 && MT <= 4 && NTW >= 1 && NTW <= 2, "k_gemm_rows: 32-row tiles, 3 or 4 of them");
     constexpr int WAVES = 4, R = 16;
@@ -1003,7 +1094,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_rows(GemmArgs a) {
 #pragma unroll
             for (int r = 0; r < R; ++r) accv[0][m][r] = acc[t][m][r];
         if (t > 0) __syncthreads();                  // the previous tile's sums have been read out of the scratch
-        mmi_gemm_epilogue<TN, MT, 1, WAVES>(a, accv, wave, lane, nt0 + t, pre[t]);
+        mmi_gemm_epilogue<TN, MT, 1, WAVES, false, false, KV4>(a, accv, wave, lane, nt0 + t, pre[t]);
     }
 }
 
@@ -1321,7 +1412,7 @@ struct MmiFalse { static constexpr bool value = false; };
 // entry meets XS = 2 activation fragments, so the production chunk is 32 / MT entries (the same 64 KiB of activations).
 // Chunks shorter than 8 entries (the tiny shapes of the tests) leave the upper waves without k-steps: they keep zero
 // accumulators and only take part in the barriers and the epilogue.
-template <int MT, int KC, int NTMAX = 3, bool STAGGER = false, int WQ = 0>
+template <int MT, int KC, int NTMAX = 3, bool STAGGER = false, int WQ = 0, bool KV4 = false>
 __global__ __launch_bounds__(512) void k_gemm_xlds(GemmArgs a) {
     typedef float acc_t __attribute__((ext_vector_type(16)));
     constexpr int XS = (WQ == 1 || WQ == 2) ? 2 : 1;   // activation fragments per weight entry (WQ = 3: int8 entries, one each)
@@ -1445,7 +1536,7 @@ __global__ __launch_bounds__(512) void k_gemm_xlds(GemmArgs a) {
                     for (int m = 0; m < MT; ++m)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) accv[0][m][r] = acc[t][m][r];
-                    mmi_gemm_epilogue<32, MT, 1, 8, true>(a, accv, wave, lane, t0 + t, u32x4{0u, 0u, 0u, 0u}, red, oct_lo(t), oct_hi(t));
+                    mmi_gemm_epilogue<32, MT, 1, 8, true, false, KV4>(a, accv, wave, lane, t0 + t, u32x4{0u, 0u, 0u, 0u}, red, oct_lo(t), oct_hi(t));
                 }
             }
         }
@@ -1469,7 +1560,7 @@ __global__ __launch_bounds__(512) void k_gemm_xlds(GemmArgs a) {
             for (int m = 0; m < MT; ++m)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) accv[0][m][r] = acc[t][m][r];     // WQ == 3: int32 bit patterns (see the epilogue)
-            mmi_gemm_epilogue<32, MT, 1, 8, true>(a, accv, wave, lane, t0 + t, u32x4{0u, 0u, 0u, 0u}, red, oct_lo(t), oct_hi(t));
+            mmi_gemm_epilogue<32, MT, 1, 8, true, false, KV4>(a, accv, wave, lane, t0 + t, u32x4{0u, 0u, 0u, 0u}, red, oct_lo(t), oct_hi(t));
         }
     }
 }
@@ -1904,6 +1995,28 @@ __global__ void k_expand_emb(const uint16_t* __restrict__ E, int R, const uint16
 // ------------------------------------------------------------------------------------------------
 // temporal attention: RoPE + ring-KV write, split decode attention over the VALID part of the ring, combine
 // ------------------------------------------------------------------------------------------------
+// mmi_lm_debug_kv4_quantize: the 4-bit ring's quantiser (mmi_fp4.h) on caller-supplied bf16 blocks of 16, one thread per block -
+// the conversions the in_proj epilogue runs, where a test can see them
+__global__ void k_kv4_quantize(const uint16_t* __restrict__ x, long nblocks, uint8_t* __restrict__ codes, uint8_t* __restrict__ scales) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nblocks) return;
+    const u32x4 lo = *reinterpret_cast<const u32x4*>(x + 16 * i), hi = *reinterpret_cast<const u32x4*>(x + 16 * i + 8);
+    float f[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        f[2 * q] = mmi_bf16_to_f32((uint16_t)(lo[q] & 0xffffu));
+        f[2 * q + 1] = mmi_bf16_to_f32((uint16_t)(lo[q] >> 16));
+        f[8 + 2 * q] = mmi_bf16_to_f32((uint16_t)(hi[q] & 0xffffu));
+        f[8 + 2 * q + 1] = mmi_bf16_to_f32((uint16_t)(hi[q] >> 16));
+    }
+    const uint32_t am0 = mmi_kv4_absmax8(f), am1 = mmi_kv4_absmax8(f + 8);
+    const uint32_t sb = mmi_kv4_scale_byte(am0 > am1 ? am0 : am1);
+    u32x2 c = {0u, 0u};
+    if (sb) { c[0] = mmi_kv4_quant8(f, sb); c[1] = mmi_kv4_quant8(f + 8, sb); }
+    *reinterpret_cast<u32x2*>(codes + 8 * i) = c;
+    scales[i] = (uint8_t)sb;
+}
+
 struct LmAttnArgs {
     uint16_t* qrot;        // [B][H][Dh] roped queries (written by in_proj's epilogue)
     uint16_t* kc;          // [B][H][cap][Dh]
@@ -1918,6 +2031,7 @@ struct LmAttnArgs {
     unsigned* done;        // k_lm_attn_wave with the ring split over NS workgroups: arrival counter per (session, head), 0 between launches
                            // (the last workgroup to arrive merges); null = leave the partials to k_lm_attn_combine
     int solo_rows;         // ... rings of at most this many rows are walked by workgroup y = 0 alone (the others exit at once); -1 = never
+    long kv_soff;          // 4-bit ring: bytes from a codes plane (kc / vc: [B][H][cap][Dh/2]) to its scale plane ([B][H][cap][Dh/16])
 };
 
 #define MMI_ATTN_CHUNK 256
@@ -1928,10 +2042,14 @@ struct LmAttnArgs {
 // fill the chip): the normalised output goes straight to out_proj's packed input; otherwise partials for the combine.
 // KV8: the ring holds e4m3 bytes (fp8 KV cache): a 16-byte load then covers 16 dims, DH/16 lanes share a row and one wave
 // instruction reads twice as many rows; the values are widened exactly (v_cvt_pk_f32_fp8) and everything else is unchanged.
-template <int DH, bool KV8 = false>
+// KVF = 2: the 4-bit ring (mmi_fp4.h): a 16-byte load covers 32 dims = two blocks, and a 2-byte load beside it their two
+// scale bytes; DH/32 lanes share a row; widened exactly (v_cvt_scalef32_pk_f32_fp4), scores, softmax and P.V stay fp32.  Rows past
+// the valid length hold scale byte 0 (the ring is zeroed at streaming_start) and reach the FMA as 0 * p with p = 0.
+template <int DH, int KVF = 0>
 __global__ __launch_bounds__(256) void k_lm_attn_split(LmAttnArgs a) {
-    constexpr int EPL = KV8 ? 16 : 8;  // elements per lane (16 bytes)
-    constexpr int ES = KV8 ? 1 : 2;    // bytes per element
+    constexpr bool KV8 = KVF == 1, KV4 = KVF == 2;
+    constexpr int EPL = KV4 ? 32 : (KV8 ? 16 : 8);  // elements per lane (16 bytes)
+    constexpr int ROWB = KV4 ? DH / 2 : (KV8 ? DH : 2 * DH);    // bytes per ring row
     constexpr int LPR = DH / EPL;      // lanes per row
     constexpr int RPW = 64 / LPR;      // rows per wave instruction
     constexpr int CH = MMI_ATTN_CHUNK;
@@ -1958,9 +2076,12 @@ __global__ __launch_bounds__(256) void k_lm_attn_split(LmAttnArgs a) {
             qv[v * 8 + 2 * q + 1] = mmi_bf16_to_f32((uint16_t)(qq[q] >> 16));
         }
     }
-    // 16 bytes of a ring row -> EPL fp32 values
-    auto widen = [](const u32x4& r, float* f) {
-        if constexpr (KV8) {
+    // 16 bytes of a ring row -> EPL fp32 values (sc2: the two scale bytes of a 4-bit lane's blocks)
+    auto widen = [](const u32x4& r, uint32_t sc2, float* f) {
+        if constexpr (KV4) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) mmi_kv4_widen8(r[q], (sc2 >> (8 * (q >> 1))) & 0xffu, f + 8 * q);
+        } else if constexpr (KV8) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) mmi_fp8x4_to_f32(r[q], f + 4 * q);
         } else {
@@ -1971,8 +2092,11 @@ __global__ __launch_bounds__(256) void k_lm_attn_split(LmAttnArgs a) {
             }
         }
     };
-    const uint8_t* kbase = reinterpret_cast<const uint8_t*>(a.kc) + (long)bh * a.cap * DH * ES;
-    const uint8_t* vbase = reinterpret_cast<const uint8_t*>(a.vc) + (long)bh * a.cap * DH * ES;
+    const uint8_t* kbase = reinterpret_cast<const uint8_t*>(a.kc) + (long)bh * a.cap * ROWB;
+    const uint8_t* vbase = reinterpret_cast<const uint8_t*>(a.vc) + (long)bh * a.cap * ROWB;
+    // 4-bit ring: the scale planes, DH / 16 bytes per row, two per lane
+    const uint8_t* ksbase = reinterpret_cast<const uint8_t*>(a.kc) + a.kv_soff + (long)bh * a.cap * (DH / 16);
+    const uint8_t* vsbase = reinterpret_cast<const uint8_t*>(a.vc) + a.kv_soff + (long)bh * a.cap * (DH / 16);
     const float scale = 1.0f / sqrtf((float)DH);
     constexpr int PER_WAVE = CH / 4;
     float m_run = -INFINITY, l_run = 0.f;
@@ -1987,10 +2111,13 @@ __global__ __launch_bounds__(256) void k_lm_attn_split(LmAttnArgs a) {
 #pragma unroll 1
         for (int h0 = 0; h0 < NIT; h0 += NB) {
             u32x4 kk[NB];
+            uint32_t ks[NB];
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
                 const int slot = min(c0 + wave * PER_WAVE + (h0 + i) * RPW + rsub, L - 1);
-                kk[i] = *reinterpret_cast<const u32x4*>(kbase + ((long)slot * DH + seg * EPL) * ES);
+                kk[i] = *reinterpret_cast<const u32x4*>(kbase + (long)slot * ROWB + seg * 16);
+                if constexpr (KV4) ks[i] = *reinterpret_cast<const uint16_t*>(ksbase + (long)slot * (DH / 16) + seg * 2);
+                else ks[i] = 0u;
             }
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
@@ -2005,7 +2132,7 @@ __global__ __launch_bounds__(256) void k_lm_attn_split(LmAttnArgs a) {
                 }
                 float dot = 0.f;
                 float kf[EPL];
-                widen(kk[i], kf);
+                widen(kk[i], ks[i], kf);
 #pragma unroll
                 for (int e = 0; e < EPL; ++e) dot += qv[e] * kf[e];
 #pragma unroll
@@ -2040,17 +2167,20 @@ __global__ __launch_bounds__(256) void k_lm_attn_split(LmAttnArgs a) {
 #pragma unroll 1
         for (int h0 = 0; h0 < NIT; h0 += NB) {
             u32x4 vv[NB];
+            uint32_t vs[NB];
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
                 const int slot = min(c0 + wave * PER_WAVE + (h0 + i) * RPW + rsub, L - 1);
-                vv[i] = *reinterpret_cast<const u32x4*>(vbase + ((long)slot * DH + seg * EPL) * ES);
+                vv[i] = *reinterpret_cast<const u32x4*>(vbase + (long)slot * ROWB + seg * 16);
+                if constexpr (KV4) vs[i] = *reinterpret_cast<const uint16_t*>(vsbase + (long)slot * (DH / 16) + seg * 2);
+                else vs[i] = 0u;
             }
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
                 const int rl = wave * PER_WAVE + (h0 + i) * RPW + rsub;
                 const float pr = (c0 + rl < L) ? sc[rl] : 0.f;
                 float vf[EPL];
-                widen(vv[i], vf);
+                widen(vv[i], vs[i], vf);
 #pragma unroll
                 for (int e = 0; e < EPL; ++e) acc[e] += pr * vf[e];
             }
@@ -2090,13 +2220,16 @@ __global__ __launch_bounds__(256) void k_lm_attn_split(LmAttnArgs a) {
 // running (max, sum, accumulator): a round requests NB key groups AND their NB value groups at once (the values do not depend
 // on the scores), the next round's 2 NB loads are issued before this round's arithmetic, and nothing but registers and
 // cross-lane shuffles is touched until the slots and the waves are merged once at the end.
-template <int DH, bool KV8 = false>
-__global__ __launch_bounds__(256, KV8 ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a) {      // bf16 ring: <= 128 VGPRs, 4 workgroups per CU
-    constexpr int EPL = KV8 ? 16 : 8;  // elements per lane (16 bytes)
-    constexpr int ES = KV8 ? 1 : 2;    // bytes per element
+// KVF: the ring form, as for k_lm_attn_split (1 = e4m3, 2 = E2M1 under block scales: a 2-byte scale load beside each 16-byte load).
+template <int DH, int KVF = 0>
+__global__ __launch_bounds__(256, KVF ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a) {      // bf16 ring: <= 128 VGPRs, 4 workgroups per CU
+    constexpr bool KV8 = KVF == 1, KV4 = KVF == 2;
+    constexpr int EPL = KV4 ? 32 : (KV8 ? 16 : 8);  // elements per lane (16 bytes)
+    constexpr int ROWB = KV4 ? DH / 2 : (KV8 ? DH : 2 * DH);    // bytes per ring row
     constexpr int LPR = DH / EPL;      // lanes per row
     constexpr int RPW = 64 / LPR;      // rows per wave instruction
-    constexpr int NB = 4;              // row groups per round (x 2 buffers x (key + value) = 16 loads of 16 bytes in flight per lane)
+    constexpr int NB = KV4 ? 2 : 4;    // row groups per round (x 2 buffers x (key + value) = 16 loads of 16 bytes in flight per lane; the 4-bit
+                                       // ring, 32 accumulators and 32 query elements per lane, keeps half as many: no scratch at head dim 128)
     const int bh = blockIdx.x;
     const int b = bh / a.H;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -2117,8 +2250,11 @@ __global__ __launch_bounds__(256, KV8 ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a)
             qv[v * 8 + 2 * q + 1] = mmi_bf16_to_f32((uint16_t)(qq[q] >> 16));
         }
     }
-    auto widen = [](const u32x4& r, float* f) {
-        if constexpr (KV8) {
+    auto widen = [](const u32x4& r, uint32_t sc2, float* f) {
+        if constexpr (KV4) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) mmi_kv4_widen8(r[q], (sc2 >> (8 * (q >> 1))) & 0xffu, f + 8 * q);
+        } else if constexpr (KV8) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) mmi_fp8x4_to_f32(r[q], f + 4 * q);
         } else {
@@ -2130,23 +2266,35 @@ __global__ __launch_bounds__(256, KV8 ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a)
         }
     };
     // wave-uniform base (scalar registers) + a 32-bit lane offset: the loads take the saddr form, no 64-bit address per lane
-    const uint8_t* kbase = reinterpret_cast<const uint8_t*>(a.kc) + (long)bh * a.cap * DH * ES;
-    const uint8_t* vbase = reinterpret_cast<const uint8_t*>(a.vc) + (long)bh * a.cap * DH * ES;
-    const unsigned loff = (unsigned)(seg * EPL * ES);
+    const uint8_t* kbase = reinterpret_cast<const uint8_t*>(a.kc) + (long)bh * a.cap * ROWB;
+    const uint8_t* vbase = reinterpret_cast<const uint8_t*>(a.vc) + (long)bh * a.cap * ROWB;
+    const unsigned loff = (unsigned)(seg * 16);
+    // 4-bit ring: the scale planes (DH / 16 bytes per row, two per lane), wave-uniform bases as well
+    const uint8_t* ksbase = reinterpret_cast<const uint8_t*>(a.kc) + a.kv_soff + (long)bh * a.cap * (DH / 16);
+    const uint8_t* vsbase = reinterpret_cast<const uint8_t*>(a.vc) + a.kv_soff + (long)bh * a.cap * (DH / 16);
+    const unsigned lsoff = (unsigned)(seg * 2);
     const float scale = 1.0f / sqrtf((float)DH);
     // One workgroup per (session, head) (gridDim.y == 1: which wave walks which row group does not depend on the ring depth): the
     // FIRST round's keys and values are requested before the session's offset - a cold scalar load of its own, ~1 us into a
     // ~40 us launch - has come back: row groups wave, wave + 4, ... of the ring's first slots, any of which lies inside the
     // allocation; rows past the valid part are masked where they are used (slot < L), as the clamped re-reads always were
     u32x4 kA[NB], vA[NB], kB[NB], vB[NB];
+    uint32_t ksA[NB], vsA[NB], ksB[NB], vsB[NB];      // 4-bit ring only: the rows' scale byte pairs
+#pragma unroll
+    for (int i = 0; i < NB; ++i) ksA[i] = vsA[i] = ksB[i] = vsB[i] = 0u;
     const bool early = gridDim.y == 1;
     if (early) {
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             const int slot_ = min((wave + i * 4) * RPW + rsub, a.cap - 1);
-            const unsigned o_ = (unsigned)slot_ * (unsigned)(DH * ES) + loff;
+            const unsigned o_ = (unsigned)slot_ * (unsigned)ROWB + loff;
             kA[i] = *reinterpret_cast<const u32x4*>(kbase + o_);
             vA[i] = *reinterpret_cast<const u32x4*>(vbase + o_);
+            if constexpr (KV4) {
+                const unsigned so_ = (unsigned)slot_ * (unsigned)(DH / 16) + lsoff;
+                ksA[i] = *reinterpret_cast<const uint16_t*>(ksbase + so_);
+                vsA[i] = *reinterpret_cast<const uint16_t*>(vsbase + so_);
+            }
         }
     }
     // context >= capacity (the LM's ring: both 3000): every written slot is inside the window - slot s < L holds a position p with
@@ -2168,14 +2316,19 @@ __global__ __launch_bounds__(256, KV8 ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a)
     for (int e = 0; e < EPL; ++e) acc[e] = 0.f;
     // every load is unconditional from a clamped (valid) slot - a load under a branch would be serialised behind
     // s_waitcnt vmcnt(0) - and rows past the end carry probability 0
-#define MMI_AW_LOAD(KK, VV, j0)                                                                  \
+#define MMI_AW_LOAD(KK, VV, KS, VS, j0)                                                          \
     _Pragma("unroll") for (int i = 0; i < NB; ++i) {                                            \
         const int slot_ = min((wg + ((j0) + i) * total) * RPW + rsub, L - 1);                   \
-        const unsigned o_ = (unsigned)slot_ * (unsigned)(DH * ES) + loff;                       \
+        const unsigned o_ = (unsigned)slot_ * (unsigned)ROWB + loff;                            \
         KK[i] = *reinterpret_cast<const u32x4*>(kbase + o_);                                    \
         VV[i] = *reinterpret_cast<const u32x4*>(vbase + o_);                                    \
+        if constexpr (KV4) {                                                                     \
+            const unsigned so_ = (unsigned)slot_ * (unsigned)(DH / 16) + lsoff;                 \
+            KS[i] = *reinterpret_cast<const uint16_t*>(ksbase + so_);                           \
+            VS[i] = *reinterpret_cast<const uint16_t*>(vsbase + so_);                           \
+        }                                                                                        \
     }
-#define MMI_AW_USE(KK, VV, j0)                                                                   \
+#define MMI_AW_USE(KK, VV, KS, VS, j0)                                                                 \
     {                                                                                            \
         float s_[NB];                                                                            \
         float mx_ = -INFINITY;                                                                   \
@@ -2190,9 +2343,9 @@ __global__ __launch_bounds__(256, KV8 ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a)
                 valid_ = pos_ >= 0 && dq_ >= 0 && dq_ < a.context;                               \
             }                                                                                    \
             float dot_ = 0.f;                                                                    \
-            if constexpr (KV8) {                                                                 \
+            if constexpr (KVF != 0) {                                                            \
                 float kf_[EPL];                                                                  \
-                widen(KK[i], kf_);                                                               \
+                widen(KK[i], KS[i], kf_);                                                              \
                 _Pragma("unroll") for (int e = 0; e < EPL; ++e) dot_ = mmi_fma(qv[e], kf_[e], dot_); \
             } else {                    /* 4 packed-pair dot products instead of 8 unpacks + 8 FMAs */ \
                 _Pragma("unroll") for (int q = 0; q < 4; ++q) dot_ = mmi_dot2_bf16(KK[i][q], qp[q], dot_); \
@@ -2209,9 +2362,9 @@ __global__ __launch_bounds__(256, KV8 ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a)
             _Pragma("unroll") for (int i = 0; i < NB; ++i) {                                    \
                 const float p_ = expf(s_[i] - m_new_);        /* exp(-inf) = 0 for masked rows */ \
                 l_run += p_;                                                                     \
-                if constexpr (KV8) {                                                             \
+                if constexpr (KVF != 0) {                                                        \
                     float vf_[EPL];                                                              \
-                    widen(VV[i], vf_);                                                           \
+                    widen(VV[i], VS[i], vf_);                                                         \
                     _Pragma("unroll") for (int e = 0; e < EPL; ++e) acc[e] = mmi_fma(p_, vf_[e], acc[e]); \
                 } else {                /* packed FMAs: two accumulator elements per instruction */ \
                     const f32x2 pp_ = {p_, p_};                                                  \
@@ -2227,12 +2380,12 @@ __global__ __launch_bounds__(256, KV8 ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a)
         }                                                                                        \
     }
     if (nrounds > 0) {
-        if (!early) { MMI_AW_LOAD(kA, vA, 0) }
+        if (!early) { MMI_AW_LOAD(kA, vA, ksA, vsA, 0) }
         for (int r = 0; r < nrounds; r += 2) {
-            MMI_AW_LOAD(kB, vB, (r + 1) * NB)          // clamped past the end: re-reads the last row (cache hit), masked on use
-            MMI_AW_USE(kA, vA, r * NB)
-            MMI_AW_LOAD(kA, vA, (r + 2) * NB)
-            MMI_AW_USE(kB, vB, (r + 1) * NB)
+            MMI_AW_LOAD(kB, vB, ksB, vsB, (r + 1) * NB)          // clamped past the end: re-reads the last row (cache hit), masked on use
+            MMI_AW_USE(kA, vA, ksA, vsA, r * NB)
+            MMI_AW_LOAD(kA, vA, ksA, vsA, (r + 2) * NB)
+            MMI_AW_USE(kB, vB, ksB, vsB, (r + 1) * NB)
         }
     }
 #undef MMI_AW_LOAD

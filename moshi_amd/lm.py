@@ -40,9 +40,12 @@ def _lm_cfg_struct(cfg: LMConfig) -> _capi.LMCfg:
     s.existing_text_padding_id = cfg.existing_text_padding_id
     s.extra_heads_num_heads = cfg.extra_heads_num_heads
     s.extra_heads_dim = cfg.extra_heads_dim
-    if cfg.kv_cache_dtype not in ("bf16", "fp8"):
-        raise ValueError("kv_cache_dtype must be 'bf16' or 'fp8'")
-    s.kv_cache_dtype = _capi.MMI_F8E4M3 if cfg.kv_cache_dtype == "fp8" else _capi.MMI_BF16
+    if cfg.kv_cache_dtype not in ("bf16", "fp8", "fp4"):
+        raise ValueError("kv_cache_dtype must be 'bf16', 'fp8' or 'fp4'")
+    if cfg.kv_cache_dtype == "fp4" and (cfg.dim // cfg.num_heads) % 32:
+        raise ValueError(f"kv_cache_dtype 'fp4' needs a head dim multiple of 32 (a 16-byte load of the ring is two blocks of 16): "
+                         f"dim {cfg.dim} / num_heads {cfg.num_heads} = {cfg.dim // cfg.num_heads}")
+    s.kv_cache_dtype = {"bf16": _capi.MMI_BF16, "fp8": _capi.MMI_F8E4M3, "fp4": _capi.MMI_F4E2M1X2}[cfg.kv_cache_dtype]
     s.cross_attention = 1 if cfg.cross_attention else 0
     return s
 
@@ -137,7 +140,8 @@ class LMModel:
                 raise ValueError("max_rows must be >= 1")
             max_batch = int(max_rows)
         self.config = config or LMConfig()
-        if kv_cache is not None:         # "fp8": e4m3 KV ring (half the attention stream); default: the config's (bf16)
+        if kv_cache is not None:         # "fp8": e4m3 KV ring (half the attention stream); "fp4": E2M1 codes under block scales
+                                         # (0.5625 bytes per element); default: the config's (bf16)
             from dataclasses import replace
             self.config = replace(self.config, kv_cache_dtype=kv_cache)
         self.fuser = fuser
@@ -255,6 +259,18 @@ class LMModel:
         self._lib.check(self._lib.mmi_lm_set_hidden_taps(self._handle, 1 if on else 0))
 
     DEBUG_PATHS = {"plain": 0, "splitk": 1, "fused": 2, "norm": 3, "norm_fused": 4}
+
+    def debug_kv4_quantize(self, x: torch.Tensor):
+        """Test aid (`mmi_lm_debug_kv4_quantize`): the device quantiser of the 4-bit KV ring on bf16 rows [n, 16 * m] ->
+        (codes uint8 [n, 8 * m], scale bytes uint8 [n, m])."""
+        x = x.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        assert x.dim() == 2 and x.shape[1] % 16 == 0, "rows of whole blocks of 16"
+        n, m = x.shape[0], x.shape[1] // 16
+        codes = torch.empty(n, 8 * m, dtype=torch.uint8, device=self.device)
+        scales = torch.empty(n, m, dtype=torch.uint8, device=self.device)
+        self._lib.check(self._lib.mmi_lm_debug_kv4_quantize(self._handle, x.data_ptr(), n, m, codes.data_ptr(), scales.data_ptr(),
+                                                            _capi.stream_ptr(self.device)))
+        return codes, scales
 
     def debug_linear(self, weight_name: str, x: torch.Tensor, path: str = "plain", alpha_name: Optional[str] = None,
                      want_codes: bool = False) -> dict:
@@ -885,6 +901,21 @@ class LMGen:
         assert len(offs) == self._batch
         arr = (C.c_int64 * len(offs))(*offs)
         self._lib.check(self._lib.mmi_lm_seek(self.lm_model._handle, C.cast(arr, C.c_void_p), self._stream()))
+
+    def kv_ring(self, layer: int, which: str = "k") -> torch.Tensor:
+        """Test aid (`mmi_lm_debug_kv_ring`): the raw bytes of temporal layer `layer`'s key ("k") or value ("v") ring, a uint8 copy.
+        bf16 ring: [rows, H, cap, Dh] bf16 as bytes; "fp8": the same in e4m3 bytes; "fp4": the codes plane [rows, H, cap, Dh/2]
+        followed by the scale plane [rows, H, cap, Dh/16] (rows = model rows: sessions, then their guidance twins)."""
+        assert self.is_streaming
+        h = self.lm_model._handle
+        n = int(self._lib.mmi_lm_debug_kv_ring(h, int(layer), {"k": 0, "v": 1}[which], None, 0, self._stream()))
+        if n < 0:
+            self._lib.check(n)
+        buf = torch.empty(n, dtype=torch.uint8, device=self.device)
+        got = int(self._lib.mmi_lm_debug_kv_ring(h, int(layer), {"k": 0, "v": 1}[which], buf.data_ptr(), n, self._stream()))
+        if got < 0:
+            self._lib.check(got)
+        return buf
 
     def hidden_taps(self) -> torch.Tensor:
         """Parity tap (tests): the residual stream of the LAST step after the first and after the last temporal layer, bf16
