@@ -614,6 +614,29 @@ int mmi_lm_debug_linear_lora(mmi_lm* lm, const char* weight_name, const char* al
 int mmi_lm_debug_kv4_quantize(mmi_lm* lm, const void* x_bf16, int32_t n, int32_t m, void* codes_u8, void* scales_u8, mmi_stream stream);
 int64_t mmi_lm_debug_kv_ring(mmi_lm* lm, int32_t layer, int32_t which, void* dst, int64_t nbytes, mmi_stream stream);
 
+/* Parity tap of the temporal decode attention (tests; no reference counterpart): the attention op of a temporal layer - the
+ * launches the step makes for it, through the step's own dispatch - on caller-supplied operands, so that the kernels can be held
+ * to an exact softmax on their own.  Works on any handle and touches no stream state: the partials, the (zeroed) arrival counters
+ * and the packed output live in scratch of the call.  The caller sets everything a handle's model would otherwise fix:
+ *   q        device bf16 [rows][H][Dh], taken as already roped (16-byte aligned)
+ *   k, v     device bytes, the layout of mmi_lm_debug_kv_ring for a ring of `cap` slots (16-byte aligned): kv_dtype MMI_BF16
+ *            [rows][H][cap][Dh] bf16, MMI_F8E4M3 the same in bytes, MMI_F4E2M1X2 the codes plane, then the scale plane
+ *   offsets  device int64 [rows], >= 0: row b attends from position offsets[b], which sits in slot offsets[b] % cap
+ *   H, Dh (32, 64 or 128), cap, context (1 <= context <= cap): context < cap is a ring longer than its attention window
+ *   kernel   MMI_ATTN_WAVE (k_lm_attn_wave) or MMI_ATTN_SPLIT (k_lm_attn_split, the chunked kernel)
+ *   NS       1 .. 16 workgroups per (row, head)
+ *   merge    NS > 1: MMI_ATTN_MERGE_LAUNCH = every workgroup leaves its partial and k_lm_attn_combine follows (solo_rows is not
+ *            read); MMI_ATTN_MERGE_KERNEL (k_lm_attn_wave only) = rings of at most solo_rows rows are walked by workgroup 0
+ *            alone, deeper ones are merged by the workgroup that arrives last
+ *   out      device bf16 [rows][H * Dh], row-major: unpacked from the packed activation layout that out_proj reads
+ * Refuses (MMI_ERR_SHAPE / MMI_ERR_UNSUPPORTED) another head dim, rows above the handle's max_batch, a 4-bit ring whose head dim
+ * is no multiple of 32, and operands aligned below what the vector loads need.  Synchronises `stream`. */
+enum { MMI_ATTN_WAVE = 0, MMI_ATTN_SPLIT = 1 };
+enum { MMI_ATTN_MERGE_LAUNCH = 0, MMI_ATTN_MERGE_KERNEL = 1 };
+int mmi_lm_debug_attn(mmi_lm* lm, const void* q_bf16, const void* k_ring, const void* v_ring, const int64_t* offsets, int32_t rows,
+                      int32_t H, int32_t Dh, int32_t cap, int32_t context, int32_t kv_dtype, int32_t kernel, int32_t NS, int32_t merge,
+                      int32_t solo_rows, void* out_bf16, mmi_stream stream);
+
 /* The launch list of one frame step, recorded while the step ran for the first time: one line "site<TAB>kernel[<TAB>weight bytes]" per kernel
  * launch in launch order (sites: "L.in_proj", "L.ffn_in", "dep.out_proj", "text_linear", ...).  scripts/rocpd_sites.py joins
  * it with a rocprofv3 kernel trace by position inside the step, which is how per-site durations of kernels that share one

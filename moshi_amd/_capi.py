@@ -206,6 +206,8 @@ SIGNATURES = {
     "mmi_lm_debug_linear_lora": (C.c_int, [_P, C.c_char_p, C.c_char_p, C.c_int32, _P, C.c_int32, _P, _P, _P, _P, C.POINTER(C.c_int32), _P]),
     "mmi_lm_debug_kv4_quantize": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P]),
     "mmi_lm_debug_kv_ring": (C.c_int64, [_P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
+    "mmi_lm_debug_attn": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_int32, C.c_int32, _P, _P]),
     "mmi_lm_enable_adapters": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "mmi_lm_load_adapter": (C.c_int, [_P, C.c_int32, C.c_float, C.POINTER(TensorDesc), C.c_int32, _P]),
     "mmi_lm_unload_adapter": (C.c_int, [_P, C.c_int32, _P]),
@@ -239,10 +241,12 @@ _SINCE_ADAPTERS = ("mmi_lm_debug_linear_lora", "mmi_lm_enable_adapters", "mmi_lm
 _SINCE_NUCLEUS = ("mmi_lm_enable_nucleus", "mmi_lm_set_top_p", "mmi_lm_top_p", "mmi_lm_nucleus_enabled", "mmi_lm_set_row_top_p",
                   "mmi_lm_clear_row_top_p", "mmi_batcher_set_channel_top_p")
 _SINCE_KV4 = ("mmi_lm_debug_kv4_quantize", "mmi_lm_debug_kv_ring")
+_SINCE_ATTN_TAP = ("mmi_lm_debug_attn",)
 
 
 def _missing(name, path):
-    what = ("the 4-bit KV ring" if name in _SINCE_KV4 else
+    what = ("the attention tap" if name in _SINCE_ATTN_TAP else
+            "the 4-bit KV ring" if name in _SINCE_KV4 else
             "nucleus sampling" if name in _SINCE_NUCLEUS else
             "per-session adapters" if name in _SINCE_ADAPTERS else
             "handles above 64 model rows" if name in _SINCE_MANY_ROWS else
@@ -261,7 +265,7 @@ class Lib:
         self.path = Path(path)
         self.cdll = C.CDLL(str(self.path))
         for name, (res, args) in SIGNATURES.items():
-            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION + _SINCE_TTS_MACHINE + _SINCE_MANY_ROWS + _SINCE_ADAPTERS + _SINCE_NUCLEUS + _SINCE_KV4 and not hasattr(self.cdll, name):
+            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION + _SINCE_TTS_MACHINE + _SINCE_MANY_ROWS + _SINCE_ADAPTERS + _SINCE_NUCLEUS + _SINCE_KV4 + _SINCE_ATTN_TAP and not hasattr(self.cdll, name):
                 # an older build of the engine (MMI_LIB_PATH, A/B runs against a parent build): everything else works, these refuse
                 setattr(self, name, _missing(name, self.path))
                 continue

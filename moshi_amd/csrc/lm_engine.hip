@@ -1198,6 +1198,18 @@ int launch_attn_split(hipStream_t s, const LmAttnArgs& a, int kvf, bool wave) {
     return MMI_OK;
 }
 
+// The L.attn op (and mmi_lm_debug_attn): the attention launch and, with merge_launch, the merge of the workgroups' partials as a
+// launch of its own
+int launch_attn(hipStream_t s, const LmAttnArgs& a, int kvf, bool wave, bool merge_launch) {
+    LmAttnArgs aa = a;
+    if (merge_launch) { aa.solo_rows = -1; aa.done = nullptr; }     // every workgroup leaves its partial (m, l, O)
+    int rc = launch_attn_split(s, aa, kvf, wave);
+    if (rc) return rc;
+    if (merge_launch) MMI_LAUNCH(k_lm_attn_combine, aa.B * aa.H, aa.Dh < 64 ? 64 : aa.Dh, 0, s, aa);
+    MMI_CHECK_LAUNCH();
+    return (int)MMI_OK;
+}
+
 TokArgs tok_args(mmi_lm* lm) {
     TokArgs t;
     t.cache = lm->cache; t.offsets = lm->offsets; t.exec = lm->exec; t.delays = lm->delays_dev;
@@ -1276,16 +1288,7 @@ int build_program(mmi_lm* lm) {
         }
         P.site("L.attn");
         const bool wave = attn_wave_kernel(lm->knobs);
-        P.add([=](hipStream_t s) {
-            LmAttnArgs aa = a;
-            const bool merge_launch = a.NS > 1 && (!wave || lm->prog.variant == 1);
-            if (merge_launch) { aa.solo_rows = -1; aa.done = nullptr; }     // every workgroup leaves its partial (m, l, O)
-            int rc = launch_attn_split(s, aa, kvf, wave);
-            if (rc) return rc;
-            if (merge_launch) MMI_LAUNCH(k_lm_attn_combine, B * H, Dh < 64 ? 64 : Dh, 0, s, aa);
-            MMI_CHECK_LAUNCH();
-            return (int)MMI_OK;
-        });
+        P.add([=](hipStream_t s) { return launch_attn(s, a, kvf, wave, a.NS > 1 && (!wave || lm->prog.variant == 1)); });
         P.site("L.out_proj");
         if (a8) {
             add_quant_rows(lm, lm->att, lm->attq, lm->sx_att, d);
@@ -3082,6 +3085,72 @@ extern "C" int mmi_lm_debug_linear_lora(mmi_lm* lm, const char* weight_name, con
                                         mmi_stream stream) {
     if (!row_slots) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_linear_lora: null row_slots");
     return debug_linear_impl(lm, weight_name, alpha_name, path, x_bf16, rows, out_bf16, codes, absmax, norm_out, row_slots, stream);
+}
+
+// Parity tap of the temporal decode attention (include/moshi_mi.h): launch_attn - the L.attn op - on caller-supplied operands, with
+// scratch of its own for the partials, the arrival counters and the packed output.  Nothing of the handle but its device, its row
+// limit and its poison knob is read.
+extern "C" int mmi_lm_debug_attn(mmi_lm* lm, const void* q_bf16, const void* k_ring, const void* v_ring, const int64_t* offsets, int32_t rows,
+                                 int32_t H, int32_t Dh, int32_t cap, int32_t context, int32_t kv_dtype, int32_t kernel, int32_t NS, int32_t merge,
+                                 int32_t solo_rows, void* out_bf16, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm || !q_bf16 || !k_ring || !v_ring || !offsets || !out_bf16) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (kv_dtype != MMI_BF16 && kv_dtype != MMI_F8E4M3 && kv_dtype != MMI_F4E2M1X2)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_attn: the ring is bf16, e4m3 or 4-bit (MMI_F4E2M1X2)");
+    const int kvf = kv_form(kv_dtype);
+    if (kvf == 2 && Dh % 32 != 0) return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_attn: a 4-bit ring needs a head dim that is a multiple of 32");
+    if (Dh != 32 && Dh != 64 && Dh != 128) return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_attn: head dim must be 32, 64 or 128");
+    if (rows <= 0 || rows > lm->max_batch) return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_attn: rows must be 1..max_batch");
+    if (H <= 0 || H > 1024 || cap <= 0 || cap > (1 << 20) || context <= 0 || context > cap)
+        return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_attn: 1 <= H <= 1024, 1 <= context <= cap <= 2^20");
+    if (NS < 1 || NS > 16) return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_attn: 1 <= NS <= 16");
+    if ((kernel != MMI_ATTN_WAVE && kernel != MMI_ATTN_SPLIT) || (merge != MMI_ATTN_MERGE_LAUNCH && merge != MMI_ATTN_MERGE_KERNEL))
+        return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_attn: unknown kernel or merge");
+    const bool wave = kernel == MMI_ATTN_WAVE;
+    if (!wave && NS > 1 && merge == MMI_ATTN_MERGE_KERNEL)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_attn: only k_lm_attn_wave merges its partials itself");
+    // 16-byte loads of the query and of ring rows (a row is a multiple of 16 bytes; so is a 4-bit codes plane, which puts the 2-byte
+    // scale loads on even addresses); 8-byte offsets; bf16 stores
+    if (((uintptr_t)q_bf16 | (uintptr_t)k_ring | (uintptr_t)v_ring) % 16 || (uintptr_t)offsets % 8 || (uintptr_t)out_bf16 % 2)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_attn: q, k and v must be 16-byte aligned, offsets 8-byte, out 2-byte");
+    hipStream_t s = (hipStream_t)stream;
+    // an offset below 0 would put the clamped loads in front of the ring
+    std::vector<int64_t> off((size_t)rows);
+    MMI_HIP_CHECK(hipStreamSynchronize(s));
+    MMI_HIP_CHECK(hipMemcpy(off.data(), offsets, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToHost));
+    for (int b = 0; b < rows; ++b)
+        if (off[b] < 0) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_attn: negative offset");
+    const int d = H * Dh, T = rows <= 16 ? 16 : 32, mt = mmi_cdiv(rows, T), ksteps = mmi_cdiv(d, mmi_kstep(T));
+    const size_t pairs = (size_t)rows * H, oelems = (size_t)mt * ksteps * 512;
+    MmiArena A;
+    A.poison = lm->knobs.debug_poison;
+    float *opart = nullptr, *ml = nullptr;
+    unsigned* arrived = nullptr;
+    uint16_t* att = nullptr;
+    bool ok = true;
+    ok &= hipSuccess == A.alloc(&opart, pairs * NS * Dh);
+    ok &= hipSuccess == A.alloc(&ml, pairs * NS * 2);
+    ok &= hipSuccess == A.alloc(&arrived, pairs);
+    ok &= hipSuccess == A.alloc(&att, oelems);
+    auto done = [&](int rc) { hipStreamSynchronize(s); A.release(); return rc; };
+    if (!ok) return done(mmi_fail(MMI_ERR_HIP, "out of device memory (mmi_lm_debug_attn)"));
+    MMI_DBG_HIP(hipMemsetAsync(arrived, 0, pairs * sizeof(unsigned), s));
+    MMI_DBG_HIP(hipMemsetAsync(att, 0, oelems * 2, s));
+    LmAttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.qrot = (uint16_t*)q_bf16; a.kc = (uint16_t*)k_ring; a.vc = (uint16_t*)v_ring;
+    a.offsets = reinterpret_cast<const long*>(offsets); a.opart = opart; a.ml = ml; a.out = att;
+    a.B = rows; a.H = H; a.Dh = Dh; a.cap = cap; a.context = context; a.NS = NS;
+    a.T = T; a.out_ksteps = ksteps;
+    a.done = arrived; a.solo_rows = solo_rows;
+    a.kv_soff = kvf == 2 ? (long)pairs * cap * Dh / 2 : 0;
+    int rc = launch_attn(s, a, kvf, wave, NS > 1 && merge == MMI_ATTN_MERGE_LAUNCH);
+    if (rc) return done(rc);
+    MMI_LAUNCH(k_unpack_rows, mmi_cdiv(rows * d, 256), 256, 0, s, (const uint16_t*)att, rows, d, (uint16_t*)out_bf16, T, ksteps);
+    MMI_DBG_LAUNCHED();
+    if (hipStreamSynchronize(s) != hipSuccess) { A.release(); return mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_attn: the launches failed"); }
+    A.release();
+    return MMI_OK;
 }
 
 extern "C" int64_t mmi_lm_stat(const mmi_lm* lm, int32_t which) {

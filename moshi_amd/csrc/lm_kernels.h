@@ -2043,8 +2043,9 @@ struct LmAttnArgs {
 // KV8: the ring holds e4m3 bytes (fp8 KV cache): a 16-byte load then covers 16 dims, DH/16 lanes share a row and one wave
 // instruction reads twice as many rows; the values are widened exactly (v_cvt_pk_f32_fp8) and everything else is unchanged.
 // KVF = 2: the 4-bit ring (mmi_fp4.h): a 16-byte load covers 32 dims = two blocks, and a 2-byte load beside it their two
-// scale bytes; DH/32 lanes share a row; widened exactly (v_cvt_scalef32_pk_f32_fp4), scores, softmax and P.V stay fp32.  Rows past
-// the valid length hold scale byte 0 (the ring is zeroed at streaming_start) and reach the FMA as 0 * p with p = 0.
+// scale bytes; DH/32 lanes share a row; widened exactly (v_cvt_scalef32_pk_f32_fp4), scores, softmax and P.V stay fp32.
+// No load reaches a slot past the valid length (every one is clamped to L - 1; the clamped re-reads carry p = 0): the result does not
+// depend on what a never-written slot holds.  A slot that is written but masked by the window is used as 0 * v and needs a finite v.
 template <int DH, int KVF = 0>
 __global__ __launch_bounds__(256) void k_lm_attn_split(LmAttnArgs a) {
     constexpr bool KV8 = KVF == 1, KV4 = KVF == 2;
@@ -2163,7 +2164,7 @@ __global__ __launch_bounds__(256) void k_lm_attn_split(LmAttnArgs a) {
         m_run = m_new;
 #pragma unroll
         for (int e = 0; e < EPL; ++e) acc[e] *= resc;
-        // ---- P.V (value rows requested up front as well; rows past L carry p = 0 and finite ring contents)
+        // ---- P.V (value rows requested up front as well, clamped to L - 1 like the keys: the re-read rows past L carry p = 0)
 #pragma unroll 1
         for (int h0 = 0; h0 < NIT; h0 += NB) {
             u32x4 vv[NB];
@@ -2277,7 +2278,8 @@ __global__ __launch_bounds__(256, KVF ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a)
     // One workgroup per (session, head) (gridDim.y == 1: which wave walks which row group does not depend on the ring depth): the
     // FIRST round's keys and values are requested before the session's offset - a cold scalar load of its own, ~1 us into a
     // ~40 us launch - has come back: row groups wave, wave + 4, ... of the ring's first slots, any of which lies inside the
-    // allocation; rows past the valid part are masked where they are used (slot < L), as the clamped re-reads always were
+    // allocation; rows past the valid part are masked where they are used (slot < L), as the clamped re-reads always were, and
+    // their values are zeroed below once L is known
     u32x4 kA[NB], vA[NB], kB[NB], vB[NB];
     uint32_t ksA[NB], vsA[NB], ksB[NB], vsB[NB];      // 4-bit ring only: the rows' scale byte pairs
 #pragma unroll
@@ -2296,6 +2298,15 @@ __global__ __launch_bounds__(256, KVF ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a)
                 vsA[i] = *reinterpret_cast<const uint16_t*>(vsbase + so_);
             }
         }
+    }
+    // The early loads came from slots up to cap - 1, whatever the ring holds there.  A slot that was never written (>= L) is used as
+    // p * v with p = 0, which is 0 only for a finite v: once per launch - not per round - such a value row reads as zeros (4-bit
+    // ring: scale byte 0 = the factor 0), so the result does not depend on what an unwritten slot holds (its key only feeds a score
+    // that the mask replaces).  Every later load is clamped to L - 1.
+    if (early) {
+#pragma unroll
+        for (int i = 0; i < NB; ++i)
+            if ((wave + i * 4) * RPW + rsub >= L) { vA[i] = u32x4{0u, 0u, 0u, 0u}; vsA[i] = 0u; }
     }
     // context >= capacity (the LM's ring: both 3000): every written slot is inside the window - slot s < L holds a position p with
     // 0 <= offset - p < cap - so the mask (transformer.py:574-582) reduces to `slot < L` and the per-row position arithmetic is

@@ -272,6 +272,31 @@ class LMModel:
                                                             _capi.stream_ptr(self.device)))
         return codes, scales
 
+    ATTN_RING_FORMS = {"bf16": _capi.MMI_BF16, "fp8": _capi.MMI_F8E4M3, "fp4": _capi.MMI_F4E2M1X2}
+
+    def debug_attn(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, offsets: torch.Tensor, cap: int, context: Optional[int] = None,
+                   ring: str = "bf16", kernel: str = "wave", ns: int = 1, merge: str = "launch", solo_rows: int = -1) -> torch.Tensor:
+        """Parity tap (tests; `mmi_lm_debug_attn`): the temporal decode attention alone, through the step's own dispatch, on
+        caller-supplied operands.  `q` bf16 [rows, H, Dh] (already roped); `k`, `v` uint8, the ring bytes in the layout of
+        `debug_kv_ring` for `cap` slots (bf16 [rows, H, cap, Dh]; "fp8" the same in bytes; "fp4" the codes plane, then the scale
+        plane); `offsets` int64 [rows].  `kernel` "wave" / "split", `ns` workgroups per (row, head), `merge` "launch"
+        (`k_lm_attn_combine`) or "kernel" (the last-arriving workgroup; rings of at most `solo_rows` rows are walked by workgroup 0
+        alone).  Returns bf16 [rows, H * Dh].  Independent of the handle's model and of any running stream."""
+        q = q.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        rows, H, Dh = q.shape
+        k, v = (t.to(device=self.device).contiguous().view(torch.uint8).reshape(-1) for t in (k, v))
+        per_elem = {"bf16": 32, "fp8": 16, "fp4": 9}[ring]                 # sixteenths of a byte
+        want = rows * H * int(cap) * Dh * per_elem // 16
+        assert k.numel() == want and v.numel() == want, f"a {ring} ring of {rows} x {H} x {cap} x {Dh} is {want} bytes, got {k.numel()} / {v.numel()}"
+        offsets = offsets.to(device=self.device, dtype=torch.int64).contiguous()
+        assert offsets.shape == (rows,), "one offset per row"
+        out = torch.empty(rows, H * Dh, dtype=torch.bfloat16, device=self.device)
+        self._lib.check(self._lib.mmi_lm_debug_attn(
+            self._handle, q.data_ptr(), k.data_ptr(), v.data_ptr(), offsets.data_ptr(), rows, H, Dh, int(cap),
+            int(cap if context is None else context), self.ATTN_RING_FORMS[ring], {"wave": 0, "split": 1}[kernel], int(ns),
+            {"launch": 0, "kernel": 1}[merge], int(solo_rows), out.data_ptr(), _capi.stream_ptr(self.device)))
+        return out
+
     def debug_linear(self, weight_name: str, x: torch.Tensor, path: str = "plain", alpha_name: Optional[str] = None,
                      want_codes: bool = False) -> dict:
         """Parity tap (tests; `mmi_lm_debug_linear`): ONE linear of the model - the module stored under `weight_name`, i.e.
