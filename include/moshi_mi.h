@@ -297,7 +297,7 @@ int mmi_mimi_device(const mmi_mimi* m);
  * both are from the stream's first step on, so that the switch is never a capture inside a live session; 2: the host's bound on
  * the ring depth (steps since streaming_start / seek / the offsets of a restored snapshot); 3: the depth transformer's MFMA tile
  * (16 at <= 32 sessions with bf16 weights, else 32); 4: GEMM launches (or captured graph nodes) that took k_gemm_rows (more
- * than 64 model rows). */
+ * than 64 model rows).  0 and 4 count the GEMMs of mmi_lm_prefill passes as well as those of steps. */
 int64_t mmi_lm_stat(const mmi_lm* lm, int32_t which);
 /* LMGen.step_with_extra_heads (lm.py:793-807): softmax(extra_head(transformer_out)) of the LAST step for every head:
  * probs f32 [model rows, extra_heads_num_heads, extra_heads_dim]. */
@@ -636,6 +636,73 @@ enum { MMI_ATTN_MERGE_LAUNCH = 0, MMI_ATTN_MERGE_KERNEL = 1 };
 int mmi_lm_debug_attn(mmi_lm* lm, const void* q_bf16, const void* k_ring, const void* v_ring, const int64_t* offsets, int32_t rows,
                       int32_t H, int32_t Dh, int32_t cap, int32_t context, int32_t kv_dtype, int32_t kernel, int32_t NS, int32_t merge,
                       int32_t solo_rows, void* out_bf16, mmi_stream stream);
+
+/* ---- chunked prefill of known frames into a live session (no reference counterpart) ----------------------------
+ * mmi_lm_prefill on sessions S with T frames equals T calls of mmi_lm_step under an exec mask that holds exactly the sessions of S,
+ * each preceded by mmi_lm_force_next_tokens with every entry of those sessions' rows >= 0, the previous exec mask restored
+ * afterwards - except that
+ *   1. no logits, no tokens and no output frame are produced: the text head, the depth transformer, the samplers and the extra
+ *      heads do not run;
+ *   2. the handle-wide draw counter does not advance and the depth transformer's per-frame cache is not touched: what a neighbour
+ *      samples does not depend on whether a session was prefilled between two steps;
+ *   3. the temporal K/V rings of layers >= 1 may differ from the stepped ones by attention summation order; everything else in the
+ *      streaming state of the named sessions is what stepping leaves, bit for bit (offsets, the token delay ring, the text history
+ *      of rows with sampling settings of their own, the last stored tokens);
+ *   4. sessions not in S are untouched, byte for byte.
+ * 128 known frames of one session cost one pass over the temporal weights instead of 128.
+ *
+ * mmi_lm_enable_prefill(lm, rows): before streaming_start, like mmi_lm_enable_nucleus.  rows = the row budget of one pass, 1..128
+ * (0 = off again); the next streaming_start allocates the scratch of a pass beside - not inside - the streaming-state arena:
+ * mmi_lm_state_bytes and snapshots are unchanged, and a handle that never enables it allocates nothing, launches nothing new and
+ * runs the device code it ran before.  Refused with MMI_ERR_UNSUPPORTED (the message names the reason; nothing is written):
+ * rows > 128; rows > 32 on a handle whose weights are packed at the 16-row tile (max_batch <= 16); quantised linears (int8, fp8,
+ * MXFP4); cross-attention layers; an adapter handle; a handle with the TTS machine enabled; a head dim other than 32 / 64 / 128.
+ * (A guided stream and per-step hooks are properties of a stream, not of the handle: mmi_lm_prefill refuses those, below; adapters or
+ * the TTS machine enabled after this call are refused by the next streaming_start.)  MMI_ERR_STATE while streaming.
+ *
+ * mmi_lm_prefill(lm, sessions, n, user_codes, tokens, T, stream): stream ordered, no synchronisation.
+ *   sessions    HOST int32 [n]: distinct indices in [0, streaming batch); 1 <= n <= rows.  They may stand at any offsets, and at
+ *               different ones; continuing a live session is allowed
+ *   user_codes  device i64 [n][n_q - dep_q][T]: what mmi_lm_step takes, per frame (NULL where the model has no user stream)
+ *   tokens      device i64 [n][1 + dep_q][T]: what mmi_lm_force_next_tokens takes, per frame; every entry >= 0
+ *   T           >= 1; cut into passes of floor(rows / n) frames.  A pass may straddle the ring's wrap and T may exceed the context
+ * MMI_ERR_STATE: not streaming, or prefill not enabled.  MMI_ERR_INVALID: a session out of range or named twice, T < 1, more
+ * sessions than rows.  MMI_ERR_UNSUPPORTED: a guided stream, or per-step hooks installed.
+ * The host's step counter (what mmi_lm_step's `valid` is derived from, lm.py:774-776) advances by T, as T masked steps would
+ * advance it - also when only some sessions were named: the next mmi_lm_step may then report valid = 1 for a stream whose other
+ * sessions are younger than max_delay (their rows hold -2, as under support_out_of_sync).
+ *
+ * mmi_lm_last_tokens: a copy of the tokens the last step (or prefill) stored, device i64 [streaming batch][1 + dep_q] in step
+ * coordinates (text, then the audio codebooks) - the log a caller keeps to hand a session back to mmi_lm_prefill; mmi_lm_step's
+ * own return value lags by up to max_delay frames.  Stream ordered. */
+int mmi_lm_enable_prefill(mmi_lm* lm, int32_t rows);
+int32_t mmi_lm_prefill_rows(const mmi_lm* lm);          /* 0 = off; a negative status for a NULL handle */
+int mmi_lm_prefill(mmi_lm* lm, const int32_t* sessions, int32_t n, const int64_t* user_codes, const int64_t* tokens, int32_t T,
+                   mmi_stream stream);
+int mmi_lm_last_tokens(mmi_lm* lm, int64_t* out, mmi_stream stream);
+
+/* Parity tap of the prefill attention (tests): k_lm_attn_prefill alone, launched through the function the prefill pass uses, on
+ * caller-supplied operands.  Works on any handle and touches no stream state.
+ *   q          device bf16 [rows][H][Dh], taken as already roped
+ *   row_ring   device int32 [rows], row_pos device int64 [rows]: the row table of a pass - n_blocks equal blocks of rows / n_blocks
+ *              rows; the rows of a block name ONE ring in [0, rings) and consecutive positions from a start >= 0
+ *   k_ring, v_ring     the layout of mmi_lm_debug_kv_ring for `rings` rings of `cap` slots: positions below a block's start, as a
+ *              stream that stands at that start holds them
+ *   k_staged, v_staged the block itself in ring format: [rows][H][row bytes], then (4-bit) the scale bytes [rows][H][Dh / 16]
+ *   out        device bf16 [rows][H * Dh]
+ * Row r attends position pos iff 0 <= row_pos[r] - pos < context.  rows <= 128.  Synchronises `stream`. */
+int mmi_lm_debug_prefill_attn(mmi_lm* lm, const void* q_bf16, const int32_t* row_ring, const int64_t* row_pos, const void* k_ring,
+                              const void* v_ring, const void* k_staged, const void* v_staged, int32_t rows, int32_t n_blocks,
+                              int32_t rings, int32_t H, int32_t Dh, int32_t cap, int32_t context, int32_t kv_dtype, void* out_bf16,
+                              mmi_stream stream);
+
+/* The regions of the streaming-state arena - the buffer of mmi_lm_state_save - by name (tests compare two streams region by
+ * region): one line "name<TAB>offset<TAB>bytes<TAB>rows<TAB>kind" each.  rows > 0: the region is `rows` equal slices, one per
+ * session (model row); kind 1 = state the next step reads ("exec", "offsets", "cache", "text_tok", "audio_tok", "rng", "rowtab",
+ * "thist", "coefs", "cond", and the temporal rings layer by layer: "kc.<l>", "vc.<l>", a 4-bit ring's "kc.<l>.scale"), kind 0 =
+ * scratch that every step rewrites before reading it.  Returns the bytes needed including the final NUL (buf = NULL to size); 0
+ * when not streaming. */
+int64_t mmi_lm_debug_state_regions(const mmi_lm* lm, char* buf, int64_t cap);
 
 /* The launch list of one frame step, recorded while the step ran for the first time: one line "site<TAB>kernel[<TAB>weight bytes]" per kernel
  * launch in launch order (sites: "L.in_proj", "L.ffn_in", "dep.out_proj", "text_linear", ...).  scripts/rocpd_sites.py joins

@@ -221,6 +221,13 @@ SIGNATURES = {
     "mmi_lm_set_row_top_p": (C.c_int, [_P, C.c_int32, C.c_float, C.c_float, _P]),
     "mmi_lm_clear_row_top_p": (C.c_int, [_P, C.c_int32, _P]),
     "mmi_batcher_set_channel_top_p": (C.c_int, [_P, C.c_int64, C.c_float, C.c_float]),
+    "mmi_lm_enable_prefill": (C.c_int, [_P, C.c_int32]),
+    "mmi_lm_prefill_rows": (C.c_int32, [_P]),
+    "mmi_lm_prefill": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int32, _P, _P, C.c_int32, _P]),
+    "mmi_lm_last_tokens": (C.c_int, [_P, _P, _P]),
+    "mmi_lm_debug_prefill_attn": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_int32, _P, _P]),
+    "mmi_lm_debug_state_regions": (C.c_int64, [_P, _P, C.c_int64]),
     "mmi_lm_launch_list": (C.c_int64, [_P, _P, C.c_int64]),
     "mmi_mimi_launch_list": (C.c_int64, [_P, C.c_int32, _P, C.c_int64]),
     "mmi_lm_seek": (C.c_int, [_P, _P, _P]),
@@ -242,10 +249,13 @@ _SINCE_NUCLEUS = ("mmi_lm_enable_nucleus", "mmi_lm_set_top_p", "mmi_lm_top_p", "
                   "mmi_lm_clear_row_top_p", "mmi_batcher_set_channel_top_p")
 _SINCE_KV4 = ("mmi_lm_debug_kv4_quantize", "mmi_lm_debug_kv_ring")
 _SINCE_ATTN_TAP = ("mmi_lm_debug_attn",)
+_SINCE_PREFILL = ("mmi_lm_enable_prefill", "mmi_lm_prefill_rows", "mmi_lm_prefill", "mmi_lm_last_tokens", "mmi_lm_debug_prefill_attn",
+                  "mmi_lm_debug_state_regions")
 
 
 def _missing(name, path):
-    what = ("the attention tap" if name in _SINCE_ATTN_TAP else
+    what = ("chunked prefill" if name in _SINCE_PREFILL else
+            "the attention tap" if name in _SINCE_ATTN_TAP else
             "the 4-bit KV ring" if name in _SINCE_KV4 else
             "nucleus sampling" if name in _SINCE_NUCLEUS else
             "per-session adapters" if name in _SINCE_ADAPTERS else
@@ -265,7 +275,7 @@ class Lib:
         self.path = Path(path)
         self.cdll = C.CDLL(str(self.path))
         for name, (res, args) in SIGNATURES.items():
-            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION + _SINCE_TTS_MACHINE + _SINCE_MANY_ROWS + _SINCE_ADAPTERS + _SINCE_NUCLEUS + _SINCE_KV4 + _SINCE_ATTN_TAP and not hasattr(self.cdll, name):
+            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION + _SINCE_TTS_MACHINE + _SINCE_MANY_ROWS + _SINCE_ADAPTERS + _SINCE_NUCLEUS + _SINCE_KV4 + _SINCE_ATTN_TAP + _SINCE_PREFILL and not hasattr(self.cdll, name):
                 # an older build of the engine (MMI_LIB_PATH, A/B runs against a parent build): everything else works, these refuse
                 setattr(self, name, _missing(name, self.path))
                 continue

@@ -3,6 +3,7 @@
 // depformer_step (8 sequential depth-transformer micro-steps, lm.py:809-850, 450-493) as one fixed launch list over
 // the kernels of lm_kernels.h, captured into a single hipGraph.
 #include "lm_kernels.h"
+#include "lm_prefill_kernels.h"
 #include "mmi_graph.h"
 
 #include <math.h>
@@ -184,12 +185,27 @@ struct mmi_lm {
     int* row_slot = nullptr;        // [gen_batch] adapter slot per session, -1 = none (streaming-state arena: snapshots carry it)
     std::vector<int> row_slot_h;    // the host's mirror (a slot is not reloaded while a live row selects it)
     uint16_t* lora_t = nullptr;     // packed t = bf16(A x) of the linear in flight (adapters need Td == T: one tile, one buffer)
+    // chunked prefill (mmi_lm_enable_prefill): the row budget of a pass belongs to the handle, the scratch of a pass
+    // to the stream - an arena of its own, so that the streaming-state arena (mmi_lm_state_bytes, snapshots) is what it was
+    int prefill_rows = 0;
+    MmiArena pf_mem;
+    struct {
+        int* tokens = nullptr;          // [rows][NC] model input
+        int* row_sess = nullptr;        // [rows]
+        long* row_pos = nullptr;        // [rows]
+        float* rope = nullptr;          // [rows][Dh/2][2]
+        uint16_t *x = nullptr, *xn = nullptr, *att = nullptr, *hb = nullptr;      // packed activations of `rows` rows
+        uint16_t *qkv = nullptr, *q = nullptr;                                    // row-major in_proj output, roped queries
+        uint8_t *sk = nullptr, *sv = nullptr, *sks = nullptr, *svs = nullptr;     // the staged block in ring format
+        float* partial = nullptr;       // [4][rows][dim] split-K partial sums
+    } pf;
     long offset_cpu = 0;
     int attn_ns = 1;                                // workgroups per (session, head) of the decode attention (attn_splits)
     long depth_bound = 0;                           // no session's offset exceeds this (steps since streaming_start / the last seek; resets
                                                     // only lower offsets): picks the step program's variant (attn_variant)
     long xlds_launches = 0;         // launches (or graph nodes captured) that took k_gemm_xlds: mmi_lm_stat(lm, 0)
     long rows_launches = 0;         // launches (or graph nodes captured) that took k_gemm_rows: mmi_lm_stat(lm, 4)
+                                    // (both count every launch_gemm: the GEMMs of a prefill pass as well as a step's)
     bool precapture_failed = false; // capturing the second attention program ahead of time failed once: not tried again for this stream
     bool dominant_xlds = false;     // the profiled (dominant) GEMM ran on k_gemm_xlds
     MmiProgram prog;
@@ -1876,6 +1892,340 @@ extern "C" int mmi_lm_get_cfg(const mmi_lm* lm, mmi_lm_cfg* out) {
     return MMI_OK;
 }
 
+// ---- chunked prefill -------------------------------------------------------------------------------------------
+// bytes of one ring row / of its scale bytes in ring form kvf
+static size_t pf_row_bytes(int kvf, int Dh) { return kvf == 2 ? Dh / 2 : (kvf == 1 ? Dh : 2 * Dh); }
+
+// what a handle must be to prefill at all (mmi_lm_enable_prefill), and what may have changed since (mmi_lm_prefill)
+static int prefill_refusal(const mmi_lm* lm, int rows) {
+    const mmi_lm_cfg& c = lm->cfg;
+    const int Dh = c.num_heads > 0 ? c.dim / c.num_heads : 0;
+    if (rows > 128) return mmi_fail(MMI_ERR_UNSUPPORTED, "prefill: a pass holds at most 128 rows");
+    if (rows > 32 && lm->T == 16)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "prefill: a handle whose weights are packed at the 16-row tile (max_batch <= 16) runs passes of at most 32 rows");
+    if (lm->q8 > 0) return mmi_fail(MMI_ERR_UNSUPPORTED, "prefill: quantised linears (int8, fp8, MXFP4) are not supported: the many-row GEMM is bf16");
+    if (c.cross_attention) return mmi_fail(MMI_ERR_UNSUPPORTED, "prefill: models with cross-attention layers are not supported");
+    if (lm->lora_on) return mmi_fail(MMI_ERR_UNSUPPORTED, "prefill: adapter handles are not supported");
+    if (lm->tts_on) return mmi_fail(MMI_ERR_UNSUPPORTED, "prefill: a handle with the TTS machine enabled is not supported (its script state advances per step)");
+    if (Dh != 32 && Dh != 64 && Dh != 128) return mmi_fail(MMI_ERR_UNSUPPORTED, "prefill: head dim must be 32, 64 or 128");
+    return MMI_OK;
+}
+
+static int prefill_alloc(mmi_lm* lm, hipStream_t s) {
+    const mmi_lm_cfg& c = lm->cfg;
+    const int rows = lm->prefill_rows, d = c.dim, H = c.num_heads, Dh = d / H, kvf = kv_form(c.kv_cache_dtype);
+    int rc = prefill_refusal(lm, rows);           // (adapters or the TTS machine may have been enabled after the prefill was)
+    if (rc) return rc;
+    const size_t mtiles = (size_t)mmi_cdiv(rows, lm->T);
+    auto packed = [&](int features) { return mtiles * packed_ksteps(lm, features) * 512; };
+    MmiArena& A = lm->pf_mem;
+    A.poison = lm->st.poison;
+    auto& P = lm->pf;
+    bool ok = true;
+    ok &= hipSuccess == A.alloc(&P.tokens, (size_t)rows * lm->NC);
+    ok &= hipSuccess == A.alloc(&P.row_sess, (size_t)rows);
+    ok &= hipSuccess == A.alloc(&P.row_pos, (size_t)rows);
+    ok &= hipSuccess == A.alloc(&P.rope, (size_t)rows * Dh);
+    ok &= hipSuccess == A.alloc(&P.x, packed(d));
+    ok &= hipSuccess == A.alloc(&P.xn, packed(d));
+    ok &= hipSuccess == A.alloc(&P.att, packed(d));
+    ok &= hipSuccess == A.alloc(&P.hb, packed(c.ffn_hidden));
+    ok &= hipSuccess == A.alloc(&P.qkv, (size_t)rows * 3 * d);
+    ok &= hipSuccess == A.alloc(&P.q, (size_t)rows * d);
+    ok &= hipSuccess == A.alloc(&P.sk, (size_t)rows * H * pf_row_bytes(kvf, Dh));
+    ok &= hipSuccess == A.alloc(&P.sv, (size_t)rows * H * pf_row_bytes(kvf, Dh));
+    ok &= hipSuccess == A.alloc(&P.sks, (size_t)rows * H * (Dh / 16));
+    ok &= hipSuccess == A.alloc(&P.svs, (size_t)rows * H * (Dh / 16));
+    ok &= hipSuccess == A.alloc(&P.partial, (size_t)4 * rows * d);
+    if (!ok) return mmi_fail(MMI_ERR_HIP, "out of device memory (prefill scratch)");
+    // packed activations: the padding rows / columns of a fragment are never written and must read as zero
+    struct { uint16_t* p; int f; } pk[] = {{P.x, d}, {P.xn, d}, {P.att, d}, {P.hb, c.ffn_hidden}};
+    for (auto& e : pk) MMI_HIP_CHECK(hipMemsetAsync(e.p, 0, packed(e.f) * sizeof(uint16_t), s));
+    return MMI_OK;
+}
+
+template <int KVF>
+static int launch_attn_prefill_f(hipStream_t s, const PfAttnArgs& a, int Dh) {
+    const dim3 grid(a.n * mmi_cdiv(a.F, MMI_PF_QT), a.H);
+    switch (Dh) {
+        case 128: MMI_LAUNCH((k_lm_attn_prefill<128, KVF>), grid, 256, 0, s, a); break;
+        case 64: MMI_LAUNCH((k_lm_attn_prefill<64, KVF>), grid, 256, 0, s, a); break;
+        case 32: MMI_LAUNCH((k_lm_attn_prefill<32, KVF>), grid, 256, 0, s, a); break;
+        default: return mmi_fail(MMI_ERR_UNSUPPORTED, "head dim must be 32, 64 or 128");
+    }
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+// the attention op of a prefill pass (and mmi_lm_debug_prefill_attn)
+static int launch_attn_prefill(hipStream_t s, const PfAttnArgs& a, int kvf, int Dh) {
+    if (kvf == 2) return launch_attn_prefill_f<2>(s, a, Dh);
+    if (kvf == 1) return launch_attn_prefill_f<1>(s, a, Dh);
+    return launch_attn_prefill_f<0>(s, a, Dh);
+}
+
+// One linear of a pass on `rows` rows: launch_gemm's own selection at that row count (k_gemm_rows above 64, k_gemm_xp / k_gemm_xlds
+// at or below)
+static int pf_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, int rows, const uint16_t* x, uint16_t* out, int out_features, bool out_packed,
+                   int epi, const uint16_t* resid) {
+    GemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.xp = reinterpret_cast<const u32x4*>(x); a.out = out; a.epi = epi; a.resid = resid; a.B = rows; a.tok_rows = rows;
+    a.out_mode = out_packed ? MMI_OUT_PACKED : MMI_OUT_ROWMAJOR;
+    a.out_ld = out_features;
+    a.out_ksteps = packed_ksteps_t(lm, g.T, out_features);
+    if (epi == MMI_EPI_PARTIAL) a.partial = lm->pf.partial;
+    return launch_gemm(lm, s, g, a, false);
+}
+// x += linear(in), in place or as split-K partials for the next norm launch to fold (add_gemm_resid's rule); returns the partials
+static int pf_gemm_resid(mmi_lm* lm, hipStream_t s, const GemmW& g, int rows, const uint16_t* in, int* pending) {
+    const GemmPlan p = plan_gemm(lm->knobs, g, true);
+    if (p.ksplit > 4) return mmi_fail(MMI_ERR_UNSUPPORTED, "prefill: the split-K partials hold at most 4 parts (MMI_GEMM_KSPLIT)");     // pf.partial is [4][rows][dim]
+    *pending = p.ksplit > 1 ? p.ksplit : 0;
+    if (p.ksplit <= 1) return pf_gemm(lm, s, g, rows, in, lm->pf.x, lm->cfg.dim, true, MMI_EPI_RESID, lm->pf.x);
+    return pf_gemm(lm, s, g, rows, in, nullptr, lm->cfg.dim, true, MMI_EPI_PARTIAL, nullptr);
+}
+static int pf_norm(mmi_lm* lm, hipStream_t s, int rows, int pending, const uint16_t* alpha) {
+    const int D = lm->cfg.dim;
+    int nth = mmi_cdiv(D / 8, 64) * 64;
+    if (nth > 1024) nth = 1024;
+    MMI_LAUNCH(k_resid_rmsnorm, rows, nth, 0, s, lm->pf.x, (const float*)lm->pf.partial, pending, rows, alpha, lm->pf.xn, D, lm->T, packed_ksteps(lm, D), 1e-8f,
+               (uint8_t*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+
+// One pass: F frames (f0 .. f0 + F - 1 of the call's arrays) of the n sessions of `p`, eager launches on `s`
+static int prefill_pass(mmi_lm* lm, hipStream_t s, PfArgs p, const int64_t* user, const int64_t* toks) {
+    const mmi_lm_cfg& c = lm->cfg;
+    const int d = c.dim, H = c.num_heads, Dh = d / H, R = p.n * p.F, n_user = c.n_q - c.dep_q, kvf = kv_form(c.kv_cache_dtype);
+    auto& P = lm->pf;
+    TokArgs t = tok_args(lm);
+    MMI_LAUNCH(k_pf_prepare, mmi_cdiv(R * lm->NC + R * (Dh / 2), 128), 128, 0, s, t, p, (const long*)user, n_user, (const long*)toks, P.tokens,
+               P.row_sess, P.row_pos, P.rope, Dh, c.max_period);
+    MMI_LAUNCH(k_pf_embed, dim3(mmi_cdiv(d, 256), R), 256, 0, s, (const int*)P.tokens, lm->NC, (const uint16_t*)lm->emb, c.card + 1,
+               (const uint16_t*)lm->text_emb, (const uint16_t*)(lm->demux ? lm->text_emb2 : nullptr), c.text_card + 1, P.x, d, lm->T,
+               packed_ksteps(lm, d), (const uint16_t*)lm->cond, (const int*)P.row_sess);
+    MMI_CHECK_LAUNCH();
+    const size_t kv_layer = kv_layer_u16(kvf, (size_t)lm->batch * H * c.context * Dh);
+    int pending = 0, rc;
+    for (int l = 0; l < c.num_layers; ++l) {
+        const LayerW& L = lm->layers[l];
+        if ((rc = pf_norm(lm, s, R, pending, L.n1))) return rc;
+        if ((rc = pf_gemm(lm, s, L.in_proj, R, P.xn, P.qkv, 3 * d, false, MMI_EPI_STORE, nullptr))) return rc;
+        PfRopeArgs ra;
+        ra.qkv = P.qkv; ra.rope = P.rope; ra.q = P.q; ra.sk = P.sk; ra.sv = P.sv; ra.sks = P.sks; ra.svs = P.svs; ra.R = R; ra.H = H; ra.Dh = Dh;
+        const int rblocks = (int)mmi_cdiv64((int64_t)R * 3 * d / 16, 256);
+        if (kvf == 2) MMI_LAUNCH(k_pf_rope_kv<2>, rblocks, 256, 0, s, ra);
+        else if (kvf == 1) MMI_LAUNCH(k_pf_rope_kv<1>, rblocks, 256, 0, s, ra);
+        else MMI_LAUNCH(k_pf_rope_kv<0>, rblocks, 256, 0, s, ra);
+        MMI_CHECK_LAUNCH();
+        PfAttnArgs a;
+        memset(&a, 0, sizeof(a));
+        a.q = P.q; a.kc = reinterpret_cast<uint8_t*>(lm->kc + l * kv_layer); a.vc = reinterpret_cast<uint8_t*>(lm->vc + l * kv_layer);
+        a.kv_soff = kvf == 2 ? (long)lm->batch * H * c.context * Dh / 2 : 0;
+        a.sk = P.sk; a.sv = P.sv; a.sks = P.sks; a.svs = P.svs; a.row_sess = P.row_sess; a.row_pos = P.row_pos;
+        a.out = P.att; a.T = lm->T; a.out_ksteps = packed_ksteps(lm, d);
+        a.H = H; a.cap = c.context; a.context = c.context; a.n = p.n; a.F = p.F;
+        const bool last = l + 1 == c.num_layers;        // the last layer's attention output, FFN and out_norm feed nothing
+        if (!last && (rc = launch_attn_prefill(s, a, kvf, Dh))) return rc;
+        const int cblocks = (int)mmi_cdiv64((int64_t)R * H * (pf_row_bytes(kvf, Dh) / 16), 256);
+        if (kvf == 2) MMI_LAUNCH(k_pf_commit_kv<2>, cblocks, 256, 0, s, a, Dh);
+        else if (kvf == 1) MMI_LAUNCH(k_pf_commit_kv<1>, cblocks, 256, 0, s, a, Dh);
+        else MMI_LAUNCH(k_pf_commit_kv<0>, cblocks, 256, 0, s, a, Dh);
+        MMI_CHECK_LAUNCH();
+        if (last) break;
+        if ((rc = pf_gemm_resid(lm, s, L.out_proj, R, P.att, &pending))) return rc;
+        if ((rc = pf_norm(lm, s, R, pending, L.n2))) return rc;
+        if ((rc = pf_gemm(lm, s, L.ffn_in, R, P.xn, P.hb, c.ffn_hidden, true, MMI_EPI_GATE, nullptr))) return rc;
+        if ((rc = pf_gemm_resid(lm, s, L.ffn_out, R, P.hb, &pending))) return rc;
+    }
+    MMI_LAUNCH(k_pf_commit_state, mmi_cdiv(p.n, 64), 64, 0, s, t, p, (const long*)user, n_user, (const long*)toks, lm->text_tok, lm->audio_tok);
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+
+extern "C" int mmi_lm_enable_prefill(mmi_lm* lm, int32_t rows) {
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (lm->streaming) return mmi_fail(MMI_ERR_STATE, "mmi_lm_enable_prefill: not while streaming");
+    if (rows < 0) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_enable_prefill: rows must be 0 (off) or 1..128");
+    if (rows > 0) {
+        const int rc = prefill_refusal(lm, rows);
+        if (rc) return rc;
+    }
+    lm->prefill_rows = rows;
+    return MMI_OK;
+}
+
+extern "C" int32_t mmi_lm_prefill_rows(const mmi_lm* lm) {
+    if (!lm) return (int32_t)mmi_fail(MMI_ERR_INVALID, "null handle");
+    return lm->prefill_rows;
+}
+
+extern "C" int mmi_lm_prefill(mmi_lm* lm, const int32_t* sessions, int32_t n, const int64_t* user_codes, const int64_t* tokens, int32_t T,
+                              mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm || !sessions || !tokens) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (!lm->streaming) return mmi_fail(MMI_ERR_STATE, "not streaming");
+    if (lm->prefill_rows <= 0 || !lm->pf.x)
+        return mmi_fail(MMI_ERR_STATE, "prefill is not enabled: call mmi_lm_enable_prefill before streaming_start");
+    const mmi_lm_cfg& c = lm->cfg;
+    if (!user_codes && c.n_q > c.dep_q) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (T < 1) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_prefill: T must be >= 1");
+    if (n < 1 || n > lm->prefill_rows) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_prefill: 1 .. prefill_rows sessions per call");
+    PfArgs p;
+    memset(&p, 0, sizeof(p));
+    std::vector<uint8_t> seen(lm->gen_batch, 0);
+    for (int i = 0; i < n; ++i) {
+        if (sessions[i] < 0 || sessions[i] >= lm->gen_batch) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_prefill: session index out of range");
+        if (seen[sessions[i]]) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_prefill: a session is named twice");
+        seen[sessions[i]] = 1;
+        p.sess[i] = (uint8_t)sessions[i];
+    }
+    // what a stream or a step may have brought since the prefill was enabled
+    if (lm->cfg_coef != 1.f || lm->batch != lm->gen_batch) return mmi_fail(MMI_ERR_UNSUPPORTED, "prefill: a guided stream (guidance twins) is not supported");
+    if (lm->hooks.on_text_logits || lm->hooks.on_text_token || lm->hooks.on_audio_tokens)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "prefill: not while per-step hooks are installed");
+    if (lm->tts || lm->lora_on) return mmi_fail(MMI_ERR_UNSUPPORTED, "prefill: not on a stream with the TTS machine or adapters");
+    hipStream_t s = (hipStream_t)stream;
+    p.n = n; p.T = T;
+    const int F = lm->prefill_rows / n;
+    for (int f0 = 0; f0 < T; f0 += F) {
+        p.f0 = f0;
+        p.F = T - f0 < F ? T - f0 : F;
+        const int rc = prefill_pass(lm, s, p, user_codes, tokens);
+        if (rc) return rc;
+    }
+    lm->offset_cpu += T;
+    if (lm->depth_bound < (1L << 40)) lm->depth_bound += T;
+    return MMI_OK;
+}
+
+extern "C" int mmi_lm_last_tokens(mmi_lm* lm, int64_t* out, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm || !out) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (!lm->streaming) return mmi_fail(MMI_ERR_STATE, "not streaming");
+    const int G = lm->gen_batch, q = lm->cfg.dep_q;
+    MMI_LAUNCH(k_pf_last_tokens, mmi_cdiv(G * (1 + q), 256), 256, 0, (hipStream_t)stream, (const int*)lm->text_tok, (const int*)lm->audio_tok, G, q, (long*)out);
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+
+// The regions of the streaming-state arena (mmi_lm_state_save's buffer) by name: "name<TAB>offset<TAB>bytes<TAB>rows<TAB>kind" per
+// line.  rows > 0: the region is `rows` equal slices, one per session (model row); kind 1 = state that the next step reads (what a
+// session IS), 0 = scratch that every step rewrites before reading it.
+extern "C" int64_t mmi_lm_debug_state_regions(const mmi_lm* lm, char* buf, int64_t cap) {
+    if (!lm || !lm->streaming) return 0;
+    const mmi_lm_cfg& c = lm->cfg;
+    const int G = lm->gen_batch, B = lm->batch, H = c.num_heads, Dh = c.dim / H, kvf = kv_form(c.kv_cache_dtype);
+    std::vector<size_t> at(lm->st.ptrs.size());
+    size_t sum = 0;
+    for (size_t i = 0; i < at.size(); ++i) { at[i] = sum; sum += lm->st.sizes[i]; }
+    struct Reg { std::string name; size_t off, bytes; int rows, kind; };
+    std::vector<Reg> regs;
+    std::vector<uint8_t> named(at.size(), 0);
+    auto base = [&](const void* p, size_t* off) {
+        for (size_t i = 0; i < at.size(); ++i)
+            if (lm->st.ptrs[i] == p) { named[i] = 1; *off = at[i]; return true; }
+        return false;
+    };
+    auto add = [&](const char* name, const void* p, size_t bytes, int rows) {
+        size_t off;
+        if (p && base(p, &off)) regs.push_back({name, off, bytes, rows, 1});
+    };
+    add("exec", lm->exec, (size_t)G, G);
+    add("offsets", lm->offsets, (size_t)G * sizeof(long), G);
+    add("cache", lm->cache, (size_t)G * lm->NC * lm->CT * sizeof(int), G);
+    add("text_tok", lm->text_tok, (size_t)G * sizeof(int), G);
+    add("audio_tok", lm->audio_tok, (size_t)G * c.dep_q * sizeof(int), c.dep_q ? G : 0);
+    add("rng", lm->rng, 2 * sizeof(unsigned long long), 0);
+    add("rowtab", lm->rowtab, (size_t)G * sizeof(RowSamp), G);
+    add("thist", lm->thist, (size_t)G * MMI_TEXT_HIST * sizeof(int), G);
+    add("coefs", lm->coefs, (size_t)G * sizeof(float), G);
+    add("cond", lm->cond, (size_t)B * c.dim * sizeof(uint16_t), B);
+    {   // the temporal rings, layer by layer (a 4-bit layer: codes plane, then scale plane)
+        const size_t elems = (size_t)B * H * c.context * Dh, layer = kv_layer_u16(kvf, elems) * sizeof(uint16_t);
+        for (int w = 0; w < 2; ++w) {
+            size_t off;
+            if (!base(w ? lm->vc : lm->kc, &off)) continue;
+            for (int l = 0; l < c.num_layers; ++l) {
+                const std::string nm = std::string(w ? "vc." : "kc.") + std::to_string(l);
+                if (kvf == 2) {
+                    regs.push_back({nm, off + l * layer, elems / 2, B, 1});
+                    regs.push_back({nm + ".scale", off + l * layer + elems / 2, elems / 16, B, 1});
+                } else regs.push_back({nm, off + l * layer, elems * (kvf ? 1 : 2), B, 1});
+            }
+        }
+    }
+    for (size_t i = 0; i < at.size(); ++i)
+        if (!named[i]) regs.push_back({"scratch" + std::to_string(i), at[i], lm->st.sizes[i], 0, 0});
+    std::string text;
+    for (const Reg& r : regs)
+        text += r.name + "\t" + std::to_string(r.off) + "\t" + std::to_string(r.bytes) + "\t" + std::to_string(r.rows) + "\t" + std::to_string(r.kind) + "\n";
+    const int64_t need = (int64_t)text.size() + 1;
+    if (buf && cap >= need) memcpy(buf, text.c_str(), (size_t)need);
+    return need;
+}
+
+// Parity tap of the prefill attention (include/moshi_mi.h): launch_attn_prefill - the attention op of a pass - on caller-supplied
+// operands, with a packed output of its own.  Nothing of the handle but its device and its poison knob is read.
+extern "C" int mmi_lm_debug_prefill_attn(mmi_lm* lm, const void* q_bf16, const int32_t* row_ring, const int64_t* row_pos, const void* k_ring,
+                                         const void* v_ring, const void* k_staged, const void* v_staged, int32_t rows, int32_t n_blocks,
+                                         int32_t rings, int32_t H, int32_t Dh, int32_t cap, int32_t context, int32_t kv_dtype, void* out_bf16,
+                                         mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm || !q_bf16 || !row_ring || !row_pos || !k_ring || !v_ring || !k_staged || !v_staged || !out_bf16)
+        return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (kv_dtype != MMI_BF16 && kv_dtype != MMI_F8E4M3 && kv_dtype != MMI_F4E2M1X2)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_prefill_attn: the ring is bf16, e4m3 or 4-bit (MMI_F4E2M1X2)");
+    const int kvf = kv_form(kv_dtype);
+    if (Dh != 32 && Dh != 64 && Dh != 128) return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_prefill_attn: head dim must be 32, 64 or 128");
+    if (rows <= 0 || rows > 128 || n_blocks <= 0 || rows % n_blocks)
+        return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_prefill_attn: 1..128 rows in n_blocks equal blocks");
+    if (H <= 0 || H > 1024 || rings <= 0 || cap <= 0 || cap > (1 << 20) || context <= 0 || context > cap)
+        return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_prefill_attn: 1 <= H <= 1024, rings >= 1, 1 <= context <= cap <= 2^20");
+    if (((uintptr_t)q_bf16 | (uintptr_t)k_ring | (uintptr_t)v_ring | (uintptr_t)k_staged | (uintptr_t)v_staged) % 16 || (uintptr_t)row_pos % 8 ||
+        (uintptr_t)row_ring % 4 || (uintptr_t)out_bf16 % 2)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_prefill_attn: q, the rings and the staged blocks must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int F = rows / n_blocks;
+    {   // the row table must be what a pass builds: one ring per block, consecutive positions from a start >= 0
+        std::vector<int32_t> rr(rows);
+        std::vector<int64_t> rp(rows);
+        MMI_HIP_CHECK(hipStreamSynchronize(s));
+        MMI_HIP_CHECK(hipMemcpy(rr.data(), row_ring, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+        MMI_HIP_CHECK(hipMemcpy(rp.data(), row_pos, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToHost));
+        for (int r = 0; r < rows; ++r) {
+            const int r0 = r / F * F;
+            if (rr[r] < 0 || rr[r] >= rings || rr[r] != rr[r0] || rp[r0] < 0 || rp[r] != rp[r0] + (r - r0))
+                return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_prefill_attn: a block's rows name one ring in [0, rings) and consecutive positions >= 0");
+        }
+    }
+    const int d = H * Dh, T = rows <= 16 ? 16 : 32, mt = mmi_cdiv(rows, T), ksteps = mmi_cdiv(d, mmi_kstep(T));
+    const size_t oelems = (size_t)mt * ksteps * 512;
+    MmiArena A;
+    A.poison = lm->knobs.debug_poison;
+    uint16_t* att = nullptr;
+    auto done = [&](int rc) { hipStreamSynchronize(s); A.release(); return rc; };
+    if (hipSuccess != A.alloc(&att, oelems)) return done(mmi_fail(MMI_ERR_HIP, "out of device memory (mmi_lm_debug_prefill_attn)"));
+    if (hipMemsetAsync(att, 0, oelems * 2, s) != hipSuccess) return done(mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_prefill_attn: hipMemsetAsync failed"));
+    PfAttnArgs a;
+    memset(&a, 0, sizeof(a));
+    const size_t rowb = pf_row_bytes(kvf, Dh);
+    a.q = (const uint16_t*)q_bf16; a.kc = (uint8_t*)k_ring; a.vc = (uint8_t*)v_ring;
+    a.kv_soff = kvf == 2 ? (long)rings * H * cap * Dh / 2 : 0;
+    a.sk = (const uint8_t*)k_staged; a.sv = (const uint8_t*)v_staged;
+    a.sks = a.sk + (size_t)rows * H * rowb; a.svs = a.sv + (size_t)rows * H * rowb;
+    a.row_sess = row_ring; a.row_pos = reinterpret_cast<const long*>(row_pos);
+    a.out = att; a.T = T; a.out_ksteps = ksteps; a.H = H; a.cap = cap; a.context = context; a.n = n_blocks; a.F = F;
+    int rc = launch_attn_prefill(s, a, kvf, Dh);
+    if (rc) return done(rc);
+    MMI_LAUNCH(k_unpack_rows, mmi_cdiv(rows * d, 256), 256, 0, s, (const uint16_t*)att, rows, d, (uint16_t*)out_bf16, T, ksteps);
+    if (hipGetLastError() != hipSuccess) return done(mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_prefill_attn: kernel launch failed"));
+    if (hipStreamSynchronize(s) != hipSuccess) { A.release(); return mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_prefill_attn: the launches failed"); }
+    A.release();
+    return MMI_OK;
+}
+
 extern "C" int mmi_lm_streaming_start(mmi_lm* lm, int32_t batch, const mmi_sampling* sampling, mmi_stream stream) {
     MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
     return mmi_lm_streaming_start_guided(lm, batch, sampling, nullptr, stream);
@@ -2094,6 +2444,7 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
     }
     rc = build_program(lm);
     if (rc) return fail(rc);
+    if (lm->prefill_rows > 0 && (rc = prefill_alloc(lm, s))) return fail(rc);
     MMI_HIP_CHECK(hipStreamSynchronize(s));
     if (lm->knobs.debug_trace) {
         static int session = 0;
@@ -2119,6 +2470,7 @@ extern "C" int mmi_lm_streaming_stop(mmi_lm* lm) {
     if (lm->trace_dev) { hipFree(lm->trace_dev); lm->trace_dev = nullptr; }
     lm->prog.clear();
     lm->st.release();
+    lm->pf_mem.release();
     lm->tts = nullptr;
     lm->row_slot = nullptr;
     lm->lora_t = nullptr;

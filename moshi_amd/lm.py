@@ -126,13 +126,17 @@ class LMModel:
         adapters: (max_adapters, max_rank) - room for up to 8 LoRA adapters of rank <= 32 / 64 / 96 / 128 NEXT TO this base model,
             chosen per session (`load_adapter`, `LMGen.set_session_adapter`; modules/lora.py, unmerged).  bf16 linears, at most 64
             model rows, no cross-attention layers, no extra heads.  None: a plain handle.
+        prefill_rows: the row budget (1..128) of one pass of `LMGen.prefill` (mmi_lm_enable_prefill): known frames
+            enter a session `prefill_rows` rows at a time, one pass over the temporal weights each.  bf16 linears, no
+            cross-attention layers, no adapters, no TTS machine; above 32 the handle must be built for more than 16 rows.
+            None: off - the handle allocates and launches what it always did.
     """
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], config: Optional[LMConfig] = None,
                  device: torch.device | str = "cuda", max_batch: int = 32, lib: Optional[_capi.Lib] = None,
                  quantize: bool | str = False, fuser: Optional[ConditionFuser] = None, kv_cache: Optional[str] = None,
                  cross_capacity: Optional[int] = None, max_rows: Optional[int] = None,
-                 adapters: Optional[Tuple[int, int]] = None):
+                 adapters: Optional[Tuple[int, int]] = None, prefill_rows: Optional[int] = None):
         if max_rows is not None:
             if max_batch > 64:
                 raise ValueError("max_rows and max_batch > 64 are mutually exclusive: max_rows alone sizes the handle")
@@ -203,6 +207,10 @@ class LMModel:
             max_adapters, max_rank = adapters
             lib.check(lib.mmi_lm_enable_adapters(self._handle, int(max_adapters), int(max_rank)))
             self.adapters = (int(max_adapters), int(max_rank))
+        self.prefill_rows = None
+        if prefill_rows is not None:
+            lib.check(lib.mmi_lm_enable_prefill(self._handle, int(prefill_rows)))
+            self.prefill_rows = int(prefill_rows)
 
     def __del__(self):
         try:
@@ -295,6 +303,32 @@ class LMModel:
             self._handle, q.data_ptr(), k.data_ptr(), v.data_ptr(), offsets.data_ptr(), rows, H, Dh, int(cap),
             int(cap if context is None else context), self.ATTN_RING_FORMS[ring], {"wave": 0, "split": 1}[kernel], int(ns),
             {"launch": 0, "kernel": 1}[merge], int(solo_rows), out.data_ptr(), _capi.stream_ptr(self.device)))
+        return out
+
+    def debug_prefill_attn(self, q: torch.Tensor, row_ring: torch.Tensor, row_pos: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                           k_staged: torch.Tensor, v_staged: torch.Tensor, cap: int, context: Optional[int] = None, ring: str = "bf16",
+                           n_blocks: int = 1, rings: int = 1) -> torch.Tensor:
+        """Parity tap (tests; `mmi_lm_debug_prefill_attn`): the prefill attention alone, through the launch function of a prefill pass.
+        `q` bf16 [rows, H, Dh] (already roped); `row_ring` int32 [rows] / `row_pos` int64 [rows]: the row table of a pass, `n_blocks`
+        equal blocks, each naming one of `rings` rings and consecutive positions; `k`, `v` uint8: the rings in the layout of
+        `debug_kv_ring` for `cap` slots; `k_staged`, `v_staged` uint8: the block in ring format ([rows, H, row bytes], then a 4-bit
+        ring's scale bytes [rows, H, Dh / 16]).  Returns bf16 [rows, H * Dh]."""
+        q = q.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        rows, H, Dh = q.shape
+        k, v, ks, vs = (t.to(device=self.device).contiguous().view(torch.uint8).reshape(-1) for t in (k, v, k_staged, v_staged))
+        per_elem = {"bf16": 32, "fp8": 16, "fp4": 9}[ring]                 # sixteenths of a byte
+        want = int(rings) * H * int(cap) * Dh * per_elem // 16
+        assert k.numel() == want and v.numel() == want, f"{rings} {ring} rings of {H} x {cap} x {Dh} are {want} bytes, got {k.numel()} / {v.numel()}"
+        want = rows * H * Dh * per_elem // 16
+        assert ks.numel() == want and vs.numel() == want, f"a staged {ring} block of {rows} x {H} x {Dh} is {want} bytes, got {ks.numel()} / {vs.numel()}"
+        row_ring = row_ring.to(device=self.device, dtype=torch.int32).contiguous()
+        row_pos = row_pos.to(device=self.device, dtype=torch.int64).contiguous()
+        assert row_ring.shape == (rows,) and row_pos.shape == (rows,), "one ring and one position per row"
+        out = torch.empty(rows, H * Dh, dtype=torch.bfloat16, device=self.device)
+        self._lib.check(self._lib.mmi_lm_debug_prefill_attn(
+            self._handle, q.data_ptr(), row_ring.data_ptr(), row_pos.data_ptr(), k.data_ptr(), v.data_ptr(), ks.data_ptr(), vs.data_ptr(),
+            rows, int(n_blocks), int(rings), H, Dh, int(cap), int(cap if context is None else context), self.ATTN_RING_FORMS[ring],
+            out.data_ptr(), _capi.stream_ptr(self.device)))
         return out
 
     def debug_linear(self, weight_name: str, x: torch.Tensor, path: str = "plain", alpha_name: Optional[str] = None,
@@ -942,6 +976,17 @@ class LMGen:
             self._lib.check(got)
         return buf
 
+    def state_regions(self) -> dict:
+        """Test aid (`mmi_lm_debug_state_regions`): {name: (offset, bytes, rows, kind)} - where each part of the streaming state sits
+        in `get_streaming_state()["lm_gen"]`; rows > 0: that many equal per-session slices; kind 1 = state, 0 = per-step scratch."""
+        assert self.is_streaming
+        text = _capi.read_text(lambda buf, cap: self._lib.mmi_lm_debug_state_regions(self.lm_model._handle, buf, cap))
+        out = {}
+        for line in text.splitlines():
+            name, off, nbytes, rows, kind = line.split("\t")
+            out[name] = (int(off), int(nbytes), int(rows), int(kind))
+        return out
+
     def hidden_taps(self) -> torch.Tensor:
         """Parity tap (tests): the residual stream of the LAST step after the first and after the last temporal layer, bf16
         [2, model rows, dim].  `lm_model.enable_hidden_taps()` must have been called before `streaming()`."""
@@ -1003,6 +1048,47 @@ class LMGen:
         if not self.support_out_of_sync and not valid.value:
             return None, tl, al
         return out, tl, al
+
+    @torch.no_grad()
+    def prefill(self, input_tokens: torch.Tensor, forced_tokens: torch.Tensor, sessions: Optional[Sequence[int]] = None) -> None:
+        """Known frames into live sessions without stepping them (mmi_lm_prefill; needs `LMModel(prefill_rows=)`): `input_tokens`
+        [n, n_q - dep_q, T] int64 user codes and `forced_tokens` [n, 1 + dep_q, T] int64 (text, then the audio codebooks: what each
+        frame's step would have stored, e.g. a log of `last_tokens()`) for the `n` sessions `sessions` (default: all of them).  The
+        sessions end where T forced steps under an exec mask of exactly them would have left them - offsets, delay ring, text
+        history, layer-0 K/V bit for bit, deeper K/V up to attention summation order - but nothing is sampled or returned, the other
+        sessions are untouched and the stream's draw counter stays.  Stream ordered."""
+        if not self.is_streaming:
+            raise RuntimeError("You should wrap those calls with a `with lm_gen.streaming(): ...`.")
+        cfg = self.lm_model.config
+        needed = cfg.n_q - cfg.dep_q
+        sess = list(range(self._batch)) if sessions is None else [int(b) for b in sessions]
+        n = len(sess)
+        assert forced_tokens.dim() == 3 and input_tokens.dim() == 3, "Shape should be [n, K, T]."
+        T = int(forced_tokens.shape[2])
+        assert forced_tokens.shape[0] == n and input_tokens.shape[0] == n, f"one row of frames per session: got {forced_tokens.shape[0]} for {n}"
+        assert forced_tokens.shape[1] == 1 + cfg.dep_q, f"forced_tokens must be [n, {1 + cfg.dep_q}, T]"
+        assert input_tokens.shape[1] >= needed and input_tokens.shape[2] == T, f"We expect {needed} tokens from the user stream for each of the {T} frames."
+        codes = input_tokens[:, :needed].to(device=self.device, dtype=torch.int64).contiguous()
+        forced = forced_tokens.to(device=self.device, dtype=torch.int64).contiguous()
+        if self.check:
+            assert not (codes == self.lm_model.ungenerated_token_id).any(), codes
+            assert (codes <= self.lm_model.card).all(), codes
+            assert (forced >= 0).all(), f"forced_tokens must be >= 0: {forced}"
+        arr = (C.c_int32 * max(n, 1))(*sess)
+        self._lib.check(self._lib.mmi_lm_prefill(self.lm_model._handle, arr, n, codes.data_ptr() if needed else None, forced.data_ptr(), T,
+                                                 self._stream()))
+        self._cond_keep = []
+        if self.device.type == "cuda":       # the launches read `codes` / `forced`: keep them until they ran
+            codes.record_stream(torch.cuda.current_stream(self.device))
+            forced.record_stream(torch.cuda.current_stream(self.device))
+
+    def last_tokens(self) -> torch.Tensor:
+        """[B, 1 + dep_q] int64: the tokens the last step (or prefill) stored for every session, in step coordinates - one frame of
+        the log `prefill` takes back (`step`'s own return value lags by the delays)."""
+        assert self.is_streaming
+        out = torch.empty(self._batch, 1 + self.lm_model.dep_q, dtype=torch.int64, device=self.device)
+        self._lib.check(self._lib.mmi_lm_last_tokens(self.lm_model._handle, out.data_ptr(), self._stream()))
+        return out
 
     @torch.no_grad()
     def step(self, input_tokens: torch.Tensor, depformer_replace_tokens: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:

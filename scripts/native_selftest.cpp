@@ -18,6 +18,11 @@
 // sampling stream with top_p = top_p_text = 1e-6 must equal the greedy stream (the nucleus is the argmax alone), and the entry points'
 // refusals must hold.
 //
+// `native_selftest <dir> --prefill`: chunked prefill through the C ABI alone (mmi_lm_enable_prefill / mmi_lm_prefill): the
+// first recorded forced frames enter the sessions by prefill - on a handle of the fixture's batch in one pass and in passes of one
+// frame, and on a 128-row handle whose 66 sessions make every pass a k_gemm_rows launch - then the remaining frames are stepped
+// against the oracle's record; the entry points' refusals must hold.
+//
 // The same source builds against the CPU simulator (-DMMI_SELFTEST_SIM, tests/test_native_selftest.py), which is how the expected
 // values and this program are checked where there is no GPU.  The checker side (oracle) never runs here: only its recorded output.
 //
@@ -30,7 +35,8 @@
 //         -o build/native_selftest_san
 //   export MMI_NO_GRAPH=1 ASAN_OPTIONS=detect_leaks=0:detect_stack_use_after_return=0 UBSAN_OPTIONS=print_stacktrace=1
 //   build/native_selftest_san tests/golden/native_selftest && build/native_selftest_san tests/golden/native_selftest --rows 65,128 &&
-//   build/native_selftest_san tests/golden/native_selftest --adapters && build/native_selftest_san tests/golden/native_selftest --nucleus
+//   build/native_selftest_san tests/golden/native_selftest --adapters && build/native_selftest_san tests/golden/native_selftest --nucleus &&
+//   build/native_selftest_san tests/golden/native_selftest --prefill
 #include "moshi_mi.h"
 #ifdef MMI_SELFTEST_SIM
 #include "hipsim.h"
@@ -74,6 +80,8 @@ int main(int argc, char** argv) {
     for (int i = 1; i < argc; ++i) adapters |= !strcmp(argv[i], "--adapters");
     bool nucleus = false;
     for (int i = 1; i < argc; ++i) nucleus |= !strcmp(argv[i], "--nucleus");
+    bool prefill = false;
+    for (int i = 1; i < argc; ++i) prefill |= !strcmp(argv[i], "--prefill");
     FILE* mf = fopen((dir + "/manifest.txt").c_str(), "r");
     if (!mf) { printf("cannot open %s/manifest.txt\n", dir.c_str()); return 2; }
     mmi_mimi_cfg mc; mmi_lm_cfg lc;
@@ -145,7 +153,7 @@ int main(int argc, char** argv) {
     int failures = 0;
 
     // ---- Mimi: encode FR frames, decode the oracle's codes
-    if (many_rows.empty() && !adapters && !nucleus) {
+    if (many_rows.empty() && !adapters && !nucleus && !prefill) {
         mmi_mimi* m = nullptr;
         MCK(mmi_mimi_create(&mc, md.data(), (int32_t)md.size(), B, &m));
         MCK(mmi_mimi_set_num_codebooks(m, K));
@@ -184,7 +192,7 @@ int main(int argc, char** argv) {
         mmi_mimi_destroy(m);
     }
     // ---- LM: greedy steps, teacher-forced with the oracle's tokens
-    if (many_rows.empty() && !adapters && !nucleus) {
+    if (many_rows.empty() && !adapters && !nucleus && !prefill) {
         mmi_lm* lm = nullptr;
         MCK(mmi_lm_create(&lc, ld.data(), (int32_t)ld.size(), B, &lm));
         mmi_sampling sp; memset(&sp, 0, sizeof(sp));
@@ -466,6 +474,115 @@ int main(int argc, char** argv) {
         failures += differ != 0 || control == 0 || produced == 0 || held != checks;
         mmi_lm_destroy(lm);
         hipFree(duc); hipFree(dout); hipFree(dnoise);
+    }
+    if (prefill) {
+        // R sessions (session r replays the fixture's session r % B) take the first `cut` recorded frames by prefill under a row budget
+        // `rows`, then the frames cut .. ST - 1 by forced steps: ring outputs (they still come out of the delay ring the prefill left)
+        // and logits against the oracle's record
+        const int NT = dep_q + 1, cut = ST / 2;
+        const int64_t* eforced = (const int64_t*)expect("lm_forced");
+        const int64_t* eout = (const int64_t*)expect("lm_out");
+        const float* etl = (const float*)expect("lm_text_logits");
+        const float* eal = (const float*)expect("lm_audio_logits");
+        mmi_sampling sp; memset(&sp, 0, sizeof(sp));
+        sp.use_sampling = 0; sp.temp = 0.8f; sp.temp_text = 0.7f; sp.top_k = 250; sp.top_k_text = 25; sp.seed = 0;
+        int held = 0, checks = 0;
+        auto holds = [&](int rc, int want) { ++checks; held += rc == want; if (rc != want) printf("  refusal check %d: status %d, expected %d\n", checks, rc, want); };
+        struct Run { int R, rows; bool many; };
+        for (const Run run : {Run{B, 2 * B, false}, Run{B, B, false}, Run{66, 128, true}}) {
+            const int R = run.R;
+            mmi_lm* lm = nullptr;
+            if (run.many) MCK(mmi_lm_create_rows(&lc, nullptr, ld.data(), (int32_t)ld.size(), 128, &lm));
+            else MCK(mmi_lm_create(&lc, ld.data(), (int32_t)ld.size(), B, &lm));
+            int64_t *duc, *dforced, *dout, *dpu, *dpt, *dlast; float *dtl, *dal;
+            HCK(hipMalloc((void**)&duc, (size_t)R * n_user * 8)); HCK(hipMalloc((void**)&dforced, (size_t)R * NT * 8));
+            HCK(hipMalloc((void**)&dout, (size_t)R * NT * 8)); HCK(hipMalloc((void**)&dlast, (size_t)R * NT * 8));
+            HCK(hipMalloc((void**)&dpu, (size_t)R * n_user * cut * 8)); HCK(hipMalloc((void**)&dpt, (size_t)R * NT * cut * 8));
+            HCK(hipMalloc((void**)&dtl, (size_t)R * text_card * 4)); HCK(hipMalloc((void**)&dal, (size_t)R * dep_q * card * 4));
+            std::vector<int32_t> sess(R);
+            for (int r = 0; r < R; ++r) sess[r] = r;
+            if (!run.many && run.rows == 2 * B) {
+                holds(mmi_lm_prefill_rows(lm), 0);
+                holds(mmi_lm_enable_prefill(lm, 129), MMI_ERR_UNSUPPORTED);
+                holds(mmi_lm_enable_prefill(lm, 33), MMI_ERR_UNSUPPORTED);             // a handle of the 16-row tile
+                MCK(mmi_lm_streaming_start(lm, R, &sp, nullptr));
+                holds(mmi_lm_prefill(lm, sess.data(), R, dpu, dpt, cut, nullptr), MMI_ERR_STATE);      // not enabled
+                holds(mmi_lm_enable_prefill(lm, 4), MMI_ERR_STATE);                    // while streaming
+                MCK(mmi_lm_streaming_stop(lm));
+            }
+            MCK(mmi_lm_enable_prefill(lm, run.rows));
+            MCK(mmi_lm_streaming_start(lm, R, &sp, nullptr));
+            const int64_t bytes_with = mmi_lm_state_bytes(lm);
+            std::vector<int64_t> pu((size_t)R * n_user * cut), pt((size_t)R * NT * cut);
+            for (int f = 0; f < cut; ++f) {
+                std::vector<int64_t> uc1((size_t)B * n_user);
+                for (size_t i = 0; i < uc1.size(); ++i) uc1[i] = (int64_t)((u_of(9000u + f, (uint32_t)i) + 1.0f) * 32768.0f) % card;
+                for (int r = 0; r < R; ++r) {
+                    for (int c = 0; c < n_user; ++c) pu[((size_t)r * n_user + c) * cut + f] = uc1[(size_t)(r % B) * n_user + c];
+                    for (int c = 0; c < NT; ++c) pt[((size_t)r * NT + c) * cut + f] = eforced[((size_t)f * B + r % B) * NT + c];
+                }
+            }
+            HCK(hipMemcpy(dpu, pu.data(), pu.size() * 8, hipMemcpyHostToDevice));
+            HCK(hipMemcpy(dpt, pt.data(), pt.size() * 8, hipMemcpyHostToDevice));
+            if (!run.many && run.rows == 2 * B) {
+                std::vector<int32_t> twice(R, 0);
+                holds(R > 1 ? mmi_lm_prefill(lm, twice.data(), R, dpu, dpt, cut, nullptr) : MMI_ERR_INVALID, MMI_ERR_INVALID);
+                holds(mmi_lm_prefill(lm, sess.data(), R, dpu, dpt, 0, nullptr), MMI_ERR_INVALID);
+                holds(mmi_lm_prefill(lm, sess.data(), run.rows + 1, dpu, dpt, cut, nullptr), MMI_ERR_INVALID);
+            }
+            MCK(mmi_lm_prefill(lm, sess.data(), R, dpu, dpt, cut, nullptr));
+            MCK(mmi_lm_last_tokens(lm, dlast, nullptr));
+            HCK(hipDeviceSynchronize());
+            std::vector<int64_t> last((size_t)R * NT);
+            HCK(hipMemcpy(last.data(), dlast, last.size() * 8, hipMemcpyDeviceToHost));
+            long last_diffs = 0, tok_diffs = 0; double worst_max = 0, worst_mean = 0;
+            for (int r = 0; r < R; ++r)
+                for (int c = 0; c < NT; ++c) last_diffs += last[(size_t)r * NT + c] != eforced[((size_t)(cut - 1) * B + r % B) * NT + c];
+            auto site = [&](const float* a, const float* r, int n) {
+                double mx = 1e-6, dmax = 0, dsum = 0;
+                for (int i = 0; i < n; ++i) { mx = fmax(mx, fabs(r[i])); const double d = fabs(a[i] - r[i]); dmax = fmax(dmax, d); dsum += d; }
+                worst_max = fmax(worst_max, dmax / mx); worst_mean = fmax(worst_mean, dsum / n / mx);
+            };
+            for (int s = cut; s < ST; ++s) {
+                std::vector<int64_t> uc1((size_t)B * n_user), uc((size_t)R * n_user), fo((size_t)R * NT);
+                for (size_t i = 0; i < uc1.size(); ++i) uc1[i] = (int64_t)((u_of(9000u + s, (uint32_t)i) + 1.0f) * 32768.0f) % card;
+                for (int r = 0; r < R; ++r) {
+                    memcpy(uc.data() + (size_t)r * n_user, uc1.data() + (size_t)(r % B) * n_user, (size_t)n_user * 8);
+                    memcpy(fo.data() + (size_t)r * NT, eforced + ((size_t)s * B + r % B) * NT, (size_t)NT * 8);
+                }
+                HCK(hipMemcpy(duc, uc.data(), uc.size() * 8, hipMemcpyHostToDevice));
+                HCK(hipMemcpy(dforced, fo.data(), fo.size() * 8, hipMemcpyHostToDevice));
+                MCK(mmi_lm_force_next_tokens(lm, dforced, nullptr));
+                int32_t valid = 0;
+                MCK(mmi_lm_step(lm, duc, n_user, dout, dtl, dal, nullptr, R, &valid, nullptr));
+                HCK(hipDeviceSynchronize());
+                std::vector<int64_t> o((size_t)R * NT); std::vector<float> tl((size_t)R * text_card), al((size_t)R * dep_q * card);
+                HCK(hipMemcpy(o.data(), dout, o.size() * 8, hipMemcpyDeviceToHost));
+                HCK(hipMemcpy(tl.data(), dtl, tl.size() * 4, hipMemcpyDeviceToHost));
+                HCK(hipMemcpy(al.data(), dal, al.size() * 4, hipMemcpyDeviceToHost));
+                for (int r = 0; r < R; ++r) {
+                    const int b = r % B;
+                    for (int i = 0; i < NT; ++i) tok_diffs += o[(size_t)r * NT + i] != eout[((size_t)s * B + b) * NT + i];
+                    site(tl.data() + (size_t)r * text_card, etl + ((size_t)s * B + b) * text_card, text_card);
+                    for (int k = 0; k < dep_q; ++k) site(al.data() + ((size_t)r * dep_q + k) * card, eal + (((size_t)s * B + b) * dep_q + k) * card, card);
+                }
+            }
+            MCK(mmi_lm_streaming_stop(lm));
+            MCK(mmi_lm_enable_prefill(lm, 0));
+            MCK(mmi_lm_streaming_start(lm, R, &sp, nullptr));
+            const int64_t bytes_without = mmi_lm_state_bytes(lm);
+            MCK(mmi_lm_streaming_stop(lm));
+            printf("lm prefill, %d sessions, %d rows per pass (%lld k_gemm_rows launches): %d frames prefilled; last_tokens differ in %ld entries (must be 0); "
+                   "%ld of %d token-ring outputs of the next %d steps differ from the oracle (must be 0); logits worst max %.4f (<= 0.05), worst mean "
+                   "%.4f (<= 0.012); state bytes %lld with, %lld without (must be equal)\n", R, run.rows, (long long)mmi_lm_stat(lm, 4), cut, last_diffs,
+                   tok_diffs, (ST - cut) * R * NT, ST - cut, worst_max, worst_mean, (long long)bytes_with, (long long)bytes_without);
+            failures += last_diffs != 0 || tok_diffs != 0 || !(worst_max <= 0.05) || !(worst_mean <= 0.012) || bytes_with != bytes_without ||
+                        (run.many && mmi_lm_stat(lm, 4) <= 0) || cut < 1;
+            mmi_lm_destroy(lm);
+            hipFree(duc); hipFree(dforced); hipFree(dout); hipFree(dlast); hipFree(dpu); hipFree(dpt); hipFree(dtl); hipFree(dal);
+        }
+        printf("lm prefill: %d of %d refusal checks held\n", held, checks);
+        failures += held != checks;
     }
     printf(failures ? "SELFTEST FAILED\n" : "SELFTEST PASSED\n");
     return failures ? 1 : 0;
