@@ -696,6 +696,56 @@ int mmi_lm_debug_prefill_attn(mmi_lm* lm, const void* q_bf16, const int32_t* row
                               int32_t rings, int32_t H, int32_t Dh, int32_t cap, int32_t context, int32_t kv_dtype, void* out_bf16,
                               mmi_stream stream);
 
+/* ---- teacher-forced scoring of known frames on the prefill path ------------------------------------------------
+ * The counterpart of LMModel.forward (lm.py:322-377: the text head over all positions, and forward_depformer_training, lm.py:410-448,
+ * the depth transformer over all positions with the given tokens as its inputs), on a live session.
+ *
+ * mmi_lm_score on sessions S with T frames is the sequence of T forced steps that defines mmi_lm_prefill (exec mask = S, every
+ * step preceded by mmi_lm_force_next_tokens with every entry >= 0) and returns, for every (session, frame, site) - site 0 the text
+ * head, sites 1 .. dep_q the audio heads - what that step's parity taps return; under forcing micro-step k's input is the given
+ * token of site k - 1 of the same frame.  These are raw model logits: temperature, repetition penalty, top-k, top-p and
+ * per-session sampling settings play no part.  128 known frames cost one pass over the weights instead of 128 steps.
+ *
+ * mmi_lm_enable_score(lm, on): after mmi_lm_enable_prefill, before streaming_start.  The next streaming_start allocates the scoring
+ * scratch beside the prefill scratch, outside the streaming-state arena: mmi_lm_state_bytes and snapshots are unchanged, and a
+ * handle with prefill but without scoring allocates and launches what it did.  MMI_ERR_STATE while streaming or without prefill;
+ * MMI_ERR_UNSUPPORTED (by name) for low-rank or demuxed depformer embeddings, for more than 32 rows per pass with the depth
+ * transformer on its own 16-row tile, and for a head whose width is no multiple of 8 or exceeds 32768.
+ *
+ * mmi_lm_score(lm, sessions, n, user_codes, tokens, T, commit, out, stream): arguments as mmi_lm_prefill.  Stream ordered, nothing
+ * synchronises.
+ *   commit = 1  the named sessions end exactly where mmi_lm_prefill of the same arguments leaves them - every region of the state
+ *               arena, all rings included, byte for byte (the same kernels in the same order).  T may span several passes.
+ *   commit = 0  nothing of the handle's streaming state changes (no offsets, no rings, no delay ring): pure rescoring.  The call
+ *               must fit one pass: n * T > rows is refused with MMI_ERR_INVALID.
+ *   In both modes sessions not named are untouched, and neither the draw counter nor the step's depth-transformer cache is
+ *   written: what a neighbour samples does not depend on a score call between two steps.
+ *   out->logp          device f32 [n][T][1 + dep_q]: ln softmax(logits)[given token], in fp32 from the bf16 head output; -inf where
+ *                      the given token lies outside the head's range (an initial-token id).  Must not be NULL
+ *   out->argmax        device i32 [n][T][1 + dep_q] or NULL: the lowest index among the largest logits
+ *   out->text_logits   device f32 [n][T][text_card_out] or NULL
+ *   out->audio_logits  device f32 [n][T][dep_q][card] or NULL
+ *   A NaN logit makes that site's logp NaN (its argmax is then unspecified).
+ * Refusals, all before anything is written: every refusal of mmi_lm_prefill in its own words; MMI_ERR_STATE when scoring is not
+ * enabled; MMI_ERR_INVALID for a NULL out or out->logp and for commit = 0 beyond one pass.
+ *
+ * mmi_lm_debug_score_rows: parity tap of the output kernel (tests) - k_score_logprob alone, through the pass's launch function, on
+ * caller-supplied rows: logits_bf16 device bf16 [rows][N] (16-byte aligned, N a multiple of 8, <= 32768), targets device i32
+ * [rows], logp f32 [rows], argmax i32 [rows], logits_f32 f32 [rows][N] or NULL.  Any handle; touches no stream state. */
+struct mmi_score_out {
+    float* logp;
+    int32_t* argmax;
+    float* text_logits;
+    float* audio_logits;
+};
+typedef struct mmi_score_out mmi_score_out;
+int mmi_lm_enable_score(mmi_lm* lm, int32_t on);
+int32_t mmi_lm_score_enabled(const mmi_lm* lm);         /* a negative status for a NULL handle */
+int mmi_lm_score(mmi_lm* lm, const int32_t* sessions, int32_t n, const int64_t* user_codes, const int64_t* tokens, int32_t T,
+                 int32_t commit, const mmi_score_out* out, mmi_stream stream);
+int mmi_lm_debug_score_rows(mmi_lm* lm, const void* logits_bf16, const int32_t* targets, int32_t rows, int32_t N, float* logp,
+                            int32_t* argmax, float* logits_f32, mmi_stream stream);
+
 /* The regions of the streaming-state arena - the buffer of mmi_lm_state_save - by name (tests compare two streams region by
  * region): one line "name<TAB>offset<TAB>bytes<TAB>rows<TAB>kind" each.  rows > 0: the region is `rows` equal slices, one per
  * session (model row); kind 1 = state the next step reads ("exec", "offsets", "cache", "text_tok", "audio_tok", "rng", "rowtab",

@@ -75,6 +75,11 @@ class RowCondition(C.Structure):
     _fields_ = [("cfg_coef", C.c_float), ("condition_sum", C.c_void_p), ("condition_cross", C.c_void_p), ("cross_len", C.c_int32)]
 
 
+class ScoreOut(C.Structure):
+    """struct mmi_score_out: where mmi_lm_score writes (device pointers; all but `logp` may be NULL)."""
+    _fields_ = [("logp", C.c_void_p), ("argmax", C.c_void_p), ("text_logits", C.c_void_p), ("audio_logits", C.c_void_p)]
+
+
 class TTSParams(C.Structure):
     """struct mmi_tts_params: StateMachine's and TTSModel's settings (mmi_lm_enable_tts_machine)."""
     _fields_ = [("text_card", C.c_int32), ("new_word", C.c_int32), ("pad", C.c_int32), ("zero", C.c_int32),
@@ -227,6 +232,10 @@ SIGNATURES = {
     "mmi_lm_last_tokens": (C.c_int, [_P, _P, _P]),
     "mmi_lm_debug_prefill_attn": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, _P, _P]),
+    "mmi_lm_enable_score": (C.c_int, [_P, C.c_int32]),
+    "mmi_lm_score_enabled": (C.c_int32, [_P]),
+    "mmi_lm_score": (C.c_int, [_P, C.POINTER(C.c_int32), C.c_int32, _P, _P, C.c_int32, C.c_int32, C.POINTER(ScoreOut), _P]),
+    "mmi_lm_debug_score_rows": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "mmi_lm_debug_state_regions": (C.c_int64, [_P, _P, C.c_int64]),
     "mmi_lm_launch_list": (C.c_int64, [_P, _P, C.c_int64]),
     "mmi_mimi_launch_list": (C.c_int64, [_P, C.c_int32, _P, C.c_int64]),
@@ -251,10 +260,12 @@ _SINCE_KV4 = ("mmi_lm_debug_kv4_quantize", "mmi_lm_debug_kv_ring")
 _SINCE_ATTN_TAP = ("mmi_lm_debug_attn",)
 _SINCE_PREFILL = ("mmi_lm_enable_prefill", "mmi_lm_prefill_rows", "mmi_lm_prefill", "mmi_lm_last_tokens", "mmi_lm_debug_prefill_attn",
                   "mmi_lm_debug_state_regions")
+_SINCE_SCORE = ("mmi_lm_enable_score", "mmi_lm_score_enabled", "mmi_lm_score", "mmi_lm_debug_score_rows")
 
 
 def _missing(name, path):
-    what = ("chunked prefill" if name in _SINCE_PREFILL else
+    what = ("teacher-forced scoring" if name in _SINCE_SCORE else
+            "chunked prefill" if name in _SINCE_PREFILL else
             "the attention tap" if name in _SINCE_ATTN_TAP else
             "the 4-bit KV ring" if name in _SINCE_KV4 else
             "nucleus sampling" if name in _SINCE_NUCLEUS else
@@ -275,7 +286,7 @@ class Lib:
         self.path = Path(path)
         self.cdll = C.CDLL(str(self.path))
         for name, (res, args) in SIGNATURES.items():
-            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION + _SINCE_TTS_MACHINE + _SINCE_MANY_ROWS + _SINCE_ADAPTERS + _SINCE_NUCLEUS + _SINCE_KV4 + _SINCE_ATTN_TAP + _SINCE_PREFILL and not hasattr(self.cdll, name):
+            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION + _SINCE_TTS_MACHINE + _SINCE_MANY_ROWS + _SINCE_ADAPTERS + _SINCE_NUCLEUS + _SINCE_KV4 + _SINCE_ATTN_TAP + _SINCE_PREFILL + _SINCE_SCORE and not hasattr(self.cdll, name):
                 # an older build of the engine (MMI_LIB_PATH, A/B runs against a parent build): everything else works, these refuse
                 setattr(self, name, _missing(name, self.path))
                 continue

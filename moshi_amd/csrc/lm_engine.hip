@@ -4,6 +4,7 @@
 // the kernels of lm_kernels.h, captured into a single hipGraph.
 #include "lm_kernels.h"
 #include "lm_prefill_kernels.h"
+#include "lm_score_kernels.h"
 #include "mmi_graph.h"
 
 #include <math.h>
@@ -81,6 +82,7 @@ struct mmi_lm {
     std::vector<int> dep_sched;
     int dep_nw = 0;
     bool demux = false;
+    bool dep_low_rank = false;      // depformer_low_rank_embeddings (the tables are expanded at create)
     uint16_t *text_emb2 = nullptr, *dep_emb2 = nullptr;
     std::vector<DepLayerW> dep_layers;
     // parity tap (mmi_lm_debug_linear): every packed linear / every norm vector by its state-dict key
@@ -199,6 +201,20 @@ struct mmi_lm {
         uint8_t *sk = nullptr, *sv = nullptr, *sks = nullptr, *svs = nullptr;     // the staged block in ring format
         float* partial = nullptr;       // [4][rows][dim] split-K partial sums
     } pf;
+    // teacher-forced scoring on the prefill path (mmi_lm_enable_score): scratch of its own in the prefill arena - the
+    // step's depth-transformer cache (dkc / dvc) and activations are not touched, so a score call between two steps changes nothing
+    // a neighbour reads
+    bool score_on = false;
+    struct {
+        uint16_t* tout = nullptr;       // packed transformer_out of the pass's rows
+        uint16_t* tlog = nullptr;       // [rows][text_card_out] bf16 text logits
+        int* targets = nullptr;         // [rows][1 + dep_q] the given tokens of the pass
+        uint16_t* dpre = nullptr;       // [rows][depformer_dim] depformer_in of the micro-step in flight
+        uint16_t *dx = nullptr, *dxn = nullptr, *datt = nullptr, *dhb = nullptr;   // packed at the depth transformer's tile
+        uint16_t* dqkv = nullptr;       // [rows][3 * depformer_dim]
+        uint16_t *dkc = nullptr, *dvc = nullptr;        // [dep_layers][rows][Hd][dep_q][Dhd]
+        uint16_t* alog = nullptr;       // [dep_q][rows][card] bf16 audio logits
+    } sc;
     long offset_cpu = 0;
     int attn_ns = 1;                                // workgroups per (session, head) of the decode attention (attn_splits)
     long depth_bound = 0;                           // no session's offset exceeds this (steps since streaming_start / the last seek; resets
@@ -1709,6 +1725,7 @@ static int lm_create_rows(const mmi_lm_cfg* cfg, const mmi_lm_cfg_ext* ext, cons
     lm->dep_sched = sched;
     lm->dep_nw = nw;
     lm->demux = demux;
+    lm->dep_low_rank = low_rank != 0;
     if (hipGetDevice(&lm->device) != hipSuccess) lm->device = -1;
     lm->cfg = norm_cfg;
     lm->max_batch = max_batch;
@@ -1911,6 +1928,52 @@ static int prefill_refusal(const mmi_lm* lm, int rows) {
     return MMI_OK;
 }
 
+// what a handle must be to score (mmi_lm_enable_score; checked again when the scratch is allocated)
+static int score_refusal(const mmi_lm* lm) {
+    const mmi_lm_cfg& c = lm->cfg;
+    if (lm->prefill_rows <= 0) return mmi_fail(MMI_ERR_STATE, "mmi_lm_enable_score: call mmi_lm_enable_prefill first (scoring runs on the prefill pass)");
+    if (c.dep_q > 0 && (lm->demux || lm->text_emb2 || lm->dep_low_rank))
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "score: low-rank or demuxed depformer embeddings are not supported");
+    if (c.dep_q > 0 && mmi_cdiv(lm->prefill_rows, lm->Td) > (lm->Td == 32 ? 4 : 2))
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "score: the depth transformer on its own 16-row tile (MMI_DEP_TILE) runs passes of at most 32 rows");
+    if (c.text_card_out % 8 || c.text_card_out > 8 * MMI_SCORE_THREADS * MMI_SCORE_PIECES || (c.dep_q > 0 && (c.card % 8 || c.card > 8 * MMI_SCORE_THREADS * MMI_SCORE_PIECES)))
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "score: a head's width must be a multiple of 8 and at most 32768");
+    return MMI_OK;
+}
+
+// the scoring scratch, beside the prefill scratch in its arena (outside the streaming-state arena)
+static int score_alloc(mmi_lm* lm, hipStream_t s) {
+    const mmi_lm_cfg& c = lm->cfg;
+    int rc = score_refusal(lm);
+    if (rc) return rc;
+    const int rows = lm->prefill_rows, d = c.dim, dd = c.depformer_dim, q = c.dep_q;
+    const size_t mt = (size_t)mmi_cdiv(rows, lm->T), mtd = (size_t)mmi_cdiv(rows, lm->Td);
+    auto packed_d = [&](int features) { return mtd * packed_ksteps_t(lm, lm->Td, features) * 512; };
+    MmiArena& A = lm->pf_mem;
+    auto& S = lm->sc;
+    bool ok = true;
+    ok &= hipSuccess == A.alloc(&S.tout, mt * packed_ksteps(lm, d) * 512);
+    ok &= hipSuccess == A.alloc(&S.tlog, (size_t)rows * c.text_card_out);
+    ok &= hipSuccess == A.alloc(&S.targets, (size_t)rows * (1 + q));
+    if (!ok) return mmi_fail(MMI_ERR_HIP, "out of device memory (score scratch)");
+    MMI_HIP_CHECK(hipMemsetAsync(S.tout, 0, mt * packed_ksteps(lm, d) * 512 * sizeof(uint16_t), s));
+    if (q == 0) return MMI_OK;
+    const size_t dkv = (size_t)c.depformer_num_layers * rows * dd * q;       // [layers][rows][Hd][dep_q][Dhd]
+    ok &= hipSuccess == A.alloc(&S.dpre, (size_t)rows * dd);
+    ok &= hipSuccess == A.alloc(&S.dx, packed_d(dd));
+    ok &= hipSuccess == A.alloc(&S.dxn, packed_d(dd));
+    ok &= hipSuccess == A.alloc(&S.datt, packed_d(dd));
+    ok &= hipSuccess == A.alloc(&S.dhb, packed_d(c.depformer_ffn_hidden));
+    ok &= hipSuccess == A.alloc(&S.dqkv, (size_t)rows * 3 * dd);
+    ok &= hipSuccess == A.alloc(&S.dkc, dkv);
+    ok &= hipSuccess == A.alloc(&S.dvc, dkv);
+    ok &= hipSuccess == A.alloc(&S.alog, (size_t)q * rows * c.card);
+    if (!ok) return mmi_fail(MMI_ERR_HIP, "out of device memory (score scratch)");
+    struct { uint16_t* p; int f; } pk[] = {{S.dx, dd}, {S.dxn, dd}, {S.datt, dd}, {S.dhb, c.depformer_ffn_hidden}};
+    for (auto& e : pk) MMI_HIP_CHECK(hipMemsetAsync(e.p, 0, packed_d(e.f) * sizeof(uint16_t), s));
+    return MMI_OK;
+}
+
 static int prefill_alloc(mmi_lm* lm, hipStream_t s) {
     const mmi_lm_cfg& c = lm->cfg;
     const int rows = lm->prefill_rows, d = c.dim, H = c.num_heads, Dh = d / H, kvf = kv_form(c.kv_cache_dtype);
@@ -1941,7 +2004,7 @@ static int prefill_alloc(mmi_lm* lm, hipStream_t s) {
     // packed activations: the padding rows / columns of a fragment are never written and must read as zero
     struct { uint16_t* p; int f; } pk[] = {{P.x, d}, {P.xn, d}, {P.att, d}, {P.hb, c.ffn_hidden}};
     for (auto& e : pk) MMI_HIP_CHECK(hipMemsetAsync(e.p, 0, packed(e.f) * sizeof(uint16_t), s));
-    return MMI_OK;
+    return lm->score_on ? score_alloc(lm, s) : (int)MMI_OK;
 }
 
 template <int KVF>
@@ -1995,7 +2058,82 @@ static int pf_norm(mmi_lm* lm, hipStream_t s, int rows, int pending, const uint1
 }
 
 // One pass: F frames (f0 .. f0 + F - 1 of the call's arrays) of the n sessions of `p`, eager launches on `s`
-static int prefill_pass(mmi_lm* lm, hipStream_t s, PfArgs p, const int64_t* user, const int64_t* toks) {
+static int launch_score_rows(hipStream_t s, const ScoreArgs& a, int rows, int sites) {
+    MMI_LAUNCH(k_score_logprob, dim3(rows, sites), MMI_SCORE_THREADS, 0, s, a);
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+
+// RMSNorm of the depth transformer's rows of a scoring pass (the norm launch of the step program's norm + GEMM form)
+static int sc_dep_norm(mmi_lm* lm, hipStream_t s, int rows, const uint16_t* alpha) {
+    const int D = lm->cfg.depformer_dim;
+    int nth = mmi_cdiv(D / 8, 64) * 64;
+    if (nth > 1024) nth = 1024;
+    MMI_LAUNCH(k_resid_rmsnorm, rows, nth, 0, s, lm->sc.dx, (const float*)nullptr, 0, rows, alpha, lm->sc.dxn, D, lm->Td, packed_ksteps_t(lm, lm->Td, D), 1e-8f,
+               (uint8_t*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+
+// The tail of a scoring pass, behind out_norm: the text head, the depth transformer as dep_q micro-steps on all R rows (micro-step
+// k's input token is the given one of site k, so the rows run side by side), the logit heads, and k_score_logprob - one launch for
+// the text sites, one for all audio sites.  Everything lives in lm->sc; nothing of the step's state is written.
+static int score_heads(mmi_lm* lm, hipStream_t s, const PfArgs& p, const int64_t* toks, const mmi_score_out* out) {
+    const mmi_lm_cfg& c = lm->cfg;
+    const int R = p.n * p.F, q = c.dep_q, sites = 1 + q, rows = lm->prefill_rows;
+    const int dd = c.depformer_dim, Hd = c.depformer_num_heads, Dhd = q ? dd / Hd : 0;
+    auto& S = lm->sc;
+    int rc;
+    MMI_LAUNCH(k_sc_targets, mmi_cdiv(R * sites, 256), 256, 0, s, p, sites, (const long*)toks, S.targets);
+    MMI_CHECK_LAUNCH();
+    if ((rc = pf_gemm(lm, s, lm->text_linear, R, S.tout, S.tlog, c.text_card_out, false, MMI_EPI_STORE, nullptr))) return rc;
+    ScoreArgs a;
+    memset(&a, 0, sizeof(a));
+    a.logits = S.tlog; a.ld = c.text_card_out; a.N = c.text_card_out;
+    a.targets = S.targets; a.tgt_stride = sites; a.tgt_off = 0;
+    a.logp = out->logp; a.argmax = out->argmax; a.out_stride = sites; a.out_off = 0;
+    a.lf32 = out->text_logits; a.lf32_row = c.text_card_out;
+    a.F = p.F; a.Tall = p.T; a.f0 = p.f0;
+    if ((rc = launch_score_rows(s, a, R, 1))) return rc;
+    if (q == 0) return MMI_OK;
+    const size_t dkv_layer = (size_t)rows * Hd * q * Dhd;
+    const int dks = packed_ksteps_t(lm, lm->Td, dd);
+    for (int k = 0; k < q; ++k) {
+        if ((rc = pf_gemm(lm, s, lm->dep_in[k], R, S.tout, S.dpre, dd, false, MMI_EPI_STORE, nullptr))) return rc;
+        ScDepInArgs in;
+        in.pre = S.dpre; in.ld = dd; in.emb = lm->dep_emb[k]; in.targets = S.targets; in.sites = sites; in.site = k;
+        in.out = S.dx; in.D = dd; in.T = lm->Td; in.ksteps = dks;
+        MMI_LAUNCH(k_sc_dep_input, R, 128, 0, s, in);
+        MMI_CHECK_LAUNCH();
+        for (int l = 0; l < c.depformer_num_layers; ++l) {
+            const DepLayerW& L = lm->dep_layers[l];
+            if ((rc = sc_dep_norm(lm, s, R, L.n1))) return rc;
+            if ((rc = pf_gemm(lm, s, L.in_proj[k], R, S.dxn, S.dqkv, 3 * dd, false, MMI_EPI_STORE, nullptr))) return rc;
+            DepAttnArgs da;
+            da.qkv = S.dqkv; da.kc = S.dkc + l * dkv_layer; da.vc = S.dvc + l * dkv_layer; da.out = S.datt;
+            da.B = R; da.H = Hd; da.Dh = Dhd; da.steps = q; da.k = k;
+            da.T = lm->Td; da.out_ksteps = dks;
+            if (Dhd % 8 == 0 && q <= 8) MMI_LAUNCH((k_dep_attn8<4>), mmi_cdiv(R * Hd, 4), 256, 0, s, da);
+            else if (q > 16) MMI_LAUNCH((k_dep_attn<32>), R * Hd, 64, 0, s, da);
+            else MMI_LAUNCH((k_dep_attn<16>), R * Hd, 64, 0, s, da);
+            MMI_CHECK_LAUNCH();
+            if ((rc = pf_gemm(lm, s, L.out_proj[k], R, S.datt, S.dx, dd, true, MMI_EPI_RESID, S.dx))) return rc;
+            if ((rc = sc_dep_norm(lm, s, R, L.n2))) return rc;
+            if ((rc = pf_gemm(lm, s, L.ffn_in[k], R, S.dxn, S.dhb, c.depformer_ffn_hidden, true, MMI_EPI_GATE, nullptr))) return rc;
+            if ((rc = pf_gemm(lm, s, L.ffn_out[k], R, S.dhb, S.dx, dd, true, MMI_EPI_RESID, S.dx))) return rc;
+        }
+        if ((rc = pf_gemm(lm, s, lm->dep_lin[k], R, S.dx, S.alog + (size_t)k * rows * c.card, c.card, false, MMI_EPI_STORE, nullptr))) return rc;
+    }
+    a.logits = S.alog; a.site_stride = (long)rows * c.card; a.ld = c.card; a.N = c.card;
+    a.tgt_off = 1; a.out_off = 1;
+    a.lf32 = out->audio_logits; a.lf32_row = (long)q * c.card; a.lf32_site = c.card;
+    return launch_score_rows(s, a, R, q);
+}
+
+// score: null = a prefill pass.  Else the pass also runs the last layer to its end, out_norm and score_heads; commit = 0 skips
+// k_pf_commit_kv and k_pf_commit_state (the attention reads the pass's own block from staging either way)
+static int prefill_pass(mmi_lm* lm, hipStream_t s, PfArgs p, const int64_t* user, const int64_t* toks, const mmi_score_out* score = nullptr,
+                        bool commit = true) {
     const mmi_lm_cfg& c = lm->cfg;
     const int d = c.dim, H = c.num_heads, Dh = d / H, R = p.n * p.F, n_user = c.n_q - c.dep_q, kvf = kv_form(c.kv_cache_dtype);
     auto& P = lm->pf;
@@ -2027,18 +2165,29 @@ static int prefill_pass(mmi_lm* lm, hipStream_t s, PfArgs p, const int64_t* user
         a.out = P.att; a.T = lm->T; a.out_ksteps = packed_ksteps(lm, d);
         a.H = H; a.cap = c.context; a.context = c.context; a.n = p.n; a.F = p.F;
         const bool last = l + 1 == c.num_layers;        // the last layer's attention output, FFN and out_norm feed nothing
-        if (!last && (rc = launch_attn_prefill(s, a, kvf, Dh))) return rc;
+        if ((!last || score) && (rc = launch_attn_prefill(s, a, kvf, Dh))) return rc;
         const int cblocks = (int)mmi_cdiv64((int64_t)R * H * (pf_row_bytes(kvf, Dh) / 16), 256);
-        if (kvf == 2) MMI_LAUNCH(k_pf_commit_kv<2>, cblocks, 256, 0, s, a, Dh);
-        else if (kvf == 1) MMI_LAUNCH(k_pf_commit_kv<1>, cblocks, 256, 0, s, a, Dh);
-        else MMI_LAUNCH(k_pf_commit_kv<0>, cblocks, 256, 0, s, a, Dh);
-        MMI_CHECK_LAUNCH();
-        if (last) break;
+        if (commit) {
+            if (kvf == 2) MMI_LAUNCH(k_pf_commit_kv<2>, cblocks, 256, 0, s, a, Dh);
+            else if (kvf == 1) MMI_LAUNCH(k_pf_commit_kv<1>, cblocks, 256, 0, s, a, Dh);
+            else MMI_LAUNCH(k_pf_commit_kv<0>, cblocks, 256, 0, s, a, Dh);
+            MMI_CHECK_LAUNCH();
+        }
+        if (last && !score) break;
         if ((rc = pf_gemm_resid(lm, s, L.out_proj, R, P.att, &pending))) return rc;
         if ((rc = pf_norm(lm, s, R, pending, L.n2))) return rc;
         if ((rc = pf_gemm(lm, s, L.ffn_in, R, P.xn, P.hb, c.ffn_hidden, true, MMI_EPI_GATE, nullptr))) return rc;
         if ((rc = pf_gemm_resid(lm, s, L.ffn_out, R, P.hb, &pending))) return rc;
     }
+    if (score) {
+        int nth = mmi_cdiv(d / 8, 64) * 64;
+        if (nth > 1024) nth = 1024;
+        MMI_LAUNCH(k_resid_rmsnorm, R, nth, 0, s, P.x, (const float*)P.partial, pending, R, (const uint16_t*)lm->out_norm, lm->sc.tout, d, lm->T,
+                   packed_ksteps(lm, d), 1e-8f, (uint8_t*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
+        MMI_CHECK_LAUNCH();
+        if ((rc = score_heads(lm, s, p, toks, score))) return rc;
+    }
+    if (!commit) return MMI_OK;
     MMI_LAUNCH(k_pf_commit_state, mmi_cdiv(p.n, 64), 64, 0, s, t, p, (const long*)user, n_user, (const long*)toks, lm->text_tok, lm->audio_tok);
     MMI_CHECK_LAUNCH();
     return MMI_OK;
@@ -2098,6 +2247,87 @@ extern "C" int mmi_lm_prefill(mmi_lm* lm, const int32_t* sessions, int32_t n, co
     lm->offset_cpu += T;
     if (lm->depth_bound < (1L << 40)) lm->depth_bound += T;
     return MMI_OK;
+}
+
+// ---- teacher-forced scoring on the prefill path ---------------------------------------------------------------
+extern "C" int mmi_lm_enable_score(mmi_lm* lm, int32_t on) {
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (lm->streaming) return mmi_fail(MMI_ERR_STATE, "mmi_lm_enable_score: not while streaming");
+    if (on) {
+        const int rc = score_refusal(lm);
+        if (rc) return rc;
+    }
+    lm->score_on = on != 0;
+    return MMI_OK;
+}
+
+extern "C" int32_t mmi_lm_score_enabled(const mmi_lm* lm) {
+    if (!lm) return (int32_t)mmi_fail(MMI_ERR_INVALID, "null handle");
+    return lm->score_on ? 1 : 0;
+}
+
+extern "C" int mmi_lm_score(mmi_lm* lm, const int32_t* sessions, int32_t n, const int64_t* user_codes, const int64_t* tokens, int32_t T,
+                            int32_t commit, const mmi_score_out* out, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm || !sessions || !tokens || !out) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (!lm->streaming) return mmi_fail(MMI_ERR_STATE, "not streaming");
+    if (!lm->score_on || lm->prefill_rows <= 0 || !lm->sc.tout)
+        return mmi_fail(MMI_ERR_STATE, "score is not enabled: call mmi_lm_enable_prefill and mmi_lm_enable_score before streaming_start");
+    const mmi_lm_cfg& c = lm->cfg;
+    if (!user_codes && c.n_q > c.dep_q) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (!out->logp) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_score: out->logp must not be null");
+    if (T < 1) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_score: T must be >= 1");
+    if (n < 1 || n > lm->prefill_rows) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_score: 1 .. prefill_rows sessions per call");
+    PfArgs p;
+    memset(&p, 0, sizeof(p));
+    std::vector<uint8_t> seen(lm->gen_batch, 0);
+    for (int i = 0; i < n; ++i) {
+        if (sessions[i] < 0 || sessions[i] >= lm->gen_batch) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_score: session index out of range");
+        if (seen[sessions[i]]) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_score: a session is named twice");
+        seen[sessions[i]] = 1;
+        p.sess[i] = (uint8_t)sessions[i];
+    }
+    if (!commit && (long)n * T > lm->prefill_rows)
+        return mmi_fail(MMI_ERR_INVALID, "mmi_lm_score: commit = 0 must fit one pass (n * T <= prefill_rows): a later pass would need the earlier one's K/V in the ring");
+    // prefill's own refusals, in its words
+    if (lm->cfg_coef != 1.f || lm->batch != lm->gen_batch) return mmi_fail(MMI_ERR_UNSUPPORTED, "prefill: a guided stream (guidance twins) is not supported");
+    if (lm->hooks.on_text_logits || lm->hooks.on_text_token || lm->hooks.on_audio_tokens)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "prefill: not while per-step hooks are installed");
+    if (lm->tts || lm->lora_on) return mmi_fail(MMI_ERR_UNSUPPORTED, "prefill: not on a stream with the TTS machine or adapters");
+    hipStream_t s = (hipStream_t)stream;
+    p.n = n; p.T = T;
+    const int F = lm->prefill_rows / n;
+    for (int f0 = 0; f0 < T; f0 += F) {
+        p.f0 = f0;
+        p.F = T - f0 < F ? T - f0 : F;
+        const int rc = prefill_pass(lm, s, p, user_codes, tokens, out, commit != 0);
+        if (rc) return rc;
+    }
+    if (commit) {
+        lm->offset_cpu += T;
+        if (lm->depth_bound < (1L << 40)) lm->depth_bound += T;
+    }
+    return MMI_OK;
+}
+
+// Parity tap of the scoring output kernel (include/moshi_mi.h): k_score_logprob alone through the pass's launch function
+extern "C" int mmi_lm_debug_score_rows(mmi_lm* lm, const void* logits_bf16, const int32_t* targets, int32_t rows, int32_t N, float* logp,
+                                       int32_t* argmax, float* logits_f32, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm || !logits_bf16 || !targets || !logp || !argmax) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (rows < 1 || rows > (1 << 20)) return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_score_rows: 1 <= rows <= 2^20");
+    if (N < 8 || N % 8 || N > 8 * MMI_SCORE_THREADS * MMI_SCORE_PIECES)
+        return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_score_rows: N must be a multiple of 8 in [8, 32768]");
+    if ((uintptr_t)logits_bf16 % 16 || (uintptr_t)logits_f32 % 16 || (uintptr_t)targets % 4 || (uintptr_t)logp % 4 || (uintptr_t)argmax % 4)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_score_rows: the logits must be 16-byte aligned");
+    ScoreArgs a;
+    memset(&a, 0, sizeof(a));
+    a.logits = (const uint16_t*)logits_bf16; a.ld = N; a.N = N;
+    a.targets = targets; a.tgt_stride = 1;
+    a.logp = logp; a.argmax = argmax; a.out_stride = 1;
+    a.lf32 = logits_f32; a.lf32_row = N;
+    a.F = rows; a.Tall = rows; a.f0 = 0;
+    return launch_score_rows((hipStream_t)stream, a, rows, 1);
 }
 
 extern "C" int mmi_lm_last_tokens(mmi_lm* lm, int64_t* out, mmi_stream stream) {
@@ -2471,6 +2701,7 @@ extern "C" int mmi_lm_streaming_stop(mmi_lm* lm) {
     lm->prog.clear();
     lm->st.release();
     lm->pf_mem.release();
+    lm->sc = {};
     lm->tts = nullptr;
     lm->row_slot = nullptr;
     lm->lora_t = nullptr;

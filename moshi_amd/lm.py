@@ -130,13 +130,16 @@ class LMModel:
             enter a session `prefill_rows` rows at a time, one pass over the temporal weights each.  bf16 linears, no
             cross-attention layers, no adapters, no TTS machine; above 32 the handle must be built for more than 16 rows.
             None: off - the handle allocates and launches what it always did.
+        score: True (with `prefill_rows`) enables `LMGen.score` (mmi_lm_enable_score): teacher-forced scoring of
+            known frames on the prefill pass, with scratch of its own beside the prefill scratch.  Plain (not low-rank, not demuxed)
+            depformer embeddings.  False: the handle allocates and launches what a prefill handle does.
     """
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], config: Optional[LMConfig] = None,
                  device: torch.device | str = "cuda", max_batch: int = 32, lib: Optional[_capi.Lib] = None,
                  quantize: bool | str = False, fuser: Optional[ConditionFuser] = None, kv_cache: Optional[str] = None,
                  cross_capacity: Optional[int] = None, max_rows: Optional[int] = None,
-                 adapters: Optional[Tuple[int, int]] = None, prefill_rows: Optional[int] = None):
+                 adapters: Optional[Tuple[int, int]] = None, prefill_rows: Optional[int] = None, score: bool = False):
         if max_rows is not None:
             if max_batch > 64:
                 raise ValueError("max_rows and max_batch > 64 are mutually exclusive: max_rows alone sizes the handle")
@@ -211,6 +214,10 @@ class LMModel:
         if prefill_rows is not None:
             lib.check(lib.mmi_lm_enable_prefill(self._handle, int(prefill_rows)))
             self.prefill_rows = int(prefill_rows)
+        self.score = False
+        if score:
+            lib.check(lib.mmi_lm_enable_score(self._handle, 1))
+            self.score = True
 
     def __del__(self):
         try:
@@ -330,6 +337,22 @@ class LMModel:
             rows, int(n_blocks), int(rings), H, Dh, int(cap), int(cap if context is None else context), self.ATTN_RING_FORMS[ring],
             out.data_ptr(), _capi.stream_ptr(self.device)))
         return out
+
+    def debug_score_rows(self, logits: torch.Tensor, targets: torch.Tensor, want_f32: bool = True):
+        """Parity tap (tests; `mmi_lm_debug_score_rows`): the output kernel of `LMGen.score` alone, through the launch function of a
+        scoring pass.  `logits` bf16 [rows, N] (N a multiple of 8, at most 32768), `targets` int32 [rows].  Returns (logp f32 [rows],
+        argmax int32 [rows], the rows widened to f32 [rows, N] or None)."""
+        logits = logits.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        rows, N = logits.shape
+        targets = targets.to(device=self.device, dtype=torch.int32).contiguous()
+        assert targets.shape == (rows,), "one given token per row"
+        logp = torch.empty(rows, dtype=torch.float32, device=self.device)
+        argmax = torch.empty(rows, dtype=torch.int32, device=self.device)
+        wide = torch.empty(rows, N, dtype=torch.float32, device=self.device) if want_f32 else None
+        self._lib.check(self._lib.mmi_lm_debug_score_rows(self._handle, logits.data_ptr(), targets.data_ptr(), rows, N, logp.data_ptr(),
+                                                          argmax.data_ptr(), wide.data_ptr() if want_f32 else None,
+                                                          _capi.stream_ptr(self.device)))
+        return logp, argmax, wide
 
     def debug_linear(self, weight_name: str, x: torch.Tensor, path: str = "plain", alpha_name: Optional[str] = None,
                      want_codes: bool = False) -> dict:
@@ -536,6 +559,15 @@ class SessionCondition:
     conditioned logits untouched; another value needs a stream that was started with guidance."""
     cfg_coef: float = 1.0
     condition_tensors: Optional[dict] = None
+
+
+@dataclass
+class ScoreOutput:
+    """What `LMGen.score` returns for n sessions and T frames; site 0 is the text head, sites 1 .. dep_q the audio heads."""
+    logp: torch.Tensor                       # f32 [n, 1 + dep_q, T]: ln softmax(logits)[given token]; -inf outside the head's range
+    argmax: torch.Tensor                     # i64 [n, 1 + dep_q, T]: the lowest index among the largest logits
+    text_logits: Optional[torch.Tensor]      # f32 [n, T, text_card] with return_logits, else None
+    audio_logits: Optional[torch.Tensor]     # f32 [n, T, dep_q, card] with return_logits (None when dep_q == 0), else None
 
 
 @dataclass
@@ -1081,6 +1113,57 @@ class LMGen:
         if self.device.type == "cuda":       # the launches read `codes` / `forced`: keep them until they ran
             codes.record_stream(torch.cuda.current_stream(self.device))
             forced.record_stream(torch.cuda.current_stream(self.device))
+
+    @torch.no_grad()
+    def score(self, input_tokens: torch.Tensor, tokens: torch.Tensor, sessions: Optional[Sequence[int]] = None, commit: bool = True,
+              return_logits: bool = False) -> "ScoreOutput":
+        """Teacher-forced scoring of known frames (mmi_lm_score; needs `LMModel(prefill_rows=, score=True)`): the model's
+        distribution over tokens that are already known, the engine's counterpart of `LMModel.forward` (lm.py:322-377, 410-448) on a
+        live session.  `input_tokens` [n, n_q - dep_q, T] and `tokens` [n, 1 + dep_q, T] int64 are `prefill`'s arguments; for every
+        (session, site, frame) - site 0 the text head, then the `dep_q` audio heads - the result holds what the forced step of that
+        frame computes: `logp`, the natural log of softmax(logits)[given token] (-inf where the token lies outside the head's range),
+        `argmax`, and with `return_logits` the raw logits.  Sampling settings play no part.
+        `commit=True`: the sessions end exactly where `prefill` of the same arguments leaves them.  `commit=False`: nothing of the
+        streaming state changes (pure rescoring of candidates against a live session); n * T must fit one pass (`prefill_rows`).
+        Either way the other sessions and the stream's draw counter are untouched.  Stream ordered."""
+        if not self.is_streaming:
+            raise RuntimeError("You should wrap those calls with a `with lm_gen.streaming(): ...`.")
+        if not self.lm_model.score:
+            raise RuntimeError("score is not enabled: build the model with LMModel(..., prefill_rows=N, score=True)")
+        cfg = self.lm_model.config
+        needed = cfg.n_q - cfg.dep_q
+        sess = list(range(self._batch)) if sessions is None else [int(b) for b in sessions]
+        n = len(sess)
+        assert tokens.dim() == 3 and input_tokens.dim() == 3, "Shape should be [n, K, T]."
+        T = int(tokens.shape[2])
+        assert tokens.shape[0] == n and input_tokens.shape[0] == n, f"one row of frames per session: got {tokens.shape[0]} for {n}"
+        assert tokens.shape[1] == 1 + cfg.dep_q, f"tokens must be [n, {1 + cfg.dep_q}, T]"
+        assert input_tokens.shape[1] >= needed and input_tokens.shape[2] == T, f"We expect {needed} tokens from the user stream for each of the {T} frames."
+        codes = input_tokens[:, :needed].to(device=self.device, dtype=torch.int64).contiguous()
+        given = tokens.to(device=self.device, dtype=torch.int64).contiguous()
+        if self.check:
+            assert not (codes == self.lm_model.ungenerated_token_id).any(), codes
+            assert (codes <= self.lm_model.card).all(), codes
+            assert (given >= 0).all(), f"tokens must be >= 0: {given}"
+        sites = 1 + cfg.dep_q
+        logp = torch.empty(n, T, sites, dtype=torch.float32, device=self.device)
+        argmax = torch.empty(n, T, sites, dtype=torch.int32, device=self.device)
+        tl = al = None
+        if return_logits:
+            tl = torch.empty(n, T, cfg.text_card, dtype=torch.float32, device=self.device)
+            if cfg.dep_q:
+                al = torch.empty(n, T, cfg.dep_q, cfg.card, dtype=torch.float32, device=self.device)
+        out = _capi.ScoreOut(logp.data_ptr(), argmax.data_ptr(), tl.data_ptr() if tl is not None else None,
+                             al.data_ptr() if al is not None else None)
+        arr = (C.c_int32 * max(n, 1))(*sess)
+        self._lib.check(self._lib.mmi_lm_score(self.lm_model._handle, arr, n, codes.data_ptr() if needed else None, given.data_ptr(), T,
+                                               1 if commit else 0, C.byref(out), self._stream()))
+        if commit:
+            self._cond_keep = []
+        if self.device.type == "cuda":       # the launches read `codes` / `given`: keep them until they ran
+            codes.record_stream(torch.cuda.current_stream(self.device))
+            given.record_stream(torch.cuda.current_stream(self.device))
+        return ScoreOutput(logp.transpose(1, 2), argmax.transpose(1, 2).to(torch.int64), tl, al)
 
     def last_tokens(self) -> torch.Tensor:
         """[B, 1 + dep_q] int64: the tokens the last step (or prefill) stored for every session, in step coordinates - one frame of

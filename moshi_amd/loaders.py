@@ -153,14 +153,15 @@ def get_moshi_lm(filename: str | Path | None, lm_kwargs: Optional[Dict[str, Any]
                  dtype: torch.dtype = torch.bfloat16, lora_weights: str | Path | None = None, fuse_lora: bool = False,
                  lm_kwargs_overrides: Optional[dict] = None, max_batch: int = 32, lib=None, state_patch=None,
                  quantize: Optional[bool | str] = None, max_rows: Optional[int] = None, adapters=None,
-                 kv_cache: Optional[str] = None, prefill_rows: Optional[int] = None) -> LMModel:
+                 kv_cache: Optional[str] = None, prefill_rows: Optional[int] = None, score: bool = False) -> LMModel:
     """loaders.get_moshi_lm (loaders.py:366-446): bf16 weights; `quantize` in the config (a `.q8` checkpoint carrying int8
     `weight` + `weight_scb`, fp8 `weight` + `weight_scale`, or MXFP4 `weight` + `weight_scale_e8m0`) is taken from the tensors
     themselves; `quantize="mxfp4"` converts a bf16 checkpoint at load.  `max_rows`: a handle of
     up to 128 model rows instead of `max_batch` sessions (LMModel).  `adapters=(max_adapters, max_rank)`: room for LoRA adapters
     next to the base, chosen per session (`load_lora_adapter`); `lora_weights=` keeps merging one adapter at load.
     `kv_cache`: "fp8" / "fp4" ring for the temporal keys and values (LMModel), default the config's (bf16).
-    `prefill_rows`: the row budget of one pass of `LMGen.prefill` (LMModel), default off."""
+    `prefill_rows`: the row budget of one pass of `LMGen.prefill` (LMModel), default off.
+    `score`: with `prefill_rows`, enables `LMGen.score` (teacher-forced scoring of known frames; LMModel), default off."""
     assert dtype == torch.bfloat16, "the engine computes the LM in bf16 (fp32 accumulation), like the reference's default"
     kw = dict(lm_kwargs) if lm_kwargs is not None else None
     if kw is not None:
@@ -203,7 +204,7 @@ def get_moshi_lm(filename: str | Path | None, lm_kwargs: Optional[Dict[str, Any]
     from .weights import is_mxfp4_state_dict
     already = any(v.dtype in (torch.int8, torch.float8_e4m3fn) for v in state.values()) or is_mxfp4_state_dict(state)
     lm = LMModel(state, cfg, device=device, max_batch=max_batch, lib=lib, quantize=False if already else quantize, fuser=fuser,
-                 max_rows=max_rows, adapters=adapters, kv_cache=kv_cache, prefill_rows=prefill_rows)
+                 max_rows=max_rows, adapters=adapters, kv_cache=kv_cache, prefill_rows=prefill_rows, score=score)
     lm.lora_scaling = cfg_lora_scaling                  # the config's `lora_scaling`: load_lora_adapter's default
     return lm
 

@@ -23,6 +23,11 @@
 // frame, and on a 128-row handle whose 66 sessions make every pass a k_gemm_rows launch - then the remaining frames are stepped
 // against the oracle's record; the entry points' refusals must hold.
 //
+// `native_selftest <dir> --score`: teacher-forced scoring through the C ABI alone (mmi_lm_enable_score / mmi_lm_score): the
+// first recorded forced frames go through mmi_lm_score with commit = 1 - in one pass and in passes of one frame - the returned logits
+// against the recorded step logits, logp against the double-precision value from the returned logits; the remaining frames are then
+// stepped against the record; the entry points' refusals must hold.
+//
 // The same source builds against the CPU simulator (-DMMI_SELFTEST_SIM, tests/test_native_selftest.py), which is how the expected
 // values and this program are checked where there is no GPU.  The checker side (oracle) never runs here: only its recorded output.
 //
@@ -36,7 +41,7 @@
 //   export MMI_NO_GRAPH=1 ASAN_OPTIONS=detect_leaks=0:detect_stack_use_after_return=0 UBSAN_OPTIONS=print_stacktrace=1
 //   build/native_selftest_san tests/golden/native_selftest && build/native_selftest_san tests/golden/native_selftest --rows 65,128 &&
 //   build/native_selftest_san tests/golden/native_selftest --adapters && build/native_selftest_san tests/golden/native_selftest --nucleus &&
-//   build/native_selftest_san tests/golden/native_selftest --prefill
+//   build/native_selftest_san tests/golden/native_selftest --prefill && build/native_selftest_san tests/golden/native_selftest --score
 #include "moshi_mi.h"
 #ifdef MMI_SELFTEST_SIM
 #include "hipsim.h"
@@ -82,6 +87,8 @@ int main(int argc, char** argv) {
     for (int i = 1; i < argc; ++i) nucleus |= !strcmp(argv[i], "--nucleus");
     bool prefill = false;
     for (int i = 1; i < argc; ++i) prefill |= !strcmp(argv[i], "--prefill");
+    bool score = false;
+    for (int i = 1; i < argc; ++i) score |= !strcmp(argv[i], "--score");
     FILE* mf = fopen((dir + "/manifest.txt").c_str(), "r");
     if (!mf) { printf("cannot open %s/manifest.txt\n", dir.c_str()); return 2; }
     mmi_mimi_cfg mc; mmi_lm_cfg lc;
@@ -153,7 +160,7 @@ int main(int argc, char** argv) {
     int failures = 0;
 
     // ---- Mimi: encode FR frames, decode the oracle's codes
-    if (many_rows.empty() && !adapters && !nucleus && !prefill) {
+    if (many_rows.empty() && !adapters && !nucleus && !prefill && !score) {
         mmi_mimi* m = nullptr;
         MCK(mmi_mimi_create(&mc, md.data(), (int32_t)md.size(), B, &m));
         MCK(mmi_mimi_set_num_codebooks(m, K));
@@ -192,7 +199,7 @@ int main(int argc, char** argv) {
         mmi_mimi_destroy(m);
     }
     // ---- LM: greedy steps, teacher-forced with the oracle's tokens
-    if (many_rows.empty() && !adapters && !nucleus && !prefill) {
+    if (many_rows.empty() && !adapters && !nucleus && !prefill && !score) {
         mmi_lm* lm = nullptr;
         MCK(mmi_lm_create(&lc, ld.data(), (int32_t)ld.size(), B, &lm));
         mmi_sampling sp; memset(&sp, 0, sizeof(sp));
@@ -582,6 +589,138 @@ int main(int argc, char** argv) {
             hipFree(duc); hipFree(dforced); hipFree(dout); hipFree(dlast); hipFree(dpu); hipFree(dpt); hipFree(dtl); hipFree(dal);
         }
         printf("lm prefill: %d of %d refusal checks held\n", held, checks);
+        failures += held != checks;
+    }
+    if (score) {
+        // The fixture's sessions take the first `cut` recorded frames through mmi_lm_score (commit = 1) under a row budget `rows`: its logits
+        // against the step logits the oracle recorded for those frames, logp against the double-precision log-softmax of the returned
+        // logits, argmax against theirs; then the frames cut .. ST - 1 by forced steps against the record, as after a prefill
+        const int NT = dep_q + 1, cut = ST / 2;
+        const int64_t* eforced = (const int64_t*)expect("lm_forced");
+        const int64_t* eout = (const int64_t*)expect("lm_out");
+        const float* etl = (const float*)expect("lm_text_logits");
+        const float* eal = (const float*)expect("lm_audio_logits");
+        mmi_sampling sp; memset(&sp, 0, sizeof(sp));
+        sp.use_sampling = 0; sp.temp = 0.8f; sp.temp_text = 0.7f; sp.top_k = 250; sp.top_k_text = 25; sp.seed = 0;
+        int held = 0, checks = 0;
+        auto holds = [&](int rc, int want) { ++checks; held += rc == want; if (rc != want) printf("  refusal check %d: status %d, expected %d\n", checks, rc, want); };
+        for (int run = 0; run < 2; ++run) {
+            const int R = B, rows = run ? B : (B * cut <= 32 ? B * cut : 2 * B);      // all scored frames in one pass; passes of one frame
+            mmi_lm* lm = nullptr;
+            MCK(mmi_lm_create(&lc, ld.data(), (int32_t)ld.size(), B, &lm));
+            int64_t *duc, *dforced, *dout, *dpu, *dpt; float *dtl, *dal, *dlogp, *dstl, *dsal; int32_t* dam;
+            HCK(hipMalloc((void**)&duc, (size_t)R * n_user * 8)); HCK(hipMalloc((void**)&dforced, (size_t)R * NT * 8));
+            HCK(hipMalloc((void**)&dout, (size_t)R * NT * 8));
+            HCK(hipMalloc((void**)&dpu, (size_t)R * n_user * cut * 8)); HCK(hipMalloc((void**)&dpt, (size_t)R * NT * cut * 8));
+            HCK(hipMalloc((void**)&dtl, (size_t)R * text_card * 4)); HCK(hipMalloc((void**)&dal, (size_t)R * dep_q * card * 4));
+            HCK(hipMalloc((void**)&dlogp, (size_t)R * cut * NT * 4)); HCK(hipMalloc((void**)&dam, (size_t)R * cut * NT * 4));
+            HCK(hipMalloc((void**)&dstl, (size_t)R * cut * text_card * 4)); HCK(hipMalloc((void**)&dsal, (size_t)R * cut * dep_q * card * 4));
+            std::vector<int32_t> sess(R);
+            for (int r = 0; r < R; ++r) sess[r] = r;
+            mmi_score_out so; so.logp = dlogp; so.argmax = dam; so.text_logits = dstl; so.audio_logits = dsal;
+            const bool first = run == 0;
+            if (first) {
+                holds(mmi_lm_score_enabled(lm), 0);
+                holds(mmi_lm_enable_score(lm, 1), MMI_ERR_STATE);                      // prefill is not enabled
+                MCK(mmi_lm_enable_prefill(lm, rows));
+                MCK(mmi_lm_streaming_start(lm, R, &sp, nullptr));
+                holds(mmi_lm_score(lm, sess.data(), R, dpu, dpt, cut, 1, &so, nullptr), MMI_ERR_STATE);     // scoring is not enabled
+                holds(mmi_lm_enable_score(lm, 1), MMI_ERR_STATE);                      // while streaming
+                MCK(mmi_lm_streaming_stop(lm));
+            }
+            MCK(mmi_lm_enable_prefill(lm, rows));
+            MCK(mmi_lm_enable_score(lm, 1));
+            MCK(mmi_lm_streaming_start(lm, R, &sp, nullptr));
+            const int64_t bytes_with = mmi_lm_state_bytes(lm);
+            std::vector<int64_t> pu((size_t)R * n_user * cut), pt((size_t)R * NT * cut);
+            for (int f = 0; f < cut; ++f) {
+                std::vector<int64_t> uc1((size_t)B * n_user);
+                for (size_t i = 0; i < uc1.size(); ++i) uc1[i] = (int64_t)((u_of(9000u + f, (uint32_t)i) + 1.0f) * 32768.0f) % card;
+                for (int r = 0; r < R; ++r) {
+                    for (int c = 0; c < n_user; ++c) pu[((size_t)r * n_user + c) * cut + f] = uc1[(size_t)r * n_user + c];
+                    for (int c = 0; c < NT; ++c) pt[((size_t)r * NT + c) * cut + f] = eforced[((size_t)f * B + r) * NT + c];
+                }
+            }
+            HCK(hipMemcpy(dpu, pu.data(), pu.size() * 8, hipMemcpyHostToDevice));
+            HCK(hipMemcpy(dpt, pt.data(), pt.size() * 8, hipMemcpyHostToDevice));
+            if (first) {
+                mmi_score_out bad = so; bad.logp = nullptr;
+                holds(mmi_lm_score(lm, sess.data(), R, dpu, dpt, cut, 1, &bad, nullptr), MMI_ERR_INVALID);          // a null logp
+                holds(mmi_lm_score(lm, sess.data(), R, dpu, dpt, cut, 1, nullptr, nullptr), MMI_ERR_INVALID);
+                holds(mmi_lm_score(lm, sess.data(), R, dpu, dpt, 0, 1, &so, nullptr), MMI_ERR_INVALID);
+                holds(mmi_lm_score(lm, sess.data(), R, dpu, dpt, rows / R + 1, 0, &so, nullptr), MMI_ERR_INVALID);   // commit = 0 beyond one pass
+                std::vector<int32_t> twice(R, 0);
+                holds(R > 1 ? mmi_lm_score(lm, twice.data(), R, dpu, dpt, cut, 1, &so, nullptr) : MMI_ERR_INVALID, MMI_ERR_INVALID);
+            }
+            MCK(mmi_lm_score(lm, sess.data(), R, dpu, dpt, cut, 1, &so, nullptr));
+            HCK(hipDeviceSynchronize());
+            std::vector<float> lp((size_t)R * cut * NT), stl((size_t)R * cut * text_card), sal((size_t)R * cut * dep_q * card);
+            std::vector<int32_t> am((size_t)R * cut * NT);
+            HCK(hipMemcpy(lp.data(), dlogp, lp.size() * 4, hipMemcpyDeviceToHost));
+            HCK(hipMemcpy(am.data(), dam, am.size() * 4, hipMemcpyDeviceToHost));
+            HCK(hipMemcpy(stl.data(), dstl, stl.size() * 4, hipMemcpyDeviceToHost));
+            if (dep_q) HCK(hipMemcpy(sal.data(), dsal, sal.size() * 4, hipMemcpyDeviceToHost));
+            long tok_diffs = 0, am_diffs = 0; double worst_max = 0, worst_mean = 0, worst_logp = 0;
+            auto site = [&](const float* a, const float* r, int n) {
+                double mx = 1e-6, dmax = 0, dsum = 0;
+                for (int i = 0; i < n; ++i) { mx = fmax(mx, fabs(r[i])); const double d = fabs(a[i] - r[i]); dmax = fmax(dmax, d); dsum += d; }
+                worst_max = fmax(worst_max, dmax / mx); worst_mean = fmax(worst_mean, dsum / n / mx);
+            };
+            // logp and argmax of one site against the double-precision values from the returned row
+            auto own = [&](const float* row, int n, int64_t tok, float got_lp, int got_am) {
+                double mx = -INFINITY, sum = 0; int best = 0;
+                for (int i = 0; i < n; ++i) if ((double)row[i] > mx) { mx = row[i]; best = i; }
+                for (int i = 0; i < n; ++i) sum += exp((double)row[i] - mx);
+                am_diffs += best != got_am;
+                if (tok >= 0 && tok < n) worst_logp = fmax(worst_logp, fabs((double)got_lp - (((double)row[tok] - mx) - log(sum))));
+                else worst_logp = fmax(worst_logp, got_lp == -INFINITY ? 0.0 : 1.0);
+            };
+            for (int r = 0; r < R; ++r)
+                for (int f = 0; f < cut; ++f) {
+                    const size_t rf = (size_t)r * cut + f;
+                    site(stl.data() + rf * text_card, etl + ((size_t)f * B + r) * text_card, text_card);
+                    own(stl.data() + rf * text_card, text_card, eforced[((size_t)f * B + r) * NT], lp[rf * NT], am[rf * NT]);
+                    for (int k = 0; k < dep_q; ++k) {
+                        site(sal.data() + (rf * dep_q + k) * card, eal + (((size_t)f * B + r) * dep_q + k) * card, card);
+                        own(sal.data() + (rf * dep_q + k) * card, card, eforced[((size_t)f * B + r) * NT + 1 + k], lp[rf * NT + 1 + k], am[rf * NT + 1 + k]);
+                    }
+                }
+            for (int s = cut; s < ST; ++s) {
+                std::vector<int64_t> uc((size_t)R * n_user);
+                for (size_t i = 0; i < uc.size(); ++i) uc[i] = (int64_t)((u_of(9000u + s, (uint32_t)i) + 1.0f) * 32768.0f) % card;
+                HCK(hipMemcpy(duc, uc.data(), uc.size() * 8, hipMemcpyHostToDevice));
+                HCK(hipMemcpy(dforced, eforced + (size_t)s * B * NT, (size_t)B * NT * 8, hipMemcpyHostToDevice));
+                MCK(mmi_lm_force_next_tokens(lm, dforced, nullptr));
+                int32_t valid = 0;
+                MCK(mmi_lm_step(lm, duc, n_user, dout, dtl, dal, nullptr, R, &valid, nullptr));
+                HCK(hipDeviceSynchronize());
+                std::vector<int64_t> o((size_t)R * NT); std::vector<float> tl((size_t)R * text_card), al((size_t)R * dep_q * card);
+                HCK(hipMemcpy(o.data(), dout, o.size() * 8, hipMemcpyDeviceToHost));
+                HCK(hipMemcpy(tl.data(), dtl, tl.size() * 4, hipMemcpyDeviceToHost));
+                if (dep_q) HCK(hipMemcpy(al.data(), dal, al.size() * 4, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < o.size(); ++i) tok_diffs += o[i] != eout[(size_t)s * B * NT + i];
+                for (int b = 0; b < B; ++b) {
+                    site(tl.data() + (size_t)b * text_card, etl + ((size_t)s * B + b) * text_card, text_card);
+                    for (int k = 0; k < dep_q; ++k) site(al.data() + ((size_t)b * dep_q + k) * card, eal + (((size_t)s * B + b) * dep_q + k) * card, card);
+                }
+            }
+            MCK(mmi_lm_streaming_stop(lm));
+            MCK(mmi_lm_enable_score(lm, 0));
+            MCK(mmi_lm_streaming_start(lm, R, &sp, nullptr));
+            const int64_t bytes_without = mmi_lm_state_bytes(lm);
+            MCK(mmi_lm_streaming_stop(lm));
+            printf("lm score, %d sessions, %d rows per pass: %d frames scored; logits of the scored frames and of the next %d steps worst max %.4f "
+                   "(<= 0.05), worst mean %.4f (<= 0.012) of max|logit|; logp worst %.3g from its own logits (<= 2^-13); argmax differs in %ld sites "
+                   "(must be 0); %ld of %d token-ring outputs of the next steps differ from the oracle (must be 0); state bytes %lld with, %lld without "
+                   "(must be equal)\n", R, rows, cut, ST - cut, worst_max, worst_mean, worst_logp, am_diffs, tok_diffs, (ST - cut) * R * NT,
+                   (long long)bytes_with, (long long)bytes_without);
+            failures += tok_diffs != 0 || am_diffs != 0 || !(worst_max <= 0.05) || !(worst_mean <= 0.012) || !(worst_logp <= 1.0 / 8192) ||
+                        bytes_with != bytes_without || cut < 1;
+            mmi_lm_destroy(lm);
+            hipFree(duc); hipFree(dforced); hipFree(dout); hipFree(dpu); hipFree(dpt); hipFree(dtl); hipFree(dal);
+            hipFree(dlogp); hipFree(dam); hipFree(dstl); hipFree(dsal);
+        }
+        printf("lm score: %d of %d refusal checks held\n", held, checks);
         failures += held != checks;
     }
     printf(failures ? "SELFTEST FAILED\n" : "SELFTEST PASSED\n");
