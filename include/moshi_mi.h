@@ -637,6 +637,46 @@ int mmi_lm_debug_attn(mmi_lm* lm, const void* q_bf16, const void* k_ring, const 
                       int32_t H, int32_t Dh, int32_t cap, int32_t context, int32_t kv_dtype, int32_t kernel, int32_t NS, int32_t merge,
                       int32_t solo_rows, void* out_bf16, mmi_stream stream);
 
+/* Parity taps of the depth transformer's attention and of the cross attention (tests; no reference counterpart):
+ * the launch functions of the step - launch_dep_attn, which the scoring pass calls too, and launch_cross_attn - on caller-supplied
+ * operands.  They work on any handle, touch no stream state and read nothing of the handle but its device, its row limit and its
+ * poison knob; the packed output lives in scratch of the call and is returned row-major.  All synchronise `stream`.
+ *
+ * mmi_lm_debug_dep_attn: micro-step k of a frame, for `rows` rows (model rows of a step, or the rows of a scoring pass).
+ *   qkv       device bf16 [rows][3 * H * Dh]: the in_proj output (q, then k, then v); 16-byte aligned
+ *   k_cache, v_cache   device bf16 [rows][H][steps][Dh], read (positions < k) and written (position k) in place; 16-byte aligned
+ *   kernel    MMI_DEP_ATTN_AUTO = the step's own choice; or MMI_DEP_ATTN_8 (k_dep_attn8<4>), MMI_DEP_ATTN_ROWS16 (k_dep_attn<16>),
+ *             MMI_DEP_ATTN_ROWS32 (k_dep_attn<32>) forced
+ *   out       device bf16 [rows][H * Dh];  kernel_run (host, may be NULL): the kernel that was launched
+ * Refuses: a null pointer, an unknown kernel (MMI_ERR_INVALID); Dh outside 1..64 (MMI_ERR_UNSUPPORTED); steps outside 1..32, k
+ * outside [0, steps), H outside 1..1024, rows outside 1..max(128, the handle's max_batch) (MMI_ERR_SHAPE); a forced kernel that does
+ * not admit the shape - MMI_DEP_ATTN_8 needs Dh % 8 == 0 and steps <= 8, MMI_DEP_ATTN_ROWS16 steps <= 16 - and misaligned operands
+ * (MMI_ERR_UNSUPPORTED).
+ *
+ * mmi_lm_debug_dep_attn_out_proj: x + out_proj(attention) of ONE row with the packed out_proj weight of the handle's own depth layer
+ * `layer`, micro-step k in [1, dep_q); H, Dh and steps are the handle's (depformer_num_heads, depformer_dim / heads, dep_q).
+ *   qkv [3 * dd], k_cache / v_cache [H][dep_q][Dh] (in place), x [dd] the residual row, out [dd]: device bf16, dd = depformer_dim
+ *   fused     != 0: k_dep_attn_out_proj with the step's plan; 0: the two launches it replaces - launch_dep_attn, then the out_proj
+ *             GEMM through the step's launch_gemm - and att (device bf16 [dd], may be NULL) also receives the attention output
+ *   kernel_run (host, may be NULL): MMI_DEP_ATTN_FUSED, or the attention kernel of the two-launch form
+ * Refused (MMI_ERR_UNSUPPORTED) where the step would not run this out_proj with the attention inside (more than one row is not
+ * offered; int8 / fp8 / MXFP4 weights, an adapter handle, MMI_NO_DEP_ATTN_FUSION, head dims and steps k_dep_attn8 does not take,
+ * a K split that is no whole heads).
+ *
+ * mmi_lm_debug_cross_attn: k_lm_cross_attn.
+ *   q         device bf16 [rows][H * Dh];  kv device bf16 [rows][cap][2 * H * Dh] (keys, then values); both 16-byte aligned
+ *   len       device int32 [rows]: live positions per row; every len in [1, cap] (checked on the host: MMI_ERR_INVALID)
+ *   Dh        32, 64 or 128;  rows 1..max(128, the handle's max_batch);  cap 1..2^20
+ *   out       device bf16 [rows][H * Dh] */
+enum { MMI_DEP_ATTN_AUTO = 0, MMI_DEP_ATTN_8 = 1, MMI_DEP_ATTN_ROWS16 = 2, MMI_DEP_ATTN_ROWS32 = 3, MMI_DEP_ATTN_FUSED = 4 };
+int mmi_lm_debug_dep_attn(mmi_lm* lm, const void* qkv_bf16, void* k_cache, void* v_cache, int32_t rows, int32_t H, int32_t Dh,
+                          int32_t steps, int32_t k, int32_t kernel, void* out_bf16, int32_t* kernel_run, mmi_stream stream);
+int mmi_lm_debug_dep_attn_out_proj(mmi_lm* lm, int32_t layer, int32_t k, int32_t fused, const void* qkv_bf16, void* k_cache,
+                                   void* v_cache, const void* x_bf16, void* out_bf16, void* att_bf16, int32_t* kernel_run,
+                                   mmi_stream stream);
+int mmi_lm_debug_cross_attn(mmi_lm* lm, const void* q_bf16, const void* kv_bf16, const int32_t* len, int32_t rows, int32_t H,
+                            int32_t Dh, int32_t cap, void* out_bf16, mmi_stream stream);
+
 /* ---- chunked prefill of known frames into a live session (no reference counterpart) ----------------------------
  * mmi_lm_prefill on sessions S with T frames equals T calls of mmi_lm_step under an exec mask that holds exactly the sessions of S,
  * each preceded by mmi_lm_force_next_tokens with every entry of those sessions' rows >= 0, the previous exec mask restored

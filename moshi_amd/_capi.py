@@ -213,6 +213,10 @@ SIGNATURES = {
     "mmi_lm_debug_kv_ring": (C.c_int64, [_P, C.c_int32, C.c_int32, _P, C.c_int64, _P]),
     "mmi_lm_debug_attn": (C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_int32, _P, _P]),
+    "mmi_lm_debug_dep_attn": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
+                                        C.POINTER(C.c_int32), _P]),
+    "mmi_lm_debug_dep_attn_out_proj": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int32), _P]),
+    "mmi_lm_debug_cross_attn": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "mmi_lm_enable_adapters": (C.c_int, [_P, C.c_int32, C.c_int32]),
     "mmi_lm_load_adapter": (C.c_int, [_P, C.c_int32, C.c_float, C.POINTER(TensorDesc), C.c_int32, _P]),
     "mmi_lm_unload_adapter": (C.c_int, [_P, C.c_int32, _P]),
@@ -257,7 +261,7 @@ _SINCE_ADAPTERS = ("mmi_lm_debug_linear_lora", "mmi_lm_enable_adapters", "mmi_lm
 _SINCE_NUCLEUS = ("mmi_lm_enable_nucleus", "mmi_lm_set_top_p", "mmi_lm_top_p", "mmi_lm_nucleus_enabled", "mmi_lm_set_row_top_p",
                   "mmi_lm_clear_row_top_p", "mmi_batcher_set_channel_top_p")
 _SINCE_KV4 = ("mmi_lm_debug_kv4_quantize", "mmi_lm_debug_kv_ring")
-_SINCE_ATTN_TAP = ("mmi_lm_debug_attn",)
+_SINCE_ATTN_TAP = ("mmi_lm_debug_attn", "mmi_lm_debug_dep_attn", "mmi_lm_debug_dep_attn_out_proj", "mmi_lm_debug_cross_attn")
 _SINCE_PREFILL = ("mmi_lm_enable_prefill", "mmi_lm_prefill_rows", "mmi_lm_prefill", "mmi_lm_last_tokens", "mmi_lm_debug_prefill_attn",
                   "mmi_lm_debug_state_regions")
 _SINCE_SCORE = ("mmi_lm_enable_score", "mmi_lm_score_enabled", "mmi_lm_score", "mmi_lm_debug_score_rows")

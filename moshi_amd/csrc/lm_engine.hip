@@ -819,12 +819,38 @@ void add_gemm(mmi_lm* lm, const GemmW& g, const uint16_t* x, uint16_t* out, int 
     lm->prog.add([lm, gw, a, dominant, lt](hipStream_t s) { return launch_gemm(lm, s, gw, a, dominant, lt); }, (long)g.bytes);
 }
 
+// The depth transformer's attention launch - the step's dep.attn op, the scoring pass and mmi_lm_debug_dep_attn: THE selection
+// between the three kernels.  k_dep_attn8: a head dim that is a multiple of 8 and at most 8 positions per frame (Moshi); else the
+// general one-wave-per-(row, head) kernel with 16 cache rows in registers, 32 for the TTS family's 17..32 micro-steps.
+int dep_attn_kernel(int Dh, int steps) {
+    if (Dh % 8 == 0 && steps <= 8) return MMI_DEP_ATTN_8;
+    return steps > 16 ? MMI_DEP_ATTN_ROWS32 : MMI_DEP_ATTN_ROWS16;
+}
+// force: MMI_DEP_ATTN_AUTO, or (the tap alone) a kernel that admits the shape; ran: the kernel launched, when asked for
+int launch_dep_attn(hipStream_t s, const DepAttnArgs& da, int force = MMI_DEP_ATTN_AUTO, int* ran = nullptr) {
+    const int kernel = force == MMI_DEP_ATTN_AUTO ? dep_attn_kernel(da.Dh, da.steps) : force;
+    if (kernel == MMI_DEP_ATTN_8) MMI_LAUNCH((k_dep_attn8<4>), mmi_cdiv(da.B * da.H, 4), 256, 0, s, da);
+    else if (kernel == MMI_DEP_ATTN_ROWS32) MMI_LAUNCH((k_dep_attn<32>), da.B * da.H, 64, 0, s, da);
+    else MMI_LAUNCH((k_dep_attn<16>), da.B * da.H, 64, 0, s, da);
+    MMI_CHECK_LAUNCH();
+    if (ran) *ran = kernel;
+    return MMI_OK;
+}
+
+// The L.cross_attn op (and mmi_lm_debug_cross_attn)
+int launch_cross_attn(hipStream_t s, const CrossAttnArgs& ca) {
+    MMI_LAUNCH(k_lm_cross_attn, ca.B * ca.H, 64, 0, s, ca);
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+
 // The depth transformer's attention inside its out_proj (k_dep_attn_out_proj): ONE session at the 16-row tile (the real-time
 // configuration), bf16 weights, a wave's K-slice = one or two whole heads.  Same-box at 1 / 2 / 4 sessions: -0.06 / +0.04 / +0.27 ms
 // per step (a wave works through its 2 B pairs one after the other; profiles/r04_logs/call_o2_summary.txt), hence one session only.
-// knobs.no_dep_attn_fusion: the two launches (A/B and the bit-equality test)
-bool dep_attn_fusable(const mmi_lm* lm, const GemmW& g, int H, int Dh, int steps) {
-    if (g.T != 16 || lm->batch != 1 || lm->act8 || g.wq != 0 || lm->knobs.no_dep_attn_fusion || lm->lora_on) return false;
+// knobs.no_dep_attn_fusion: the two launches (A/B and the bit-equality test).  A function of the weight, the shape and the rows
+// (the step: its streaming batch; mmi_lm_debug_dep_attn_out_proj: 1) - nothing of a running stream.
+bool dep_attn_fusable(const mmi_lm* lm, const GemmW& g, int H, int Dh, int steps, int rows) {
+    if (g.T != 16 || rows != 1 || lm->act8 || g.wq != 0 || lm->knobs.no_dep_attn_fusion || lm->lora_on) return false;
     if (Dh % 8 || Dh > 64 || steps > 8 || g.KSTEPS * 32 != H * Dh) return false;
     const GemmPlan p = plan_gemm(lm->knobs, g, false);
     const int kper = mmi_cdiv(g.KSTEPS, p.waves);
@@ -839,19 +865,30 @@ int launch_dep_attn_out_proj(hipStream_t s, int groups, const GemmArgs& a, const
 }
 
 // x += out_proj(attention(qkv, frame cache)) (dep_attn_fusable)
-void add_dep_attn_out_proj(mmi_lm* lm, const GemmW& g, const DepAttnArgs& da, uint16_t* x, int features) {
-    GemmArgs a;
+// the fused launch with its plan (the step's op and mmi_lm_debug_dep_attn_out_proj): B = tok_rows = 1 (dep_attn_fusable)
+struct DepAttnOutProj { GemmArgs a; int groups, waves; };
+DepAttnOutProj plan_dep_attn_out_proj(const mmi_lm* lm, const GemmW& g, uint16_t* x, int features, int B, int tok_rows) {
+    DepAttnOutProj f;
+    GemmArgs& a = f.a;
     memset(&a, 0, sizeof(a));
-    a.out = x; a.epi = MMI_EPI_RESID; a.resid = x; a.B = lm->batch; a.tok_rows = lm->gen_batch;
+    a.out = x; a.epi = MMI_EPI_RESID; a.resid = x; a.B = B; a.tok_rows = tok_rows;
     a.out_mode = MMI_OUT_PACKED; a.out_ld = features; a.out_ksteps = packed_ksteps_t(lm, g.T, features);
     a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT; a.wscale = g.scale; a.xinv = g.xinv;
     const GemmPlan p = plan_gemm(lm->knobs, g, false);
     a.osplit = plan_osplit(lm->knobs, g, p, a.epi, g.T);
-    const int groups = g.NT * (a.osplit > 1 ? a.osplit : 1), waves = p.waves;
+    f.groups = g.NT * (a.osplit > 1 ? a.osplit : 1);
+    f.waves = p.waves;
+    return f;
+}
+int launch_dep_attn_out_proj_planned(hipStream_t s, const DepAttnOutProj& f, const DepAttnArgs& da) {
+    return f.waves == 8 ? launch_dep_attn_out_proj<8>(s, f.groups, f.a, da) : launch_dep_attn_out_proj<4>(s, f.groups, f.a, da);
+}
+void add_dep_attn_out_proj(mmi_lm* lm, const GemmW& g, const DepAttnArgs& da, uint16_t* x, int features) {
+    const DepAttnOutProj f = plan_dep_attn_out_proj(lm, g, x, features, lm->batch, lm->gen_batch);
     const long bytes = (long)g.bytes;
     lm->prog.add([=](hipStream_t s) {
         mmi_record_bytes(bytes);
-        return waves == 8 ? launch_dep_attn_out_proj<8>(s, groups, a, da) : launch_dep_attn_out_proj<4>(s, groups, a, da);
+        return launch_dep_attn_out_proj_planned(s, f, da);
     }, bytes);
 }
 
@@ -1349,11 +1386,7 @@ int build_program(mmi_lm* lm) {
                 CrossAttnArgs ca;
                 ca.q = lm->qrot; ca.kv = lm->xkv + (size_t)l * B * lm->cross_cap * 2 * d; ca.out = lm->att;
                 ca.len = lm->xlen; ca.B = B; ca.H = H; ca.Dh = Dh; ca.cap = lm->cross_cap; ca.T = lm->T; ca.out_ksteps = packed_ksteps(lm, d);
-                P.add([=](hipStream_t s) {
-                    MMI_LAUNCH(k_lm_cross_attn, B * H, 64, 0, s, ca);
-                    MMI_CHECK_LAUNCH();
-                    return (int)MMI_OK;
-                });
+                P.add([=](hipStream_t s) { return launch_cross_attn(s, ca); });
             }
             P.site("L.cross_out");
             pending = add_gemm_resid(lm, L.x_out, lm->att, lm->x, d);
@@ -1463,17 +1496,9 @@ int build_program(mmi_lm* lm) {
             da.B = B; da.H = Hd; da.Dh = Dhd; da.steps = c.dep_q; da.k = k;
             da.T = lm->Td; da.out_ksteps = packed_ksteps_t(lm, lm->Td, dd);
             P.site("dep.attn");
-            const bool attn8 = Dhd % 8 == 0 && c.dep_q <= 8;        // else the general one-wave-per-(session, head) kernel
-            const bool rows32 = c.dep_q > 16;                        // its 32-row form: the TTS family's 17..32 micro-steps
-            const bool attn_in_gemm = !skip_attn0 && attn8 && dep_attn_fusable(lm, L.out_proj[k], Hd, Dhd, c.dep_q);
+            const bool attn_in_gemm = !skip_attn0 && dep_attn_fusable(lm, L.out_proj[k], Hd, Dhd, c.dep_q, lm->batch);
             if (!skip_attn0 && !attn_in_gemm)
-            P.add([=](hipStream_t s) {
-                if (attn8) MMI_LAUNCH((k_dep_attn8<4>), mmi_cdiv(B * Hd, 4), 256, 0, s, da);
-                else if (rows32) MMI_LAUNCH((k_dep_attn<32>), B * Hd, 64, 0, s, da);
-                else MMI_LAUNCH((k_dep_attn<16>), B * Hd, 64, 0, s, da);
-                MMI_CHECK_LAUNCH();
-                return (int)MMI_OK;
-            });
+            P.add([=](hipStream_t s) { return launch_dep_attn(s, da); });
             // int8 activations: the chain's linears quantise their own input row inside the GEMM (k_gemm_q8)
             P.site("dep.out_proj");
             if (attn_in_gemm) add_dep_attn_out_proj(lm, L.out_proj[k], da, lm->dx, dd);
@@ -2113,10 +2138,7 @@ static int score_heads(mmi_lm* lm, hipStream_t s, const PfArgs& p, const int64_t
             da.qkv = S.dqkv; da.kc = S.dkc + l * dkv_layer; da.vc = S.dvc + l * dkv_layer; da.out = S.datt;
             da.B = R; da.H = Hd; da.Dh = Dhd; da.steps = q; da.k = k;
             da.T = lm->Td; da.out_ksteps = dks;
-            if (Dhd % 8 == 0 && q <= 8) MMI_LAUNCH((k_dep_attn8<4>), mmi_cdiv(R * Hd, 4), 256, 0, s, da);
-            else if (q > 16) MMI_LAUNCH((k_dep_attn<32>), R * Hd, 64, 0, s, da);
-            else MMI_LAUNCH((k_dep_attn<16>), R * Hd, 64, 0, s, da);
-            MMI_CHECK_LAUNCH();
+            if ((rc = launch_dep_attn(s, da))) return rc;
             if ((rc = pf_gemm(lm, s, L.out_proj[k], R, S.datt, S.dx, dd, true, MMI_EPI_RESID, S.dx))) return rc;
             if ((rc = sc_dep_norm(lm, s, R, L.n2))) return rc;
             if ((rc = pf_gemm(lm, s, L.ffn_in[k], R, S.dxn, S.dhb, c.depformer_ffn_hidden, true, MMI_EPI_GATE, nullptr))) return rc;
@@ -3732,6 +3754,146 @@ extern "C" int mmi_lm_debug_attn(mmi_lm* lm, const void* q_bf16, const void* k_r
     MMI_LAUNCH(k_unpack_rows, mmi_cdiv(rows * d, 256), 256, 0, s, (const uint16_t*)att, rows, d, (uint16_t*)out_bf16, T, ksteps);
     MMI_DBG_LAUNCHED();
     if (hipStreamSynchronize(s) != hipSuccess) { A.release(); return mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_attn: the launches failed"); }
+    A.release();
+    return MMI_OK;
+}
+
+// Parity tap of the depth transformer's attention (include/moshi_mi.h): launch_dep_attn - the step's dep.attn op and the scoring
+// pass's - on caller-supplied operands, with a packed output of its own.  Nothing of the handle but its device, its row limit and its
+// poison knob is read.
+static int debug_rows_bound(const mmi_lm* lm) { return lm->max_batch > 128 ? lm->max_batch : 128; }
+
+extern "C" int mmi_lm_debug_dep_attn(mmi_lm* lm, const void* qkv_bf16, void* k_cache, void* v_cache, int32_t rows, int32_t H, int32_t Dh,
+                                     int32_t steps, int32_t k, int32_t kernel, void* out_bf16, int32_t* kernel_run, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm || !qkv_bf16 || !k_cache || !v_cache || !out_bf16) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_dep_attn: null argument");
+    if (kernel != MMI_DEP_ATTN_AUTO && kernel != MMI_DEP_ATTN_8 && kernel != MMI_DEP_ATTN_ROWS16 && kernel != MMI_DEP_ATTN_ROWS32)
+        return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_dep_attn: unknown kernel");
+    if (Dh < 1 || Dh > 64) return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_dep_attn: head dim must be 1..64");
+    if (steps < 1 || steps > 32) return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_dep_attn: steps must be 1..32");
+    if (k < 0 || k >= steps) return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_dep_attn: k must be in [0, steps)");
+    if (H < 1 || H > 1024) return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_dep_attn: 1 <= H <= 1024");
+    if (rows < 1 || rows > debug_rows_bound(lm))
+        return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_dep_attn: rows must be 1.." + std::to_string(debug_rows_bound(lm)) + " (128, or the handle's max_batch above it)");
+    if (kernel == MMI_DEP_ATTN_8 && (Dh % 8 || steps > 8))
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_dep_attn: k_dep_attn8 needs a head dim that is a multiple of 8 and steps <= 8");
+    if (kernel == MMI_DEP_ATTN_ROWS16 && steps > 16)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_dep_attn: k_dep_attn<16> holds 16 cache rows: steps <= 16");
+    // 16-byte loads and stores of qkv and cache pieces (k_dep_attn8); bf16 stores of the result
+    if (((uintptr_t)qkv_bf16 | (uintptr_t)k_cache | (uintptr_t)v_cache) % 16 || (uintptr_t)out_bf16 % 2)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_dep_attn: qkv and the caches must be 16-byte aligned, out 2-byte");
+    hipStream_t s = (hipStream_t)stream;
+    const int d = H * Dh, T = rows <= 16 ? 16 : 32, mt = mmi_cdiv(rows, T), ksteps = mmi_cdiv(d, mmi_kstep(T));
+    const size_t oelems = (size_t)mt * ksteps * 512;
+    MmiArena A;
+    A.poison = lm->knobs.debug_poison;
+    uint16_t* att = nullptr;
+    auto done = [&](int rc) { hipStreamSynchronize(s); A.release(); return rc; };
+    if (hipSuccess != A.alloc(&att, oelems)) return done(mmi_fail(MMI_ERR_HIP, "out of device memory (mmi_lm_debug_dep_attn)"));
+    MMI_DBG_HIP(hipMemsetAsync(att, 0, oelems * 2, s));
+    DepAttnArgs da;
+    da.qkv = (const uint16_t*)qkv_bf16; da.kc = (uint16_t*)k_cache; da.vc = (uint16_t*)v_cache; da.out = att;
+    da.B = rows; da.H = H; da.Dh = Dh; da.steps = steps; da.k = k; da.T = T; da.out_ksteps = ksteps;
+    int ran = -1;
+    const int rc = launch_dep_attn(s, da, kernel, &ran);
+    if (rc) return done(rc);
+    MMI_LAUNCH(k_unpack_rows, mmi_cdiv(rows * d, 256), 256, 0, s, (const uint16_t*)att, rows, d, (uint16_t*)out_bf16, T, ksteps);
+    MMI_DBG_LAUNCHED();
+    if (hipStreamSynchronize(s) != hipSuccess) { A.release(); return mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_dep_attn: the launches failed"); }
+    A.release();
+    if (kernel_run) *kernel_run = ran;
+    return MMI_OK;
+}
+
+// The same for the attention inside out_proj: depth layer `layer`, micro-step k >= 1 of the handle's own model, ONE row.  fused != 0:
+// the launch and plan of add_dep_attn_out_proj; else the two launches it replaces - launch_dep_attn, then out_proj through
+// launch_gemm with the arguments add_gemm gives it.
+extern "C" int mmi_lm_debug_dep_attn_out_proj(mmi_lm* lm, int32_t layer, int32_t k, int32_t fused, const void* qkv_bf16, void* k_cache,
+                                              void* v_cache, const void* x_bf16, void* out_bf16, void* att_bf16, int32_t* kernel_run,
+                                              mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm || !qkv_bf16 || !k_cache || !v_cache || !x_bf16 || !out_bf16) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_dep_attn_out_proj: null argument");
+    const mmi_lm_cfg& c = lm->cfg;
+    if (layer < 0 || layer >= c.depformer_num_layers) return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_dep_attn_out_proj: layer must be in [0, depformer_num_layers)");
+    if (k < 1 || k >= c.dep_q) return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_dep_attn_out_proj: k must be in [1, dep_q) (micro-step 0 has no attention launch)");
+    const int dd = c.depformer_dim, H = c.depformer_num_heads, Dh = dd / H, steps = c.dep_q;
+    const GemmW g = lm->dep_layers[layer].out_proj[k];
+    if (!dep_attn_fusable(lm, g, H, Dh, steps, 1))
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_dep_attn_out_proj: the engine does not run this out_proj with the attention inside (dep_attn_fusable)");
+    if (((uintptr_t)qkv_bf16 | (uintptr_t)k_cache | (uintptr_t)v_cache) % 16 || ((uintptr_t)x_bf16 | (uintptr_t)out_bf16 | (uintptr_t)att_bf16) % 2)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_dep_attn_out_proj: qkv and the caches must be 16-byte aligned, x and out 2-byte");
+    hipStream_t s = (hipStream_t)stream;
+    const int T = g.T, ksteps = packed_ksteps_t(lm, T, dd);
+    const size_t elems = (size_t)ksteps * 512;
+    MmiArena A;
+    A.poison = lm->knobs.debug_poison;
+    uint16_t *xp = nullptr, *att = nullptr;
+    auto done = [&](int rc) { hipStreamSynchronize(s); A.release(); return rc; };
+    if (hipSuccess != A.alloc(&xp, elems) || hipSuccess != A.alloc(&att, elems))
+        return done(mmi_fail(MMI_ERR_HIP, "out of device memory (mmi_lm_debug_dep_attn_out_proj)"));
+    MMI_DBG_HIP(hipMemsetAsync(xp, 0, elems * 2, s));
+    MMI_DBG_HIP(hipMemsetAsync(att, 0, elems * 2, s));
+    MMI_LAUNCH(k_pack_rows, mmi_cdiv(dd, 256), 256, 0, s, (const uint16_t*)x_bf16, 1, dd, xp, T, ksteps);
+    MMI_DBG_LAUNCHED();
+    DepAttnArgs da;
+    da.qkv = (const uint16_t*)qkv_bf16; da.kc = (uint16_t*)k_cache; da.vc = (uint16_t*)v_cache; da.out = att;
+    da.B = 1; da.H = H; da.Dh = Dh; da.steps = steps; da.k = k; da.T = T; da.out_ksteps = ksteps;
+    int ran = -1, rc;
+    if (fused) {
+        rc = launch_dep_attn_out_proj_planned(s, plan_dep_attn_out_proj(lm, g, xp, dd, 1, 1), da);
+        ran = MMI_DEP_ATTN_FUSED;
+    } else {
+        if ((rc = launch_dep_attn(s, da, MMI_DEP_ATTN_AUTO, &ran))) return done(rc);
+        GemmArgs a;                                                 // add_gemm(lm, out_proj, datt, dx, dd, true, MMI_EPI_RESID, dx)
+        memset(&a, 0, sizeof(a));
+        a.xp = reinterpret_cast<const u32x4*>(att); a.out = xp; a.epi = MMI_EPI_RESID; a.resid = xp;
+        a.tok_rows = 1; a.B = 1; a.out_mode = MMI_OUT_PACKED; a.out_ld = dd; a.out_ksteps = ksteps;
+        rc = launch_gemm(lm, s, g, a, false);
+    }
+    if (rc) return done(rc);
+    MMI_LAUNCH(k_unpack_rows, mmi_cdiv(dd, 256), 256, 0, s, (const uint16_t*)xp, 1, dd, (uint16_t*)out_bf16, T, ksteps);
+    if (att_bf16 && !fused) MMI_LAUNCH(k_unpack_rows, mmi_cdiv(dd, 256), 256, 0, s, (const uint16_t*)att, 1, dd, (uint16_t*)att_bf16, T, ksteps);
+    MMI_DBG_LAUNCHED();
+    if (hipStreamSynchronize(s) != hipSuccess) { A.release(); return mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_dep_attn_out_proj: the launches failed"); }
+    A.release();
+    if (kernel_run) *kernel_run = ran;
+    return MMI_OK;
+}
+
+// Parity tap of the cross attention (include/moshi_mi.h): launch_cross_attn - the L.cross_attn op - on caller-supplied operands.
+extern "C" int mmi_lm_debug_cross_attn(mmi_lm* lm, const void* q_bf16, const void* kv_bf16, const int32_t* len, int32_t rows, int32_t H,
+                                       int32_t Dh, int32_t cap, void* out_bf16, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm || !q_bf16 || !kv_bf16 || !len || !out_bf16) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_cross_attn: null argument");
+    if (Dh != 32 && Dh != 64 && Dh != 128) return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_cross_attn: head dim must be 32, 64 or 128");
+    if (rows < 1 || rows > debug_rows_bound(lm))
+        return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_cross_attn: rows must be 1.." + std::to_string(debug_rows_bound(lm)) + " (128, or the handle's max_batch above it)");
+    if (H < 1 || H > 1024 || cap < 1 || cap > (1 << 20)) return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_cross_attn: 1 <= H <= 1024, 1 <= cap <= 2^20");
+    if (((uintptr_t)q_bf16 | (uintptr_t)kv_bf16) % 16 || (uintptr_t)len % 4 || (uintptr_t)out_bf16 % 2)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_cross_attn: q and kv must be 16-byte aligned, len 4-byte, out 2-byte");
+    hipStream_t s = (hipStream_t)stream;
+    // a length outside [1, cap] would put the loads (the clamped ones: row len - 1) outside the row's positions
+    std::vector<int32_t> L((size_t)rows);
+    MMI_HIP_CHECK(hipStreamSynchronize(s));
+    MMI_HIP_CHECK(hipMemcpy(L.data(), len, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int b = 0; b < rows; ++b)
+        if (L[b] < 1 || L[b] > cap) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_cross_attn: every len must be in [1, cap]");
+    const int d = H * Dh, T = rows <= 16 ? 16 : 32, mt = mmi_cdiv(rows, T), ksteps = mmi_cdiv(d, mmi_kstep(T));
+    const size_t oelems = (size_t)mt * ksteps * 512;
+    MmiArena A;
+    A.poison = lm->knobs.debug_poison;
+    uint16_t* att = nullptr;
+    auto done = [&](int rc) { hipStreamSynchronize(s); A.release(); return rc; };
+    if (hipSuccess != A.alloc(&att, oelems)) return done(mmi_fail(MMI_ERR_HIP, "out of device memory (mmi_lm_debug_cross_attn)"));
+    MMI_DBG_HIP(hipMemsetAsync(att, 0, oelems * 2, s));
+    CrossAttnArgs ca;
+    ca.q = (const uint16_t*)q_bf16; ca.kv = (const uint16_t*)kv_bf16; ca.out = att; ca.len = len;
+    ca.B = rows; ca.H = H; ca.Dh = Dh; ca.cap = cap; ca.T = T; ca.out_ksteps = ksteps;
+    const int rc = launch_cross_attn(s, ca);
+    if (rc) return done(rc);
+    MMI_LAUNCH(k_unpack_rows, mmi_cdiv(rows * d, 256), 256, 0, s, (const uint16_t*)att, rows, d, (uint16_t*)out_bf16, T, ksteps);
+    MMI_DBG_LAUNCHED();
+    if (hipStreamSynchronize(s) != hipSuccess) { A.release(); return mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_cross_attn: the launches failed"); }
     A.release();
     return MMI_OK;
 }

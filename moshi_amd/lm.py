@@ -312,6 +312,62 @@ class LMModel:
             {"launch": 0, "kernel": 1}[merge], int(solo_rows), out.data_ptr(), _capi.stream_ptr(self.device)))
         return out
 
+    DEP_ATTN_KERNELS = {"auto": 0, "attn8": 1, "rows16": 2, "rows32": 3, "fused": 4}
+    _DEP_ATTN_NAMES = {v: k for k, v in DEP_ATTN_KERNELS.items()}
+
+    def debug_dep_attn(self, qkv: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, H: int, k: int, kernel: str = "auto"):
+        """Parity tap (tests; `mmi_lm_debug_dep_attn`): micro-step `k` of the depth transformer's attention alone, through the launch
+        function of the step and of the scoring pass.  `qkv` bf16 [rows, 3 * H * Dh]; `kc`, `vc` bf16 [rows, H, steps, Dh], device
+        tensors that are read and WRITTEN in place (row k).  `kernel` "auto" (the step's choice) / "attn8" / "rows16" / "rows32".
+        Returns (bf16 [rows, H * Dh], the name of the kernel that ran)."""
+        qkv = qkv.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        rows, steps, Dh = kc.shape[0], kc.shape[2], kc.shape[3]
+        for c in (kc, vc):
+            assert c.dtype == torch.bfloat16 and c.is_contiguous() and c.device == qkv.device and c.shape == (rows, H, steps, Dh), \
+                "the caches are contiguous bf16 [rows, H, steps, Dh] on the handle's device (they are written in place)"
+        assert qkv.shape == (rows, 3 * H * Dh), "qkv is [rows, 3 * H * Dh]"
+        out = torch.empty(rows, H * Dh, dtype=torch.bfloat16, device=self.device)
+        ran = C.c_int32(-1)
+        self._lib.check(self._lib.mmi_lm_debug_dep_attn(self._handle, qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(), rows, int(H), Dh, steps,
+                                                        int(k), self.DEP_ATTN_KERNELS[kernel], out.data_ptr(), C.byref(ran),
+                                                        _capi.stream_ptr(self.device)))
+        return out, self._DEP_ATTN_NAMES[ran.value]
+
+    def debug_dep_attn_out_proj(self, layer: int, k: int, qkv: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, x: torch.Tensor,
+                                fused: bool = True):
+        """Parity tap (tests; `mmi_lm_debug_dep_attn_out_proj`): x + out_proj(attention) of one row with the out_proj weight of depth
+        layer `layer`, micro-step `k` >= 1 of this model - `fused`: the attention inside the GEMM (k_dep_attn_out_proj), else the two
+        launches it replaces.  `qkv` bf16 [3 * dd], `kc` / `vc` bf16 [H, dep_q, Dh] (written in place), `x` bf16 [dd].
+        Returns (bf16 [dd], the attention output bf16 [dd] of the two-launch form or None, the name of the kernel that ran)."""
+        qkv, x = (t.to(device=self.device, dtype=torch.bfloat16).contiguous().reshape(-1) for t in (qkv, x))
+        dd = x.numel()
+        assert qkv.numel() == 3 * dd, "qkv is [3 * depformer_dim]"
+        for c in (kc, vc):
+            assert c.dtype == torch.bfloat16 and c.is_contiguous() and c.device == qkv.device and c.numel() == dd * self.config.dep_q, \
+                "the caches are contiguous bf16 [H, dep_q, Dh] on the handle's device (they are written in place)"
+        out = torch.empty(dd, dtype=torch.bfloat16, device=self.device)
+        att = None if fused else torch.empty(dd, dtype=torch.bfloat16, device=self.device)
+        ran = C.c_int32(-1)
+        self._lib.check(self._lib.mmi_lm_debug_dep_attn_out_proj(
+            self._handle, int(layer), int(k), 1 if fused else 0, qkv.data_ptr(), kc.data_ptr(), vc.data_ptr(), x.data_ptr(), out.data_ptr(),
+            None if fused else att.data_ptr(), C.byref(ran), _capi.stream_ptr(self.device)))
+        return out, att, self._DEP_ATTN_NAMES[ran.value]
+
+    def debug_cross_attn(self, q: torch.Tensor, kv: torch.Tensor, length: torch.Tensor) -> torch.Tensor:
+        """Parity tap (tests; `mmi_lm_debug_cross_attn`): the cross attention alone, through the step's launch function.  `q` bf16
+        [rows, H, Dh]; `kv` bf16 [rows, cap, 2 * H * Dh] (keys, then values); `length` int32 [rows], each in [1, cap].
+        Returns bf16 [rows, H * Dh]."""
+        q = q.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        rows, H, Dh = q.shape
+        kv = kv.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        assert kv.dim() == 3 and kv.shape[0] == rows and kv.shape[2] == 2 * H * Dh, "kv is [rows, cap, 2 * H * Dh]"
+        length = length.to(device=self.device, dtype=torch.int32).contiguous()
+        assert length.shape == (rows,), "one length per row"
+        out = torch.empty(rows, H * Dh, dtype=torch.bfloat16, device=self.device)
+        self._lib.check(self._lib.mmi_lm_debug_cross_attn(self._handle, q.data_ptr(), kv.data_ptr(), length.data_ptr(), rows, H, Dh,
+                                                          int(kv.shape[1]), out.data_ptr(), _capi.stream_ptr(self.device)))
+        return out
+
     def debug_prefill_attn(self, q: torch.Tensor, row_ring: torch.Tensor, row_pos: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                            k_staged: torch.Tensor, v_staged: torch.Tensor, cap: int, context: Optional[int] = None, ring: str = "bf16",
                            n_blocks: int = 1, rings: int = 1) -> torch.Tensor:

@@ -42,6 +42,29 @@ def test_tiny_matches_oracle_with_masks_and_reset(gpu_lib, B):
     lm_cases.oracle_vs_engine(DEV, None, tiny_lm_config(), seed=50 + B, B=B, S=16 if B <= 5 else 4)
 
 
+@pytest.mark.parametrize("B", [1, 5])
+def test_twelve_generated_codebooks_run_the_16_row_depth_attention(gpu_lib, B):
+    """dep_q = 12 (checkpoints with 9..16 generated codebooks): the step's dep.attn op launches k_dep_attn<16>, at one session too
+    (the attention inside out_proj takes at most 8 positions); micro-step 0 has no attention launch."""
+    from dataclasses import replace
+    cfg = replace(tiny_lm_config(), dep_q=12)
+    st = {}
+    lm_cases.oracle_vs_engine(DEV, None, cfg, seed=90 + B, B=B, S=5, stats=st)
+    assert st["launch_sites"]["dep.attn"] == 11 * 2
+    # the launch list names kernels without their template arguments: the general kernel, not k_dep_attn8 and not the fused one ...
+    assert {k for site, k in st["launch_list"] if site == "dep.attn"} == {"k_dep_attn"}
+    assert not any("k_dep_attn_out_proj" in k or "k_dep_attn8" in k for _, k in st["launch_list"])
+    # ... and of its two forms the op's own launch function (launch_dep_attn, through the tap) takes the 16-row one at this shape
+    from tests import dep_attn_cases as dc
+    from tests.lm_cases import cached_lm_state_dict
+    from moshi_amd import LMModel
+    lm = LMModel(cached_lm_state_dict(cfg, 90 + B), cfg, device=DEV, max_batch=B, lib=None)
+    Dh = cfg.depformer_dim // cfg.depformer_num_heads
+    lc = dc.build_dep(dc.Shape("auto", "rows16", Dh, cfg.dep_q, (11,)), 11, "random", rows=B, heads=cfg.depformer_num_heads)
+    msg = dc._within(dc.run_dep(lm, lc), lc.ref, lc.A, "dep_q=12 k=11")
+    assert not msg, msg
+
+
 @pytest.mark.parametrize("kv,path", [("bf16", "launch"), ("bf16", "solo"), ("bf16", "switch"), ("bf16", "kernel"), ("fp8", "switch")])
 def test_long_ring_split_over_workgroups_matches_oracle(gpu_lib, monkeypatch, kv, path):
     """A ring longer than one 256-slot chunk with few (session, head) pairs: the decode attention (k_lm_attn_wave) splits the

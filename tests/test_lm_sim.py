@@ -121,6 +121,29 @@ def test_depformer_attention_inside_out_proj_for_one_session(sim_lib, monkeypatc
     assert st["launch_sites"]["dep.attn"] == 7 * 2
 
 
+@pytest.mark.parametrize("B", [1, 5])
+def test_twelve_generated_codebooks_run_the_16_row_depth_attention(sim_lib, B):
+    """dep_q = 12 (checkpoints with 9..16 generated codebooks): the step's dep.attn op launches k_dep_attn<16>, at one session too
+    (the attention inside out_proj takes at most 8 positions); micro-step 0 has no attention launch."""
+    from dataclasses import replace
+    cfg = replace(tiny_lm_config(), dep_q=12)
+    st = {}
+    lm_cases.oracle_vs_engine("cpu", sim_lib, cfg, seed=90 + B, B=B, S=5, stats=st)
+    assert st["launch_sites"]["dep.attn"] == 11 * 2
+    # the launch list names kernels without their template arguments: the general kernel, not k_dep_attn8 and not the fused one ...
+    assert {k for site, k in st["launch_list"] if site == "dep.attn"} == {"k_dep_attn"}
+    assert not any("k_dep_attn_out_proj" in k or "k_dep_attn8" in k for _, k in st["launch_list"])
+    # ... and of its two forms the op's own launch function (launch_dep_attn, through the tap) takes the 16-row one at this shape
+    from tests import dep_attn_cases as dc
+    from tests.lm_cases import cached_lm_state_dict
+    from moshi_amd import LMModel
+    lm = LMModel(cached_lm_state_dict(cfg, 90 + B), cfg, device="cpu", max_batch=B, lib=sim_lib)
+    Dh = cfg.depformer_dim // cfg.depformer_num_heads
+    lc = dc.build_dep(dc.Shape("auto", "rows16", Dh, cfg.dep_q, (11,)), 11, "random", rows=B, heads=cfg.depformer_num_heads)
+    msg = dc._within(dc.run_dep(lm, lc), lc.ref, lc.A, "dep_q=12 k=11")
+    assert not msg, msg
+
+
 def test_split_k_gemm_with_fused_residual_norm(sim_lib, monkeypatch):
     """The K-split GEMM path (fp32 partials folded into the residual stream by k_resid_rmsnorm) that the 4096-wide
     layers take at 17..64 sessions, forced onto the tiny shapes."""
