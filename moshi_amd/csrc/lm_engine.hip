@@ -48,6 +48,43 @@ struct EvPair { hipEvent_t a, b; };
 // like the linear's own); slot j owns rows / columns [j * R, (j + 1) * R), zero where nothing is loaded
 struct LoraBank { u32x4* a = nullptr; u32x4* b = nullptr; };
 
+// One buffer of a stream's device memory, declared ONCE: state_table() lists the streaming-state arena (mmi_lm::st), prefill_table()
+// and score_table() the prefill arena.  The allocation, the start-up fill, mmi_lm_streaming_stop and mmi_lm_debug_state_regions all
+// walk these lists.  The order of state_table() is the layout of a snapshot (mmi_lm_state_save): DESIGN.md section 2.
+struct BufDecl {
+    void** slot;                // the mmi_lm member that receives the pointer
+    size_t elem, count;         // element size and count (an empty buffer still takes one element: MmiArena::alloc's rule)
+    const char* name;
+    int rows;                   // equal per-session slices, or 0
+    int kind;                   // 1 = what a session is, 0 = rewritten before it is read (reported as `scratch<arena index>`)
+    enum { UNTOUCHED, BYTES, I32 } init = UNTOUCHED;   // how it starts: as allocated, a byte fill, or ints through k_fill_i32
+    int value = 0;
+    size_t tail = 0;            // elements behind `count`, allocated and filled with it but outside the reported region
+    int late = 0;               // the regions report lists the state buffers in table order, those with late > 0 behind them by
+                                // ascending `late` (its line order is older than the table; tests/golden/lm_state_layout.json pins it)
+    size_t off = 0, size = 0;   // where the arena holds it: set by alloc_table
+    BufDecl& fill(int byte) { init = BYTES; value = byte; return *this; }
+    BufDecl& fill_i32(int v) { init = I32; value = v; return *this; }
+};
+
+struct BufTable : std::vector<BufDecl> {
+    template <class T>
+    BufDecl& add(T** slot, size_t count, const char* name, int rows = 0, int kind = 0) {
+        push_back(BufDecl{reinterpret_cast<void**>(slot), sizeof(T), count, name, rows, kind});
+        return back();
+    }
+};
+
+// The temporal ring of the stream (keys or values; filled at streaming_start).  bf16: an element each; e4m3: a byte each; 4-bit
+// (MMI_F4E2M1X2): per layer the codes plane [B][H][cap][Dh/2] bytes, then the scale plane [B][H][cap][Dh/16] bytes.
+struct KvRing {
+    int form = 0;               // kv_form
+    size_t elems = 0;           // values per layer: B * H * context * Dh
+    size_t layer_u16 = 0;       // layer stride in uint16 units (kv_layer_u16: the 4-bit layer is padded)
+    size_t codes_bytes = 0;     // bytes of a layer's values (the codes plane of the 4-bit form)
+    size_t scale_off = 0;       // byte offset of the scale plane inside a 4-bit layer (elems / 16 bytes long), else 0
+};
+
 }  // namespace
 
 struct mmi_lm {
@@ -110,6 +147,8 @@ struct mmi_lm {
     mmi_sampling samp;
     int kmax = 0;
     MmiArena st;
+    BufTable st_table;              // what `st` holds, in allocation order (state_table): entry i is allocation i of the arena
+    KvRing ring;
     uint8_t* exec = nullptr;
     long* offsets = nullptr;
     int* cache = nullptr;
@@ -191,6 +230,7 @@ struct mmi_lm {
     // to the stream - an arena of its own, so that the streaming-state arena (mmi_lm_state_bytes, snapshots) is what it was
     int prefill_rows = 0;
     MmiArena pf_mem;
+    BufTable pf_table;              // what `pf_mem` holds (prefill_table, then score_table)
     struct {
         int* tokens = nullptr;          // [rows][NC] model input
         int* row_sess = nullptr;        // [rows]
@@ -1203,6 +1243,16 @@ static int kv_form(int32_t kv_cache_dtype) { return kv_cache_dtype == MMI_F8E4M3
 // The 4-bit layer is padded to a multiple of 256 bytes, so that the next layer's codes plane starts 16-byte aligned whatever the
 // capacity (the scale plane is a multiple of 2 bytes only); the other rings are as they were.
 static size_t kv_layer_u16(int kvf, size_t elems) { return kvf == 2 ? (elems / 4 + elems / 32 + 127) / 128 * 128 : elems / (kvf ? 2 : 1); }
+// The ring of a stream of B model rows: the one place that derives it from the configuration (mmi_lm::ring)
+static KvRing kv_ring_of(const mmi_lm_cfg& c, int B) {
+    KvRing r;
+    r.form = kv_form(c.kv_cache_dtype);
+    r.elems = (size_t)B * c.num_heads * c.context * (c.dim / c.num_heads);
+    r.layer_u16 = kv_layer_u16(r.form, r.elems);
+    r.codes_bytes = r.form == 2 ? r.elems / 2 : r.elems * (r.form ? 1 : 2);
+    r.scale_off = r.form == 2 ? r.codes_bytes : 0;
+    return r;
+}
 
 // kvf: the ring form (kv_form).  The bf16 and e4m3 launches are spelled as they always were: the spelling is the kernel's name in
 // mmi_lm_launch_list
@@ -1327,8 +1377,8 @@ int build_program(mmi_lm* lm) {
     // ---- temporal transformer
     const int NS = attn_splits(lm->knobs, c, B);
     lm->attn_ns = NS;
-    const int kvf = kv_form(c.kv_cache_dtype);
-    const size_t kv_layer = kv_layer_u16(kvf, (size_t)B * H * c.context * Dh);  // in uint16 units: an fp8 ring is half as large
+    const int kvf = lm->ring.form;
+    const size_t kv_layer = lm->ring.layer_u16;  // in uint16 units: an fp8 ring is half as large
     Pending pending;   // split-K partials of the previous linear_out still to be folded into x
     for (int l = 0; l < c.num_layers; ++l) {
         const LayerW& L = lm->layers[l];
@@ -1341,7 +1391,7 @@ int build_program(mmi_lm* lm) {
         a.B = B; a.H = H; a.Dh = Dh; a.cap = c.context; a.context = c.context; a.NS = NS; a.max_period = c.max_period;
         a.T = lm->T; a.out_ksteps = packed_ksteps(lm, d);
         a.done = lm->attn_done; a.solo_rows = attn_solo_rows(lm->knobs, B * H);
-        a.kv_soff = kvf == 2 ? (long)B * H * c.context * Dh / 2 : 0;
+        a.kv_soff = (long)lm->ring.scale_off;
         P.site("L.in_proj");
         {   // in_proj with RoPE + ring-KV write in its epilogue
             GemmArgs ga;
@@ -1966,70 +2016,84 @@ static int score_refusal(const mmi_lm* lm) {
     return MMI_OK;
 }
 
-// the scoring scratch, beside the prefill scratch in its arena (outside the streaming-state arena)
-static int score_alloc(mmi_lm* lm, hipStream_t s) {
-    const mmi_lm_cfg& c = lm->cfg;
-    int rc = score_refusal(lm);
-    if (rc) return rc;
-    const int rows = lm->prefill_rows, d = c.dim, dd = c.depformer_dim, q = c.dep_q;
-    const size_t mt = (size_t)mmi_cdiv(rows, lm->T), mtd = (size_t)mmi_cdiv(rows, lm->Td);
-    auto packed_d = [&](int features) { return mtd * packed_ksteps_t(lm, lm->Td, features) * 512; };
-    MmiArena& A = lm->pf_mem;
-    auto& S = lm->sc;
-    bool ok = true;
-    ok &= hipSuccess == A.alloc(&S.tout, mt * packed_ksteps(lm, d) * 512);
-    ok &= hipSuccess == A.alloc(&S.tlog, (size_t)rows * c.text_card_out);
-    ok &= hipSuccess == A.alloc(&S.targets, (size_t)rows * (1 + q));
-    if (!ok) return mmi_fail(MMI_ERR_HIP, "out of device memory (score scratch)");
-    MMI_HIP_CHECK(hipMemsetAsync(S.tout, 0, mt * packed_ksteps(lm, d) * 512 * sizeof(uint16_t), s));
-    if (q == 0) return MMI_OK;
-    const size_t dkv = (size_t)c.depformer_num_layers * rows * dd * q;       // [layers][rows][Hd][dep_q][Dhd]
-    ok &= hipSuccess == A.alloc(&S.dpre, (size_t)rows * dd);
-    ok &= hipSuccess == A.alloc(&S.dx, packed_d(dd));
-    ok &= hipSuccess == A.alloc(&S.dxn, packed_d(dd));
-    ok &= hipSuccess == A.alloc(&S.datt, packed_d(dd));
-    ok &= hipSuccess == A.alloc(&S.dhb, packed_d(c.depformer_ffn_hidden));
-    ok &= hipSuccess == A.alloc(&S.dqkv, (size_t)rows * 3 * dd);
-    ok &= hipSuccess == A.alloc(&S.dkc, dkv);
-    ok &= hipSuccess == A.alloc(&S.dvc, dkv);
-    ok &= hipSuccess == A.alloc(&S.alog, (size_t)q * rows * c.card);
-    if (!ok) return mmi_fail(MMI_ERR_HIP, "out of device memory (score scratch)");
-    struct { uint16_t* p; int f; } pk[] = {{S.dx, dd}, {S.dxn, dd}, {S.datt, dd}, {S.dhb, c.depformer_ffn_hidden}};
-    for (auto& e : pk) MMI_HIP_CHECK(hipMemsetAsync(e.p, 0, packed_d(e.f) * sizeof(uint16_t), s));
+// Allocates entries [from, end) of `t` in `A`, in the table's order, hands every member its pointer and starts the fills on s
+static int alloc_table(MmiArena& A, BufTable& t, size_t from, hipStream_t s, const char* what) {
+    for (size_t i = from; i < t.size(); ++i) {
+        BufDecl& e = t[i];
+        const size_t nb = (e.count + e.tail) * e.elem;
+        e.off = A.bytes;
+        e.size = nb ? nb : e.elem;
+        if (A.alloc(reinterpret_cast<uint8_t**>(e.slot), e.size) != hipSuccess)
+            return mmi_fail(MMI_ERR_HIP, std::string("out of device memory (") + what + ")");
+    }
+    for (size_t i = from; i < t.size(); ++i) {
+        const BufDecl& e = t[i];
+        const size_t n = e.count + e.tail;
+        if (e.init == BufDecl::BYTES) MMI_HIP_CHECK(hipMemsetAsync(*e.slot, e.value, n * e.elem, s));
+        if (e.init == BufDecl::I32) MMI_LAUNCH(k_fill_i32, mmi_cdiv((int)n, 256), 256, 0, s, (int*)*e.slot, e.value, (long)n);
+    }
+    MMI_CHECK_LAUNCH();
     return MMI_OK;
 }
 
-static int prefill_alloc(mmi_lm* lm, hipStream_t s) {
+// The scoring scratch, beside the prefill scratch in its arena (outside the streaming-state arena).  Packed activations start as
+// zeros: the padding rows / columns of a fragment are never written and must read as zero.
+static void score_table(mmi_lm* lm, BufTable& t) {
     const mmi_lm_cfg& c = lm->cfg;
-    const int rows = lm->prefill_rows, d = c.dim, H = c.num_heads, Dh = d / H, kvf = kv_form(c.kv_cache_dtype);
-    int rc = prefill_refusal(lm, rows);           // (adapters or the TTS machine may have been enabled after the prefill was)
-    if (rc) return rc;
-    const size_t mtiles = (size_t)mmi_cdiv(rows, lm->T);
+    const int rows = lm->prefill_rows, d = c.dim, dd = c.depformer_dim, q = c.dep_q;
+    const size_t mt = (size_t)mmi_cdiv(rows, lm->T), mtd = (size_t)mmi_cdiv(rows, lm->Td);
+    auto packed_d = [&](int features) { return mtd * packed_ksteps_t(lm, lm->Td, features) * 512; };
+    auto& S = lm->sc;
+    t.add(&S.tout, mt * packed_ksteps(lm, d) * 512, "sc.tout").fill(0);
+    t.add(&S.tlog, (size_t)rows * c.text_card_out, "sc.tlog");
+    t.add(&S.targets, (size_t)rows * (1 + q), "sc.targets");
+    if (q == 0) return;
+    const size_t dkv = (size_t)c.depformer_num_layers * rows * dd * q;       // [layers][rows][Hd][dep_q][Dhd]
+    t.add(&S.dpre, (size_t)rows * dd, "sc.dpre");
+    t.add(&S.dx, packed_d(dd), "sc.dx").fill(0);
+    t.add(&S.dxn, packed_d(dd), "sc.dxn").fill(0);
+    t.add(&S.datt, packed_d(dd), "sc.datt").fill(0);
+    t.add(&S.dhb, packed_d(c.depformer_ffn_hidden), "sc.dhb").fill(0);
+    t.add(&S.dqkv, (size_t)rows * 3 * dd, "sc.dqkv");
+    t.add(&S.dkc, dkv, "sc.dkc");
+    t.add(&S.dvc, dkv, "sc.dvc");
+    t.add(&S.alog, (size_t)q * rows * c.card, "sc.alog");
+}
+
+static void prefill_table(mmi_lm* lm, BufTable& t) {
+    const mmi_lm_cfg& c = lm->cfg;
+    const int rows = lm->prefill_rows, d = c.dim, H = c.num_heads, Dh = d / H;
+    const size_t mtiles = (size_t)mmi_cdiv(rows, lm->T), staged = (size_t)rows * H * pf_row_bytes(lm->ring.form, Dh);
     auto packed = [&](int features) { return mtiles * packed_ksteps(lm, features) * 512; };
-    MmiArena& A = lm->pf_mem;
-    A.poison = lm->st.poison;
     auto& P = lm->pf;
-    bool ok = true;
-    ok &= hipSuccess == A.alloc(&P.tokens, (size_t)rows * lm->NC);
-    ok &= hipSuccess == A.alloc(&P.row_sess, (size_t)rows);
-    ok &= hipSuccess == A.alloc(&P.row_pos, (size_t)rows);
-    ok &= hipSuccess == A.alloc(&P.rope, (size_t)rows * Dh);
-    ok &= hipSuccess == A.alloc(&P.x, packed(d));
-    ok &= hipSuccess == A.alloc(&P.xn, packed(d));
-    ok &= hipSuccess == A.alloc(&P.att, packed(d));
-    ok &= hipSuccess == A.alloc(&P.hb, packed(c.ffn_hidden));
-    ok &= hipSuccess == A.alloc(&P.qkv, (size_t)rows * 3 * d);
-    ok &= hipSuccess == A.alloc(&P.q, (size_t)rows * d);
-    ok &= hipSuccess == A.alloc(&P.sk, (size_t)rows * H * pf_row_bytes(kvf, Dh));
-    ok &= hipSuccess == A.alloc(&P.sv, (size_t)rows * H * pf_row_bytes(kvf, Dh));
-    ok &= hipSuccess == A.alloc(&P.sks, (size_t)rows * H * (Dh / 16));
-    ok &= hipSuccess == A.alloc(&P.svs, (size_t)rows * H * (Dh / 16));
-    ok &= hipSuccess == A.alloc(&P.partial, (size_t)4 * rows * d);
-    if (!ok) return mmi_fail(MMI_ERR_HIP, "out of device memory (prefill scratch)");
-    // packed activations: the padding rows / columns of a fragment are never written and must read as zero
-    struct { uint16_t* p; int f; } pk[] = {{P.x, d}, {P.xn, d}, {P.att, d}, {P.hb, c.ffn_hidden}};
-    for (auto& e : pk) MMI_HIP_CHECK(hipMemsetAsync(e.p, 0, packed(e.f) * sizeof(uint16_t), s));
-    return lm->score_on ? score_alloc(lm, s) : (int)MMI_OK;
+    t.add(&P.tokens, (size_t)rows * lm->NC, "pf.tokens");
+    t.add(&P.row_sess, (size_t)rows, "pf.row_sess");
+    t.add(&P.row_pos, (size_t)rows, "pf.row_pos");
+    t.add(&P.rope, (size_t)rows * Dh, "pf.rope");
+    t.add(&P.x, packed(d), "pf.x").fill(0);
+    t.add(&P.xn, packed(d), "pf.xn").fill(0);
+    t.add(&P.att, packed(d), "pf.att").fill(0);
+    t.add(&P.hb, packed(c.ffn_hidden), "pf.hb").fill(0);
+    t.add(&P.qkv, (size_t)rows * 3 * d, "pf.qkv");
+    t.add(&P.q, (size_t)rows * d, "pf.q");
+    t.add(&P.sk, staged, "pf.sk");
+    t.add(&P.sv, staged, "pf.sv");
+    t.add(&P.sks, (size_t)rows * H * (Dh / 16), "pf.sks");
+    t.add(&P.svs, (size_t)rows * H * (Dh / 16), "pf.svs");
+    t.add(&P.partial, (size_t)4 * rows * d, "pf.partial");
+}
+
+// the scratch of a stream's prefill passes (and of its scoring): an arena of its own, see mmi_lm::pf_mem
+static int prefill_alloc(mmi_lm* lm, hipStream_t s) {
+    int rc = prefill_refusal(lm, lm->prefill_rows);           // (adapters or the TTS machine may have been enabled after the prefill was)
+    if (rc) return rc;
+    lm->pf_mem.poison = lm->st.poison;
+    prefill_table(lm, lm->pf_table);
+    if ((rc = alloc_table(lm->pf_mem, lm->pf_table, 0, s, "prefill scratch")) || !lm->score_on) return rc;
+    if ((rc = score_refusal(lm))) return rc;
+    const size_t from = lm->pf_table.size();
+    score_table(lm, lm->pf_table);
+    return alloc_table(lm->pf_mem, lm->pf_table, from, s, "score scratch");
 }
 
 template <int KVF>
@@ -2157,7 +2221,7 @@ static int score_heads(mmi_lm* lm, hipStream_t s, const PfArgs& p, const int64_t
 static int prefill_pass(mmi_lm* lm, hipStream_t s, PfArgs p, const int64_t* user, const int64_t* toks, const mmi_score_out* score = nullptr,
                         bool commit = true) {
     const mmi_lm_cfg& c = lm->cfg;
-    const int d = c.dim, H = c.num_heads, Dh = d / H, R = p.n * p.F, n_user = c.n_q - c.dep_q, kvf = kv_form(c.kv_cache_dtype);
+    const int d = c.dim, H = c.num_heads, Dh = d / H, R = p.n * p.F, n_user = c.n_q - c.dep_q, kvf = lm->ring.form;
     auto& P = lm->pf;
     TokArgs t = tok_args(lm);
     MMI_LAUNCH(k_pf_prepare, mmi_cdiv(R * lm->NC + R * (Dh / 2), 128), 128, 0, s, t, p, (const long*)user, n_user, (const long*)toks, P.tokens,
@@ -2166,7 +2230,7 @@ static int prefill_pass(mmi_lm* lm, hipStream_t s, PfArgs p, const int64_t* user
                (const uint16_t*)lm->text_emb, (const uint16_t*)(lm->demux ? lm->text_emb2 : nullptr), c.text_card + 1, P.x, d, lm->T,
                packed_ksteps(lm, d), (const uint16_t*)lm->cond, (const int*)P.row_sess);
     MMI_CHECK_LAUNCH();
-    const size_t kv_layer = kv_layer_u16(kvf, (size_t)lm->batch * H * c.context * Dh);
+    const size_t kv_layer = lm->ring.layer_u16;
     int pending = 0, rc;
     for (int l = 0; l < c.num_layers; ++l) {
         const LayerW& L = lm->layers[l];
@@ -2182,7 +2246,7 @@ static int prefill_pass(mmi_lm* lm, hipStream_t s, PfArgs p, const int64_t* user
         PfAttnArgs a;
         memset(&a, 0, sizeof(a));
         a.q = P.q; a.kc = reinterpret_cast<uint8_t*>(lm->kc + l * kv_layer); a.vc = reinterpret_cast<uint8_t*>(lm->vc + l * kv_layer);
-        a.kv_soff = kvf == 2 ? (long)lm->batch * H * c.context * Dh / 2 : 0;
+        a.kv_soff = (long)lm->ring.scale_off;
         a.sk = P.sk; a.sv = P.sv; a.sks = P.sks; a.svs = P.svs; a.row_sess = P.row_sess; a.row_pos = P.row_pos;
         a.out = P.att; a.T = lm->T; a.out_ksteps = packed_ksteps(lm, d);
         a.H = H; a.cap = c.context; a.context = c.context; a.n = p.n; a.F = p.F;
@@ -2367,52 +2431,27 @@ extern "C" int mmi_lm_last_tokens(mmi_lm* lm, int64_t* out, mmi_stream stream) {
 // session IS), 0 = scratch that every step rewrites before reading it.
 extern "C" int64_t mmi_lm_debug_state_regions(const mmi_lm* lm, char* buf, int64_t cap) {
     if (!lm || !lm->streaming) return 0;
-    const mmi_lm_cfg& c = lm->cfg;
-    const int G = lm->gen_batch, B = lm->batch, H = c.num_heads, Dh = c.dim / H, kvf = kv_form(c.kv_cache_dtype);
-    std::vector<size_t> at(lm->st.ptrs.size());
-    size_t sum = 0;
-    for (size_t i = 0; i < at.size(); ++i) { at[i] = sum; sum += lm->st.sizes[i]; }
-    struct Reg { std::string name; size_t off, bytes; int rows, kind; };
-    std::vector<Reg> regs;
-    std::vector<uint8_t> named(at.size(), 0);
-    auto base = [&](const void* p, size_t* off) {
-        for (size_t i = 0; i < at.size(); ++i)
-            if (lm->st.ptrs[i] == p) { named[i] = 1; *off = at[i]; return true; }
-        return false;
+    const BufTable& t = lm->st_table;
+    const KvRing& ring = lm->ring;
+    std::string text;
+    auto line = [&](const std::string& name, size_t off, size_t bytes, int rows, int kind) {
+        text += name + "\t" + std::to_string(off) + "\t" + std::to_string(bytes) + "\t" + std::to_string(rows) + "\t" + std::to_string(kind) + "\n";
     };
-    auto add = [&](const char* name, const void* p, size_t bytes, int rows) {
-        size_t off;
-        if (p && base(p, &off)) regs.push_back({name, off, bytes, rows, 1});
-    };
-    add("exec", lm->exec, (size_t)G, G);
-    add("offsets", lm->offsets, (size_t)G * sizeof(long), G);
-    add("cache", lm->cache, (size_t)G * lm->NC * lm->CT * sizeof(int), G);
-    add("text_tok", lm->text_tok, (size_t)G * sizeof(int), G);
-    add("audio_tok", lm->audio_tok, (size_t)G * c.dep_q * sizeof(int), c.dep_q ? G : 0);
-    add("rng", lm->rng, 2 * sizeof(unsigned long long), 0);
-    add("rowtab", lm->rowtab, (size_t)G * sizeof(RowSamp), G);
-    add("thist", lm->thist, (size_t)G * MMI_TEXT_HIST * sizeof(int), G);
-    add("coefs", lm->coefs, (size_t)G * sizeof(float), G);
-    add("cond", lm->cond, (size_t)B * c.dim * sizeof(uint16_t), B);
-    {   // the temporal rings, layer by layer (a 4-bit layer: codes plane, then scale plane)
-        const size_t elems = (size_t)B * H * c.context * Dh, layer = kv_layer_u16(kvf, elems) * sizeof(uint16_t);
-        for (int w = 0; w < 2; ++w) {
-            size_t off;
-            if (!base(w ? lm->vc : lm->kc, &off)) continue;
-            for (int l = 0; l < c.num_layers; ++l) {
-                const std::string nm = std::string(w ? "vc." : "kc.") + std::to_string(l);
-                if (kvf == 2) {
-                    regs.push_back({nm, off + l * layer, elems / 2, B, 1});
-                    regs.push_back({nm + ".scale", off + l * layer + elems / 2, elems / 16, B, 1});
-                } else regs.push_back({nm, off + l * layer, elems * (kvf ? 1 : 2), B, 1});
+    int last = 0;
+    for (const BufDecl& e : t) last = e.late > last ? e.late : last;
+    for (int pass = 0; pass <= last; ++pass)
+        for (const BufDecl& e : t) {
+            if (e.kind != 1 || e.late != pass) continue;
+            if (e.slot != (void**)&lm->kc && e.slot != (void**)&lm->vc) { line(e.name, e.off, e.count * e.elem, e.rows, 1); continue; }
+            for (int l = 0; l < lm->cfg.num_layers; ++l) {   // a ring, layer by layer (a 4-bit layer: codes plane, then scale plane)
+                const std::string nm = std::string(e.name) + "." + std::to_string(l);
+                const size_t off = e.off + l * ring.layer_u16 * sizeof(uint16_t);
+                line(nm, off, ring.codes_bytes, e.rows, 1);
+                if (ring.form == 2) line(nm + ".scale", off + ring.scale_off, ring.elems / 16, e.rows, 1);
             }
         }
-    }
-    for (size_t i = 0; i < at.size(); ++i)
-        if (!named[i]) regs.push_back({"scratch" + std::to_string(i), at[i], lm->st.sizes[i], 0, 0});
-    std::string text;
-    for (const Reg& r : regs)
-        text += r.name + "\t" + std::to_string(r.off) + "\t" + std::to_string(r.bytes) + "\t" + std::to_string(r.rows) + "\t" + std::to_string(r.kind) + "\n";
+    for (size_t i = 0; i < t.size(); ++i)
+        if (t[i].kind == 0) line("scratch" + std::to_string(i), t[i].off, t[i].size, 0, 0);
     const int64_t need = (int64_t)text.size() + 1;
     if (buf && cap >= need) memcpy(buf, text.c_str(), (size_t)need);
     return need;
@@ -2478,6 +2517,93 @@ extern "C" int mmi_lm_debug_prefill_attn(mmi_lm* lm, const void* q_bf16, const i
     return MMI_OK;
 }
 
+// The streaming-state arena of the stream being started, buffer by buffer: add(member, count, name, rows, kind), then how it starts.
+// ORDER IS FORMAT: a snapshot (mmi_lm_state_save) is these buffers back to back, so a new buffer goes where its feature's
+// condition puts it and nothing moves (tests/golden/lm_state_layout.json pins order, sizes and fills).
+// Needs batch / gen_batch, kmax, cross_cap, act8, tts_stride and ring of the stream.  "state*": holds per-session state but is
+// declared kind 0, because mmi_lm_debug_state_regions has always reported it as scratch.
+static void state_table(mmi_lm* lm, const mmi_guidance* guide, bool guided, BufTable& t) {
+    const mmi_lm_cfg& c = lm->cfg;
+    const int G = lm->gen_batch, B = lm->batch, d = c.dim, H = c.num_heads, Dh = d / H, dd = c.depformer_dim, q = c.dep_q, T = lm->T, Td = lm->Td;
+    const int NS = attn_splits(lm->knobs, c, B);
+    const size_t kvn = (size_t)c.num_layers * lm->ring.layer_u16;                  // uint16 units
+    const int Hd = c.depformer_num_heads, Dhd = dd / Hd;
+    const size_t dkvn = (size_t)c.depformer_num_layers * B * Hd * q * Dhd;         // [dep_layers][B][Hd][dep_q][Dhd]
+    t.add(&lm->exec, G, "exec", G, 1).fill(1);
+    t.add(&lm->offsets, G, "offsets", G, 1).fill(0);
+    if (guided) t.add(&lm->offsets_m, B, "offsets_m", B).fill(0);                                          // state*
+    if (guided && guide->cfg_is_masked_until) t.add(&lm->masked_until, G, "masked_until", G);              // state*
+    if (guide && guide->condition_sum) t.add(&lm->cond, (size_t)B * d, "cond", B, 1).late = 2;
+    t.add(&lm->coefs, G, "coefs", G, 1).late = 1;
+    if (c.cross_attention) {
+        // slots [cross_len, cap) of a row are never read before mmi_lm_set_row_condition fills them: zero for the snapshot's sake
+        BufDecl& xkv = t.add(&lm->xkv, (size_t)c.num_layers * B * lm->cross_cap * 2 * d, "xkv");          // state*
+        if (lm->cross_cap != lm->cross_len) xkv.fill(0);
+        t.add(&lm->xlen, B, "xlen", B).fill_i32(lm->cross_len);                                            // state*
+    }
+    t.add(&lm->cache, (size_t)G * lm->NC * lm->CT, "cache", G, 1).fill_i32(-2);                            // lm.py:608-613
+    t.add(&lm->user_i32, (size_t)G * (c.n_q - q), "user_i32");
+    t.add(&lm->tokens, (size_t)B * lm->NC, "tokens");
+    t.add(&lm->text_tok, G, "text_tok", G, 1).fill(0);
+    t.add(&lm->audio_tok, (size_t)G * q, "audio_tok", q ? G : 0, 1).fill(0);
+    t.add(&lm->out_i32, (size_t)G * (q + 1), "out_i32");
+    // packed activations start as zeros: the padding rows / columns of a fragment are never written and must read as zero
+    t.add(&lm->x, packed_elems(lm, d), "x").fill(0);
+    t.add(&lm->xn, packed_elems(lm, d), "xn").fill(0);
+    t.add(&lm->qrot, (size_t)B * d, "qrot");
+    t.add(&lm->att, packed_elems(lm, d), "att").fill(0);
+    t.add(&lm->hb, packed_elems(lm, c.ffn_hidden), "hb").fill(0);
+    t.add(&lm->tout, packed_elems(lm, d), "tout").fill(0);
+    t.add(&lm->text_logits, (size_t)B * c.text_card_out, "text_logits");
+    // every plane of the ring, a 4-bit ring's scale planes included: the attention reads rows past the valid length with p = 0, so
+    // they must decode to finite values - scale byte 0 is the factor 0.0f, 255 would be Inf (Inf * 0 = NaN)
+    t.add(&lm->kc, kvn, "kc", B, 1).fill(0).late = 3;
+    t.add(&lm->vc, kvn, "vc", B, 1).fill(0).late = 3;
+    t.add(&lm->opart, (size_t)B * H * NS * Dh, "opart");
+    t.add(&lm->ml, (size_t)B * H * NS * 2, "ml");
+    t.add(&lm->attn_done, (size_t)B * H, "attn_done").fill(0);
+    t.add(&lm->partial, (size_t)4 * B * (d > dd ? d : dd), "partial");
+    t.add(&lm->rope, (size_t)B * Dh, "rope");
+    if (lm->hidden_taps) t.add(&lm->htap, (size_t)2 * B * d, "htap");
+    if (lm->act8) {   // the int8 operands (see mmi_lm::act8): like their bf16 twins, padding rows / k-steps must read as zero
+        const size_t mtiles = (size_t)mmi_cdiv(B, T), rows = mtiles * T;
+        auto qbytes = [&](int features) { return mtiles * (size_t)(packed_ksteps(lm, features) / 2) * 1024; };
+        t.add(&lm->xnq, qbytes(d), "xnq").fill(0);
+        t.add(&lm->attq, qbytes(d), "attq").fill(0);
+        t.add(&lm->hbq, qbytes(c.ffn_hidden > c.depformer_ffn_hidden ? c.ffn_hidden : c.depformer_ffn_hidden), "hbq").fill(0);
+        t.add(&lm->toutq, qbytes(d), "toutq").fill(0);
+        t.add(&lm->dxnq, qbytes(dd > 0 ? dd : 8), "dxnq").fill(0);
+        t.add(&lm->sx_xn, rows, "sx_xn").fill(0);
+        t.add(&lm->sx_tout, rows, "sx_tout").fill(0);
+        t.add(&lm->sx_dxn, rows, "sx_dxn").fill(0);
+        t.add(&lm->sx_att, rows, "sx_att").fill(0);
+        t.add(&lm->sx_hb, rows, "sx_hb").fill(0);
+    }
+    t.add(&lm->dx, packed_elems_t(lm, Td, dd), "dx").fill(0);
+    t.add(&lm->dxn, packed_elems_t(lm, Td, dd), "dxn").fill(0);
+    t.add(&lm->dqkv, (size_t)B * 3 * dd, "dqkv");
+    t.add(&lm->datt, packed_elems_t(lm, Td, dd), "datt").fill(0);
+    t.add(&lm->dhb, packed_elems_t(lm, Td, c.depformer_ffn_hidden), "dhb").fill(0);
+    t.add(&lm->dlogits, (size_t)q * B * c.card, "dlogits");
+    t.add(&lm->dpre, (size_t)B * q * dd, "dpre");
+    t.add(&lm->dkc, dkvn, "dkc").fill(0);
+    t.add(&lm->dvc, dkvn, "dvc").fill(0);
+    t.add(&lm->noise, (size_t)G * (1 + q) * lm->kmax, "noise");
+    t.add(&lm->use_noise, 1, "use_noise").fill(0);
+    t.add(&lm->forced, (size_t)G * (1 + q), "forced");
+    t.add(&lm->use_forced, 1, "use_forced").fill(0);
+    t.add(&lm->rng, 2, "rng", 0, 1);
+    // every row inactive.  The nucleus table rides behind the row table (k_sample_nucleus finds it at rows + G): whole RowSamp
+    // entries, so that the snapshot of a stream without the nucleus kernels keeps its size
+    t.add(&lm->rowtab, G, "rowtab", G, 1).fill(0).tail = lm->nucleus_on ? ((size_t)G * sizeof(RowTopP) + sizeof(RowSamp) - 1) / sizeof(RowSamp) : 0;
+    t.add(&lm->thist, (size_t)G * MMI_TEXT_HIST, "thist", G, 1).fill(0);
+    if (lm->tts_on) t.add(&lm->tts, (size_t)G * lm->tts_stride, "tts", G).fill(0);    // state*; no session has a script: every header word 0
+    if (lm->lora_on) {      // every row without an adapter; the padding rows of t are never written and must read as zero
+        t.add(&lm->row_slot, G, "row_slot", G).fill_i32(-1);                           // state*
+        t.add(&lm->lora_t, (size_t)mmi_cdiv(B, T) * (lm->lora_S * lm->lora_R / mmi_kstep(T)) * 512, "lora_t").fill(0);
+    }
+}
+
 extern "C" int mmi_lm_streaming_start(mmi_lm* lm, int32_t batch, const mmi_sampling* sampling, mmi_stream stream) {
     MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
     return mmi_lm_streaming_start_guided(lm, batch, sampling, nullptr, stream);
@@ -2500,31 +2626,14 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
     lm->gen_batch = batch;
     lm->cfg_coef = guided ? guide->cfg_coef : 1.f;
     lm->cfg_no_text = guided && guide->cfg_is_no_text ? 1 : 0;
-    lm->masked_until = nullptr;
-    lm->cond = nullptr;
     lm->samp = *sampling;
     lm->kmax = sampling->top_k > sampling->top_k_text ? sampling->top_k : sampling->top_k_text;
     if (lm->kmax < 1) lm->kmax = 1;
     lm->offset_cpu = 0;
     lm->depth_bound = 0;
     lm->precapture_failed = false;
-    const int G = batch;
-    const int B = rows, d = c.dim, H = c.num_heads, Dh = d / H, dd = c.depformer_dim, Hd = c.depformer_num_heads, Dhd = dd / Hd;
-    const int NS = attn_splits(lm->knobs, c, B);
+    const int G = batch, B = rows, d = c.dim;
     auto fail = [&](int code) { lm->streaming = true; mmi_lm_streaming_stop(lm); return code; };
-    MmiArena& A = lm->st;
-    const size_t kvn = (size_t)c.num_layers * kv_layer_u16(kv_form(c.kv_cache_dtype), (size_t)B * H * c.context * Dh);   // uint16 units
-    const size_t dkvn = (size_t)c.depformer_num_layers * B * Hd * c.dep_q * Dhd;
-    bool ok = true;
-    ok &= hipSuccess == A.alloc(&lm->exec, (size_t)G);
-    ok &= hipSuccess == A.alloc(&lm->offsets, (size_t)G);
-    lm->offsets_m = lm->offsets;
-    if (guided) ok &= hipSuccess == A.alloc(&lm->offsets_m, (size_t)B);
-    if (guided && guide->cfg_is_masked_until) ok &= hipSuccess == A.alloc(&lm->masked_until, (size_t)G);
-    if (guide && guide->condition_sum) ok &= hipSuccess == A.alloc(&lm->cond, (size_t)B * d);
-    ok &= hipSuccess == A.alloc(&lm->coefs, (size_t)G);
-    lm->xkv = nullptr;
-    lm->xlen = nullptr;
     lm->cross_len = lm->cross_cap = 0;
     if (c.cross_attention) {
         if (!guide || !guide->condition_cross || guide->cross_len <= 0)
@@ -2533,171 +2642,59 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
             return fail(mmi_fail(MMI_ERR_SHAPE, "mmi_guidance.cross_len exceeds the capacity set with mmi_lm_set_cross_capacity"));
         lm->cross_len = guide->cross_len;
         lm->cross_cap = lm->cross_cap_set ? lm->cross_cap_set : lm->cross_len;
-        ok &= hipSuccess == A.alloc(&lm->xkv, (size_t)c.num_layers * B * lm->cross_cap * 2 * d);
-        ok &= hipSuccess == A.alloc(&lm->xlen, (size_t)B);
     } else if (guide && guide->condition_cross) {
         return fail(mmi_fail(MMI_ERR_INVALID, "a cross-attention condition was given to a model without cross-attention layers"));
     }
-    ok &= hipSuccess == A.alloc(&lm->cache, (size_t)G * lm->NC * lm->CT);
-    ok &= hipSuccess == A.alloc(&lm->user_i32, (size_t)G * (c.n_q - c.dep_q));
-    ok &= hipSuccess == A.alloc(&lm->tokens, (size_t)B * lm->NC);
-    ok &= hipSuccess == A.alloc(&lm->text_tok, (size_t)G);
-    ok &= hipSuccess == A.alloc(&lm->audio_tok, (size_t)G * c.dep_q);
-    ok &= hipSuccess == A.alloc(&lm->out_i32, (size_t)G * (c.dep_q + 1));
-    ok &= hipSuccess == A.alloc(&lm->x, packed_elems(lm, d));
-    ok &= hipSuccess == A.alloc(&lm->xn, packed_elems(lm, d));
-    ok &= hipSuccess == A.alloc(&lm->qrot, (size_t)B * d);
-    ok &= hipSuccess == A.alloc(&lm->att, packed_elems(lm, d));
-    ok &= hipSuccess == A.alloc(&lm->hb, packed_elems(lm, c.ffn_hidden));
-    ok &= hipSuccess == A.alloc(&lm->tout, packed_elems(lm, d));
-    ok &= hipSuccess == A.alloc(&lm->text_logits, (size_t)B * c.text_card_out);
-    ok &= hipSuccess == A.alloc(&lm->kc, kvn);
-    ok &= hipSuccess == A.alloc(&lm->vc, kvn);
-    ok &= hipSuccess == A.alloc(&lm->opart, (size_t)B * H * NS * Dh);
-    ok &= hipSuccess == A.alloc(&lm->ml, (size_t)B * H * NS * 2);
-    ok &= hipSuccess == A.alloc(&lm->attn_done, (size_t)B * H);
-    ok &= hipSuccess == A.alloc(&lm->partial, (size_t)4 * B * (d > dd ? d : dd));
-    ok &= hipSuccess == A.alloc(&lm->rope, (size_t)B * Dh);
-    lm->htap = nullptr;
-    if (lm->hidden_taps) ok &= hipSuccess == A.alloc(&lm->htap, (size_t)2 * B * d);
-    {   // int8 activations (see mmi_lm::act8)
-        lm->act8 = act8_of(lm);
-        lm->xnq = lm->attq = lm->hbq = lm->toutq = lm->dxnq = nullptr;
-        lm->sx_xn = lm->sx_tout = lm->sx_dxn = lm->sx_att = lm->sx_hb = nullptr;
-        if (lm->act8) {
-            const size_t mtiles = (size_t)mmi_cdiv(B, lm->T);
-            auto qbytes = [&](int features) { return mtiles * (size_t)(packed_ksteps(lm, features) / 2) * 1024; };
-            const size_t rows = mtiles * lm->T;
-            ok &= hipSuccess == A.alloc(&lm->xnq, qbytes(d));
-            ok &= hipSuccess == A.alloc(&lm->attq, qbytes(d));
-            ok &= hipSuccess == A.alloc(&lm->hbq, qbytes(c.ffn_hidden > c.depformer_ffn_hidden ? c.ffn_hidden : c.depformer_ffn_hidden));
-            ok &= hipSuccess == A.alloc(&lm->toutq, qbytes(d));
-            ok &= hipSuccess == A.alloc(&lm->dxnq, qbytes(dd > 0 ? dd : 8));
-            ok &= hipSuccess == A.alloc(&lm->sx_xn, rows);
-            ok &= hipSuccess == A.alloc(&lm->sx_tout, rows);
-            ok &= hipSuccess == A.alloc(&lm->sx_dxn, rows);
-            ok &= hipSuccess == A.alloc(&lm->sx_att, rows);
-            ok &= hipSuccess == A.alloc(&lm->sx_hb, rows);
-        }
-    }
-    ok &= hipSuccess == A.alloc(&lm->dx, packed_elems_t(lm, lm->Td, dd));
-    ok &= hipSuccess == A.alloc(&lm->dxn, packed_elems_t(lm, lm->Td, dd));
-    ok &= hipSuccess == A.alloc(&lm->dqkv, (size_t)B * 3 * dd);
-    ok &= hipSuccess == A.alloc(&lm->datt, packed_elems_t(lm, lm->Td, dd));
-    ok &= hipSuccess == A.alloc(&lm->dhb, packed_elems_t(lm, lm->Td, c.depformer_ffn_hidden));
-    ok &= hipSuccess == A.alloc(&lm->dlogits, (size_t)c.dep_q * B * c.card);
-    ok &= hipSuccess == A.alloc(&lm->dpre, (size_t)B * c.dep_q * dd);
-    ok &= hipSuccess == A.alloc(&lm->dkc, dkvn);
-    ok &= hipSuccess == A.alloc(&lm->dvc, dkvn);
-    ok &= hipSuccess == A.alloc(&lm->noise, (size_t)G * (1 + c.dep_q) * lm->kmax);
-    ok &= hipSuccess == A.alloc(&lm->use_noise, (size_t)1);
-    ok &= hipSuccess == A.alloc(&lm->forced, (size_t)G * (1 + c.dep_q));
-    ok &= hipSuccess == A.alloc(&lm->use_forced, (size_t)1);
-    ok &= hipSuccess == A.alloc(&lm->rng, (size_t)2);
-    // the nucleus table rides behind the row table (k_sample_nucleus finds it at rows + G): whole RowSamp entries, so that the
-    // snapshot of a stream without the nucleus kernels keeps its size
-    const size_t top_p_entries = lm->nucleus_on ? ((size_t)G * sizeof(RowTopP) + sizeof(RowSamp) - 1) / sizeof(RowSamp) : 0;
-    ok &= hipSuccess == A.alloc(&lm->rowtab, (size_t)G + top_p_entries);
-    ok &= hipSuccess == A.alloc(&lm->thist, (size_t)G * MMI_TEXT_HIST);
-    lm->tts = nullptr;
-    lm->tts_stride = 0;
-    if (lm->tts_on) {
-        lm->tts_stride = MMI_TTS_HDR + 2 * lm->tts_max_tokens + 3 * lm->tts_max_entries + 1 + (1 + c.dep_q) * lm->tts_max_prefix;
-        ok &= hipSuccess == A.alloc(&lm->tts, (size_t)G * lm->tts_stride);
-    }
-    lm->row_slot = nullptr;
-    lm->lora_t = nullptr;
-    size_t lora_t_elems = 0;
-    if (lm->lora_on) {
-        const int SR = lm->lora_S * lm->lora_R;
-        lora_t_elems = (size_t)mmi_cdiv(B, lm->T) * (SR / mmi_kstep(lm->T)) * 512;
-        ok &= hipSuccess == A.alloc(&lm->row_slot, (size_t)G);
-        ok &= hipSuccess == A.alloc(&lm->lora_t, lora_t_elems);
-    }
-    if (!ok) return fail(mmi_fail(MMI_ERR_HIP, "out of device memory (LM streaming state)"));
-    if (lm->lora_on) {      // every row without an adapter; the padding rows of t are never written and must read as zero
-        MMI_LAUNCH(k_fill_i32, mmi_cdiv(G, 256), 256, 0, s, lm->row_slot, -1, (long)G);
-        MMI_HIP_CHECK(hipMemsetAsync(lm->lora_t, 0, lora_t_elems * sizeof(uint16_t), s));
-        lm->row_slot_h.assign(G, -1);
-    }
-    MMI_HIP_CHECK(hipMemsetAsync(lm->exec, 1, G, s));
-    MMI_HIP_CHECK(hipMemsetAsync(lm->offsets, 0, G * sizeof(long), s));
-    if (guided) MMI_HIP_CHECK(hipMemsetAsync(lm->offsets_m, 0, B * sizeof(long), s));
-    if (lm->masked_until) {   // host int64[batch] (LMGen(cfg_is_masked_until=[...]), lm.py:637-640)
-        std::vector<int> mu(G);
-        for (int i = 0; i < G; ++i) mu[i] = (int)guide->cfg_is_masked_until[i];
-        MMI_HIP_CHECK(hipMemcpy(lm->masked_until, mu.data(), G * sizeof(int), hipMemcpyHostToDevice));
-    }
-    if (lm->cond) MMI_HIP_CHECK(hipMemcpyAsync(lm->cond, guide->condition_sum, (size_t)B * d * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
-    MMI_LAUNCH(k_fill_i32, mmi_cdiv(G * lm->NC * lm->CT, 256), 256, 0, s, lm->cache, -2, (long)G * lm->NC * lm->CT);   // lm.py:608-613
-    // every plane of the ring, a 4-bit ring's scale planes included: the attention reads rows past the valid length with p = 0, so
-    // they must decode to finite values - scale byte 0 is the factor 0.0f, 255 would be Inf (Inf * 0 = NaN).  A snapshot
-    // (mmi_lm_state_save / load) is the whole arena and so carries both planes.
-    MMI_HIP_CHECK(hipMemsetAsync(lm->kc, 0, kvn * sizeof(uint16_t), s));
-    MMI_HIP_CHECK(hipMemsetAsync(lm->vc, 0, kvn * sizeof(uint16_t), s));
-    MMI_HIP_CHECK(hipMemsetAsync(lm->attn_done, 0, (size_t)B * H * sizeof(unsigned), s));
-    MMI_HIP_CHECK(hipMemsetAsync(lm->dkc, 0, dkvn * sizeof(uint16_t), s));
-    MMI_HIP_CHECK(hipMemsetAsync(lm->dvc, 0, dkvn * sizeof(uint16_t), s));
-    MMI_HIP_CHECK(hipMemsetAsync(lm->use_noise, 0, sizeof(int), s));
-    lm->noise_on = false;
-    MMI_HIP_CHECK(hipMemsetAsync(lm->use_forced, 0, sizeof(int), s));
-    lm->forced_armed = false;
-    MMI_HIP_CHECK(hipMemsetAsync(lm->rowtab, 0, ((size_t)G + top_p_entries) * sizeof(RowSamp), s));   // every row inactive
+    lm->act8 = act8_of(lm);
+    lm->tts_stride = lm->tts_on ? MMI_TTS_HDR + 2 * lm->tts_max_tokens + 3 * lm->tts_max_entries + 1 + (1 + c.dep_q) * lm->tts_max_prefix : 0;
+    lm->ring = kv_ring_of(c, B);
+    state_table(lm, guide, guided, lm->st_table);
+    int rc = alloc_table(lm->st, lm->st_table, 0, s, "LM streaming state");
+    if (rc) return fail(rc);
+    if (!guided) lm->offsets_m = lm->offsets;
     lm->nucleus_live = lm->nucleus_on;
     lm->row_top_p.assign(lm->nucleus_live ? G : 0, RowTopP{lm->top_p, lm->top_p_text});   // every session starts with the handle's values
-    if (lm->nucleus_live)
-        MMI_HIP_CHECK(hipMemcpyAsync(lm->rowtab + G, lm->row_top_p.data(), (size_t)G * sizeof(RowTopP), hipMemcpyHostToDevice, s));
-    MMI_HIP_CHECK(hipMemsetAsync(lm->thist, 0, (size_t)G * MMI_TEXT_HIST * sizeof(int), s));
+    // the host's mirrors of what the fills wrote
+    lm->noise_on = lm->forced_armed = false;
     lm->row_active.assign(G, 0);
-    if (lm->tts) {          // no session has a script: every header word 0
-        MMI_HIP_CHECK(hipMemsetAsync(lm->tts, 0, (size_t)G * lm->tts_stride * sizeof(int), s));
-        if (hipHostMalloc((void**)&lm->tts_stage, (size_t)G * lm->tts_stride * sizeof(int), 0) != hipSuccess) {
-            lm->tts_stage = nullptr;
-            return fail(mmi_fail(MMI_ERR_HIP, "out of pinned host memory (TTS script staging)"));
+    if (lm->row_slot) lm->row_slot_h.assign(G, -1);
+    auto rest = [&]() -> int {      // what is left of the start; a failure leaves through fail() like every other
+        // the starts that need a host image or a copy
+        if (lm->masked_until) {   // host int64[batch] (LMGen(cfg_is_masked_until=[...]), lm.py:637-640)
+            std::vector<int> mu(G);
+            for (int i = 0; i < G; ++i) mu[i] = (int)guide->cfg_is_masked_until[i];
+            MMI_HIP_CHECK(hipMemcpy(lm->masked_until, mu.data(), G * sizeof(int), hipMemcpyHostToDevice));
         }
-        lm->tts_stage_ev.assign(G, nullptr);
-        lm->tts_stage_used.assign(G, 0);
-        for (int i = 0; i < G; ++i) MMI_HIP_CHECK(hipEventCreateWithFlags(&lm->tts_stage_ev[i], hipEventDisableTiming));
-    }
-    {   // packed activations: the padding rows / columns of a fragment are never written and must read as zero
-        struct { uint16_t* p; int f; int T; } pk[] = {{lm->x, d, lm->T}, {lm->xn, d, lm->T}, {lm->att, d, lm->T}, {lm->hb, c.ffn_hidden, lm->T},
-                                                      {lm->tout, d, lm->T}, {lm->dx, dd, lm->Td}, {lm->dxn, dd, lm->Td}, {lm->datt, dd, lm->Td},
-                                                      {lm->dhb, c.depformer_ffn_hidden, lm->Td}};
-        for (auto& e : pk) MMI_HIP_CHECK(hipMemsetAsync(e.p, 0, packed_elems_t(lm, e.T, e.f) * sizeof(uint16_t), s));
-    }
-    if (lm->act8) {   // the int8 operands: like their bf16 twins, padding rows / k-steps are never written and must read as zero
-        const size_t mtiles = (size_t)mmi_cdiv(B, lm->T), rows = mtiles * lm->T;
-        auto qbytes = [&](int features) { return mtiles * (size_t)(packed_ksteps(lm, features) / 2) * 1024; };
-        struct { uint8_t* p; int f; } qk[] = {{lm->xnq, d}, {lm->attq, d}, {lm->hbq, c.ffn_hidden > c.depformer_ffn_hidden ? c.ffn_hidden : c.depformer_ffn_hidden},
-                                              {lm->toutq, d}, {lm->dxnq, dd > 0 ? dd : 8}};
-        for (auto& e : qk) MMI_HIP_CHECK(hipMemsetAsync(e.p, 0, qbytes(e.f), s));
-        for (float* p : {lm->sx_xn, lm->sx_tout, lm->sx_dxn, lm->sx_att, lm->sx_hb}) MMI_HIP_CHECK(hipMemsetAsync(p, 0, rows * sizeof(float), s));
-    }
-    MMI_HIP_CHECK(hipMemsetAsync(lm->text_tok, 0, G * sizeof(int), s));
-    MMI_HIP_CHECK(hipMemsetAsync(lm->audio_tok, 0, (size_t)G * c.dep_q * sizeof(int), s));
-    unsigned long long r0[2] = {sampling->seed, 0ull};
-    MMI_HIP_CHECK(hipMemcpyAsync(lm->rng, r0, sizeof(r0), hipMemcpyHostToDevice, s));
-    {   // every session starts with the stream's coefficient and, on a cross-attention model, the start's length
-        std::vector<float> cf(G, lm->cfg_coef);
+        std::vector<float> cf(G, lm->cfg_coef);    // every session starts with the stream's coefficient
         MMI_HIP_CHECK(hipMemcpy(lm->coefs, cf.data(), G * sizeof(float), hipMemcpyHostToDevice));
-    }
-    if (lm->xlen) MMI_LAUNCH(k_fill_i32, mmi_cdiv(B, 256), 256, 0, s, lm->xlen, lm->cross_len, (long)B);
-    MMI_CHECK_LAUNCH();
-    int rc = 0;
-    if (lm->xkv) {
-        const uint16_t* src = reinterpret_cast<const uint16_t*>(guide->condition_cross);
-        if (lm->cross_cap == lm->cross_len) rc = project_cross_source(lm, src, 0, B * lm->cross_len, s);
-        else {      // slots [cross_len, cap) of a row are never read before mmi_lm_set_row_condition fills them: zero for the snapshot's sake
-            MMI_HIP_CHECK(hipMemsetAsync(lm->xkv, 0, (size_t)c.num_layers * B * lm->cross_cap * 2 * d * sizeof(uint16_t), s));
-            for (int r = 0; r < B && !rc; ++r)
+        unsigned long long r0[2] = {sampling->seed, 0ull};
+        MMI_HIP_CHECK(hipMemcpyAsync(lm->rng, r0, sizeof(r0), hipMemcpyHostToDevice, s));
+        if (lm->nucleus_live)
+            MMI_HIP_CHECK(hipMemcpyAsync(lm->rowtab + G, lm->row_top_p.data(), (size_t)G * sizeof(RowTopP), hipMemcpyHostToDevice, s));
+        if (lm->cond) MMI_HIP_CHECK(hipMemcpyAsync(lm->cond, guide->condition_sum, (size_t)B * d * sizeof(uint16_t), hipMemcpyDeviceToDevice, s));
+        if (lm->tts) {
+            if (hipHostMalloc((void**)&lm->tts_stage, (size_t)G * lm->tts_stride * sizeof(int), 0) != hipSuccess) {
+                lm->tts_stage = nullptr;
+                return mmi_fail(MMI_ERR_HIP, "out of pinned host memory (TTS script staging)");
+            }
+            lm->tts_stage_ev.assign(G, nullptr);
+            lm->tts_stage_used.assign(G, 0);
+            for (int i = 0; i < G; ++i) MMI_HIP_CHECK(hipEventCreateWithFlags(&lm->tts_stage_ev[i], hipEventDisableTiming));
+        }
+        int rc = 0;
+        if (lm->xkv) {      // the cross source projection: all rows at once, or row by row into a capacity above the start's length
+            const uint16_t* src = reinterpret_cast<const uint16_t*>(guide->condition_cross);
+            if (lm->cross_cap == lm->cross_len) rc = project_cross_source(lm, src, 0, B * lm->cross_len, s);
+            for (int r = 0; lm->cross_cap != lm->cross_len && r < B && !rc; ++r)
                 rc = project_cross_source(lm, src + (size_t)r * lm->cross_len * d, (size_t)r * lm->cross_cap, lm->cross_len, s);
         }
-        if (rc) return fail(rc);
-    }
-    rc = build_program(lm);
-    if (rc) return fail(rc);
-    if (lm->prefill_rows > 0 && (rc = prefill_alloc(lm, s))) return fail(rc);
-    MMI_HIP_CHECK(hipStreamSynchronize(s));
+        if (!rc) rc = build_program(lm);
+        if (!rc && lm->prefill_rows > 0) rc = prefill_alloc(lm, s);
+        if (rc) return rc;
+        MMI_HIP_CHECK(hipStreamSynchronize(s));
+        return MMI_OK;
+    };
+    if ((rc = rest())) return fail(rc);
     if (lm->knobs.debug_trace) {
         static int session = 0;
         lm->trace_name = lm->knobs.debug_trace_prefix + "." + std::to_string(session++);
@@ -2723,10 +2720,11 @@ extern "C" int mmi_lm_streaming_stop(mmi_lm* lm) {
     lm->prog.clear();
     lm->st.release();
     lm->pf_mem.release();
-    lm->sc = {};
-    lm->tts = nullptr;
-    lm->row_slot = nullptr;
-    lm->lora_t = nullptr;
+    for (BufTable* t : {&lm->st_table, &lm->pf_table}) {      // no member keeps pointing into the freed arenas
+        for (BufDecl& e : *t) *e.slot = nullptr;
+        t->clear();
+    }
+    lm->offsets_m = nullptr;                                  // (the alias of `offsets` on a stream without guidance)
     lm->row_slot_h.clear();
     lm->row_top_p.clear();
     lm->nucleus_live = false;
@@ -3511,15 +3509,13 @@ extern "C" int64_t mmi_lm_debug_kv_ring(mmi_lm* lm, int32_t layer, int32_t which
     const mmi_lm_cfg& c = lm->cfg;
     if (layer < 0 || layer >= c.num_layers || (which != 0 && which != 1))
         return (int64_t)mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_kv_ring: layer must be a temporal layer, which 0 (keys) or 1 (values)");
-    const int kvf = kv_form(c.kv_cache_dtype);
-    const size_t elems = (size_t)lm->batch * c.num_heads * c.context * (c.dim / c.num_heads);
-    const size_t layer_u16 = kv_layer_u16(kvf, elems);
-    const int64_t want = kvf == 2 ? (int64_t)(elems / 2 + elems / 16) : (int64_t)(layer_u16 * sizeof(uint16_t));   // without the layer's padding
+    const KvRing& r = lm->ring;
+    const int64_t want = (int64_t)(r.codes_bytes + (r.form == 2 ? r.elems / 16 : 0));   // without the layer's padding
     if (!dst) return want;
     if (nbytes != want)
         return (int64_t)mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_kv_ring: the buffer holds " + std::to_string(nbytes) + " bytes, the layer's ring " + std::to_string(want));
     hipStream_t s = (hipStream_t)stream;
-    const uint16_t* src = (which == 0 ? lm->kc : lm->vc) + (size_t)layer * layer_u16;
+    const uint16_t* src = (which == 0 ? lm->kc : lm->vc) + (size_t)layer * r.layer_u16;
     hipError_t e = hipMemcpyAsync(dst, src, (size_t)want, hipMemcpyDeviceToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return (int64_t)mmi_fail(MMI_ERR_HIP, std::string("mmi_lm_debug_kv_ring: ") + hipGetErrorString(e));
