@@ -705,6 +705,44 @@ GemmArgs rows_group_view(const GemmArgs& a_in, int r0, int rows) {
     return a;
 }
 
+// k-steps of a packed activation buffer with `features` columns (even when the linears are int8: their weight entries
+// carry k-step pairs, and the padding k-step reads as zero)
+int packed_ksteps_t(const mmi_lm* lm, int T, int features) {
+    const int ks = mmi_cdiv(features, mmi_kstep(T));
+    if (lm->q8 == 4) return 4 * mmi_cdiv(ks, 4);       // MXFP4 entries carry four k-steps
+    return lm->q8 >= 1 ? 2 * mmi_cdiv(ks, 2) : ks;
+}
+int packed_ksteps(const mmi_lm* lm, int features) { return packed_ksteps_t(lm, lm->T, features); }
+// number of bf16 elements of a packed activation buffer with `features` columns
+size_t packed_elems_t(const mmi_lm* lm, int T, int features) {
+    return (size_t)mmi_cdiv(lm->batch, T) * packed_ksteps_t(lm, T, features) * 512;
+}
+size_t packed_elems(const mmi_lm* lm, int features) { return packed_elems_t(lm, lm->T, features); }
+
+// Where a linear writes: `features` columns, packed at the linear's tile (the operand of the next linear) or row-major with leading
+// dim `features`.  GemmOut{}: the epilogue has no such output (split-K partials, the temporal in_proj's ring and q)
+struct GemmOut { uint16_t* out = nullptr; int features = 0; bool packed = false; };
+
+// THE start of every GemmArgs: all zero but the operand x (packed at tile T), the epilogue, the rows B - tok_rows sessions and
+// their guidance twins - and the output geometry
+GemmArgs gemm_args(const mmi_lm* lm, int T, const void* x, int epi, int B, int tok_rows, const GemmOut& o, const uint16_t* resid = nullptr) {
+    GemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.xp = reinterpret_cast<const u32x4*>(x); a.out = o.out; a.resid = resid; a.epi = epi; a.B = B; a.tok_rows = tok_rows;
+    a.out_mode = o.packed ? MMI_OUT_PACKED : MMI_OUT_ROWMAJOR;
+    a.out_ld = o.features;
+    a.out_ksteps = packed_ksteps_t(lm, T, o.features);
+    return a;
+}
+
+// THE binding of a packed weight: every member of GemmArgs that is a property of the weight alone (a new weight format adds its
+// members here).  wq is not: int8 activations make it a property of the launch (launch_gemm, the fused forms)
+void bind_weight(GemmArgs& a, const GemmW& g) {
+    a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT;
+    a.wscale = g.scale; a.wscb = g.scb; a.ws4 = g.s4; a.gate_rows = g.gate ? g.N : 0;
+    a.xinv = g.xinv;
+}
+
 // The shrink launch in front of an adapted linear g: t = bf16(A_all x) for the columns of each row's own slot (MMI_EPI_LORA_T),
 // packed as the operand of g's tail.  An ordinary k_gemm_xp launch of S * R / T n-tiles over the linear's K: the waves of a
 // workgroup split K as for any GEMM, and with 4..32 n-tiles the row octets of a tile are shared out (plan_osplit)
@@ -715,11 +753,10 @@ int launch_lora_shrink(mmi_lm* lm, hipStream_t s, const GemmW& g, const u32x4* x
     GemmW ga;
     ga.wp = it->second.a; ga.N = SR; ga.K = g.K; ga.NT = SR / g.T; ga.KSTEPS = g.KSTEPS; ga.T = g.T;
     ga.bytes = (size_t)ga.NT * ga.KSTEPS * 1024;
-    GemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.wp = ga.wp; a.xp = xp; a.out = t; a.B = B; a.N = SR; a.KSTEPS = ga.KSTEPS; a.NT = ga.NT;
-    a.out_mode = MMI_OUT_PACKED; a.out_ld = SR; a.out_ksteps = SR / mmi_kstep(g.T);
-    a.epi = MMI_EPI_LORA_T; a.row_slot = row_slot; a.tok_rows = tok_rows; a.lora_rank = lm->lora_R;
+    // (t's k-steps are whole: SR / mmi_kstep(g.T) - a slot is a multiple of 32 columns and an adapter handle's linears are bf16)
+    GemmArgs a = gemm_args(lm, g.T, xp, MMI_EPI_LORA_T, B, tok_rows, {t, SR, true});
+    a.wp = ga.wp; a.N = SR; a.KSTEPS = ga.KSTEPS; a.NT = ga.NT;        // a bank, not a linear of the model: no scales, no xinv
+    a.row_slot = row_slot; a.lora_rank = lm->lora_R;
     const GemmPlan p = plan_gemm(lm->knobs, ga, false);
     a.osplit = plan_osplit(lm->knobs, ga, p, a.epi, g.T);
     const dim3 groups(ga.NT * (a.osplit > 1 ? a.osplit : 1), 1);
@@ -741,11 +778,8 @@ int launch_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, GemmArgs a, bool is_d
         }
         return MMI_OK;
     }
-    a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT;
-    a.wscale = g.scale; a.wscb = g.scb; a.gate_rows = g.gate ? g.N : 0;
-    if (!lora_t) a.ws4 = g.s4;
+    bind_weight(a, g);                                         // (an adapter's lora_wp goes over ws4 below: bf16 linears have none)
     a.wq = (g.wq == 1 && a.wq >= 3) ? a.wq : g.wq;             // int8 linears: 3 / 4 = int8 activations (set by the program builder)
-    a.xinv = g.xinv;
     const int mt = mmi_cdiv(a.B, g.T);
     const MmiKnobs& k = lm->knobs;
     const GemmPlan p = plan_gemm(k, g, a.epi == MMI_EPI_PARTIAL);
@@ -807,25 +841,20 @@ int launch_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, GemmArgs a, bool is_d
 // int8 activations (see mmi_lm::act8)
 bool act8_of(const mmi_lm* lm) { return lm->q8 == 1 && !lm->cfg.cross_attention && !lm->knobs.q8_act_bf16; }
 
-// number of bf16 elements of a packed activation buffer with `features` columns
-// k-steps of a packed activation buffer with `features` columns (even when the linears are int8: their weight entries
-// carry k-step pairs, and the padding k-step reads as zero)
-int packed_ksteps_t(const mmi_lm* lm, int T, int features) {
-    const int ks = mmi_cdiv(features, mmi_kstep(T));
-    if (lm->q8 == 4) return 4 * mmi_cdiv(ks, 4);       // MXFP4 entries carry four k-steps
-    return lm->q8 >= 1 ? 2 * mmi_cdiv(ks, 2) : ks;
-}
-int packed_ksteps(const mmi_lm* lm, int features) { return packed_ksteps_t(lm, lm->T, features); }
-size_t packed_elems_t(const mmi_lm* lm, int T, int features) {
-    return (size_t)mmi_cdiv(lm->batch, T) * packed_ksteps_t(lm, T, features) * 512;
-}
-size_t packed_elems(const mmi_lm* lm, int features) { return packed_elems_t(lm, lm->T, features); }
-
-// x: packed activations.  out: packed with `out_features` columns (out_packed) or row-major with leading dim out_features.
 // MMI_EPI_DEP_QKV0 (the depth transformer's in_proj at micro-step 0): where its epilogue writes k / v (frame cache, position 0)
-struct DepKv { uint16_t* kc; uint16_t* vc; int H, Dh, steps; };
+struct DepKv { uint16_t* kc = nullptr; uint16_t* vc = nullptr; int H = 0, Dh = 0, steps = 0; };
 // int8 activations of one GEMM (lm->act8): `x` is the int8 operand Xq and sx its rows' absmax (wq 3)
 struct Q8 { int wq = 0; const float* sx = nullptr; };
+// What an op of the step program needs beyond the weight, the operand, the epilogue and the output: a caller names the members
+// its linear uses and leaves the rest alone
+struct GemmOpt {
+    const uint16_t* resid = nullptr;                                              // MMI_EPI_RESID: same geometry as the output
+    const uint16_t* emb = nullptr; const int* tok = nullptr; int tok_stride = 0;  // MMI_EPI_EMB: the table and each session's token
+    bool dominant = false;                                                        // the launch mmi_lm_profile_* times
+    DepKv kv;                                                                     // MMI_EPI_DEP_QKV0
+    const LmAttnArgs* ring = nullptr;      // MMI_EPI_ROPE_KV: the attention launch behind this in_proj - it reads the ring and q written here
+    Q8 q8;
+};
 
 // Adapter handles: the shrink launch of linear g on its packed operand xp, as an op of its own under the site `<site>.lora`.
 // Returns the packed t the linear's tail reads (launch_gemm's lora_t); null on a handle without adapters (nothing is added)
@@ -842,20 +871,22 @@ const u32x4* add_lora_shrink(mmi_lm* lm, const GemmW& g, const u32x4* xp) {
     return reinterpret_cast<const u32x4*>(t);
 }
 
-void add_gemm(mmi_lm* lm, const GemmW& g, const uint16_t* x, uint16_t* out, int out_features, bool out_packed, int epi,
-              const uint16_t* resid, const uint16_t* emb = nullptr, const int* tok = nullptr, int tok_stride = 0,
-              bool dominant = false, const DepKv* kv = nullptr, const Q8* q8 = nullptr) {
-    GemmArgs a;
-    memset(&a, 0, sizeof(a));
-    if (kv) { a.kc = kv->kc; a.vc = kv->vc; a.H = kv->H; a.Dh = kv->Dh; a.cap = kv->steps; }
-    if (q8) { a.wq = q8->wq; a.sx = q8->sx; }
-    a.xp = reinterpret_cast<const u32x4*>(x); a.out = out; a.epi = epi; a.resid = resid; a.emb = emb; a.tok = tok;
-    a.tok_stride = tok_stride; a.tok_rows = lm->gen_batch; a.B = lm->batch;
-    a.out_mode = out_packed ? MMI_OUT_PACKED : MMI_OUT_ROWMAJOR;
-    a.out_ld = out_features;
-    a.out_ksteps = packed_ksteps_t(lm, g.T, out_features);
+// One linear of the step program on the stream's rows: x = its packed operand (lm->act8: the int8 copy, with o.q8), then the
+// epilogue and where it writes.  An adapter handle's shrink launch goes first, as an op of its own (add_lora_shrink)
+void add_gemm(mmi_lm* lm, const GemmW& g, const void* x, int epi, const GemmOut& out, const GemmOpt& o = {}) {
+    GemmArgs a = gemm_args(lm, g.T, x, epi, lm->batch, lm->gen_batch, out, o.resid);
+    a.kc = o.kv.kc; a.vc = o.kv.vc; a.H = o.kv.H; a.Dh = o.kv.Dh; a.cap = o.kv.steps;
+    a.wq = o.q8.wq; a.sx = o.q8.sx;
+    a.emb = o.emb; a.tok = o.tok; a.tok_stride = o.tok_stride;
+    if (epi == MMI_EPI_PARTIAL) a.partial = lm->partial;
+    if (const LmAttnArgs* r = o.ring) {       // RoPE + ring-KV write in the epilogue
+        a.qrot = r->qrot; a.kc = r->kc; a.vc = r->vc; a.offsets = r->offsets; a.H = r->H; a.Dh = r->Dh; a.cap = r->cap;
+        a.max_period = r->max_period; a.rope = lm->rope; a.kv8 = lm->ring.form;
+        if (a.kv8 == 2) a.kv_soff = r->kv_soff;
+    }
     const u32x4* lt = add_lora_shrink(lm, g, a.xp);
-    GemmW gw = g;
+    const GemmW gw = g;
+    const bool dominant = o.dominant;
     lm->prog.add([lm, gw, a, dominant, lt](hipStream_t s) { return launch_gemm(lm, s, gw, a, dominant, lt); }, (long)g.bytes);
 }
 
@@ -910,10 +941,8 @@ struct DepAttnOutProj { GemmArgs a; int groups, waves; };
 DepAttnOutProj plan_dep_attn_out_proj(const mmi_lm* lm, const GemmW& g, uint16_t* x, int features, int B, int tok_rows) {
     DepAttnOutProj f;
     GemmArgs& a = f.a;
-    memset(&a, 0, sizeof(a));
-    a.out = x; a.epi = MMI_EPI_RESID; a.resid = x; a.B = B; a.tok_rows = tok_rows;
-    a.out_mode = MMI_OUT_PACKED; a.out_ld = features; a.out_ksteps = packed_ksteps_t(lm, g.T, features);
-    a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT; a.wscale = g.scale; a.xinv = g.xinv;
+    a = gemm_args(lm, g.T, nullptr, MMI_EPI_RESID, B, tok_rows, {x, features, true}, x);     // (the operand is the attention's, in registers)
+    bind_weight(a, g);
     const GemmPlan p = plan_gemm(lm->knobs, g, false);
     a.osplit = plan_osplit(lm->knobs, g, p, a.epi, g.T);
     f.groups = g.NT * (a.osplit > 1 ? a.osplit : 1);
@@ -938,40 +967,43 @@ struct Pending { int P = 0; const float* sx = nullptr; const float* scb = nullpt
 
 // K-split GEMM whose partial sums (lm->partial) the following add_resid_rmsnorm folds into the residual stream.
 // Returns the partials, P = 0 when the GEMM is not split (then it applied the residual itself, in place on x).
-Pending add_gemm_resid(mmi_lm* lm, const GemmW& g, const uint16_t* in, uint16_t* x, int features, const Q8* q8 = nullptr) {
+Pending add_gemm_resid(mmi_lm* lm, const GemmW& g, const void* in, uint16_t* x, int features, Q8 q8 = {}) {
     const GemmPlan p = plan_gemm(lm->knobs, g, true);
+    GemmOpt o;
+    o.q8 = q8;
     if (p.ksplit <= 1) {
-        add_gemm(lm, g, in, x, features, true, MMI_EPI_RESID, x, nullptr, nullptr, 0, false, nullptr, q8);
+        o.resid = x;
+        add_gemm(lm, g, in, MMI_EPI_RESID, {x, features, true}, o);
         return Pending{};
     }
-    GemmArgs a;
-    memset(&a, 0, sizeof(a));
-    if (q8) { a.wq = q8->wq; a.sx = q8->sx; }
-    a.xp = reinterpret_cast<const u32x4*>(in); a.epi = MMI_EPI_PARTIAL; a.partial = lm->partial; a.B = lm->batch;
-    const u32x4* lt = add_lora_shrink(lm, g, a.xp);
-    GemmW gw = g;
-    lm->prog.add([lm, gw, a, lt](hipStream_t s) { return launch_gemm(lm, s, gw, a, false, lt); }, (long)g.bytes);
+    add_gemm(lm, g, in, MMI_EPI_PARTIAL, {}, o);
     Pending pd;
     pd.P = p.ksplit;
-    if (q8 && q8->wq == 3 && g.wq == 1) { pd.sx = q8->sx; pd.scb = g.scb; }
+    if (q8.wq == 3 && g.wq == 1) { pd.sx = q8.sx; pd.scb = g.scb; }
     return pd;
 }
 
-// x (+= the P pending split-K partials), y = rms_norm(x) * alpha
-// yq / sx: also store the row quantised row-wise to int8 (+ its absmax) for the int8 linears that read it (lm->act8)
+// threads of a launch with one workgroup per row of D features: one 16-byte piece per thread where the row allows it
+int row_threads(int D) {
+    const int nth = mmi_cdiv(D / 8, 64) * 64;
+    return nth > 1024 ? 1024 : nth;
+}
+
+// THE launch of k_resid_rmsnorm: x (+= the pending split-K partials, held in `partial`), y = rms_norm(x) * alpha, rows packed at
+// `tile` with `ksteps` k-steps.  yq / sx: also store the row quantised row-wise to int8 (+ its absmax) for the int8 linears that
+// read it (lm->act8)
+int launch_rmsnorm(hipStream_t s, int rows, uint16_t* x, const float* partial, Pending pd, const uint16_t* alpha, uint16_t* y, int D, int tile,
+                   int ksteps, uint8_t* yq = nullptr, float* sx = nullptr) {
+    MMI_LAUNCH(k_resid_rmsnorm, rows, row_threads(D), 0, s, x, partial, pd.P, rows, alpha, y, D, tile, ksteps, 1e-8f, yq, sx, pd.sx, pd.scb);
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+
 void add_resid_rmsnorm(mmi_lm* lm, uint16_t* x, Pending pd, const uint16_t* alpha, uint16_t* y, int D, uint8_t* yq = nullptr, float* sx = nullptr,
                        int tile = 0) {
     const int B = lm->batch, T = tile ? tile : lm->T, ksteps = packed_ksteps_t(lm, T, D);
     const float* partial = lm->partial;
-    const int P = pd.P;
-    const float *psx = pd.sx, *pscb = pd.scb;
-    lm->prog.add([=](hipStream_t s) {
-        int nth = mmi_cdiv(D / 8, 64) * 64;            // one 16-byte piece per thread where the row allows it
-        if (nth > 1024) nth = 1024;
-        MMI_LAUNCH(k_resid_rmsnorm, B, nth, 0, s, x, partial, P, B, alpha, y, D, T, ksteps, 1e-8f, yq, sx, psx, pscb);
-        MMI_CHECK_LAUNCH();
-        return (int)MMI_OK;
-    });
+    lm->prog.add([=](hipStream_t s) { return launch_rmsnorm(s, B, x, partial, pd, alpha, y, D, T, ksteps, yq, sx); });
 }
 
 // parity tap (mmi_lm_set_hidden_taps; off in production: no op is added): the residual stream, row-major, into htap[which]
@@ -1057,34 +1089,25 @@ static int norm_fused_max(int wq) { return wq == 4 ? 16 : (wq ? 32 : 64); }
 // RMSNorm(x) * alpha fused into the GEMM (k_gemm_xp_norm) when a workgroup's 8 waves can hold the whole row slice in
 // registers (rows of <= 1024 features at the 32-wide tile: the depth transformer); otherwise norm kernel + GEMM.
 // lm->act8: the normalised row is quantised inside the GEMM (k_gemm_q8, fused) or by the norm launch
-void add_norm_gemm(mmi_lm* lm, const GemmW& g, uint16_t* x, const uint16_t* alpha, uint16_t* xn_scratch, int D, uint16_t* out,
-                   int out_features, bool out_packed, int epi, const DepKv* kv = nullptr) {
+void add_norm_gemm(mmi_lm* lm, const GemmW& g, uint16_t* x, const uint16_t* alpha, uint16_t* xn_scratch, int D, int epi, const GemmOut& out,
+                   const DepKv& kv = {}) {
     const bool a8 = lm->act8 && g.wq == 1;
     const int wq = a8 ? 3 : g.wq;
     const bool fuse = g.KSTEPS <= norm_fused_max(wq) && !lm->knobs.no_norm_fusion && mmi_cdiv(lm->batch, g.T) <= 2 &&   // k_gemm_rows has no fused norm
                       !lm->lora_on;                            // an adapter's shrink launch reads the materialised operand
     if (!fuse) {
-        if (a8) {
-            add_resid_rmsnorm(lm, x, Pending{}, alpha, xn_scratch, D, lm->dxnq, lm->sx_dxn, g.T);
-            Q8 q{3, lm->sx_dxn};
-            add_gemm(lm, g, reinterpret_cast<const uint16_t*>(lm->dxnq), out, out_features, out_packed, epi, nullptr, nullptr, nullptr, 0, false, kv, &q);
-            return;
-        }
-        add_resid_rmsnorm(lm, x, Pending{}, alpha, xn_scratch, D, nullptr, nullptr, g.T);
-        add_gemm(lm, g, xn_scratch, out, out_features, out_packed, epi, nullptr, nullptr, nullptr, 0, false, kv);
+        GemmOpt o;
+        o.kv = kv;
+        if (a8) o.q8 = Q8{3, lm->sx_dxn};
+        add_resid_rmsnorm(lm, x, Pending{}, alpha, xn_scratch, D, a8 ? lm->dxnq : nullptr, a8 ? lm->sx_dxn : nullptr, g.T);
+        add_gemm(lm, g, a8 ? (const void*)lm->dxnq : xn_scratch, epi, out, o);
         return;
     }
-    GemmArgs a;
-    memset(&a, 0, sizeof(a));
-    if (kv) { a.kc = kv->kc; a.vc = kv->vc; a.H = kv->H; a.Dh = kv->Dh; a.cap = kv->steps; }
-    a.xp = reinterpret_cast<const u32x4*>(x); a.out = out; a.epi = epi; a.B = lm->batch;
-    a.out_mode = out_packed ? MMI_OUT_PACKED : MMI_OUT_ROWMAJOR;
-    a.out_ld = out_features;
-    a.out_ksteps = packed_ksteps_t(lm, g.T, out_features);
+    GemmArgs a = gemm_args(lm, g.T, x, epi, lm->batch, lm->gen_batch, out);
+    a.kc = kv.kc; a.vc = kv.vc; a.H = kv.H; a.Dh = kv.Dh; a.cap = kv.steps;
     a.alpha = alpha; a.D = D; a.eps = 1e-8f;
-    a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT;
-    a.wscale = g.scale; a.wscb = g.scb; a.ws4 = g.s4; a.gate_rows = g.gate ? g.N : 0;
-    a.wq = wq; a.xinv = g.xinv;
+    bind_weight(a, g);
+    a.wq = wq;
     a.osplit = 1;
     const int T = g.T, mt = mmi_cdiv(lm->batch, g.T), NT = g.NT * (a.osplit > 1 ? a.osplit : 1);
     const long gbytes = (long)g.bytes;
@@ -1099,9 +1122,7 @@ void add_norm_gemm(mmi_lm* lm, const GemmW& g, uint16_t* x, const uint16_t* alph
 void add_quant_rows(mmi_lm* lm, const uint16_t* xp, uint8_t* xq, float* sx, int features, int tile = 0) {
     const int B = lm->batch, T = tile ? tile : lm->T, ksteps = packed_ksteps_t(lm, T, features);
     lm->prog.add([=](hipStream_t s) {
-        int nth = mmi_cdiv(features / 8, 64) * 64;
-        if (nth > 1024) nth = 1024;
-        MMI_LAUNCH(k_quant_rows_i8, B, nth, 0, s, xp, B, features, T, ksteps, xq, sx);
+        MMI_LAUNCH(k_quant_rows_i8, B, row_threads(features), 0, s, xp, B, features, T, ksteps, xq, sx);
         MMI_CHECK_LAUNCH();
         return (int)MMI_OK;
     });
@@ -1110,25 +1131,20 @@ void add_quant_rows(mmi_lm* lm, const uint16_t* xp, uint8_t* xq, float* sx, int 
 // An int8 linear of the depth transformer on a bf16 input WITHOUT a norm in front (out_proj, linear_out, the logits heads) under
 // lm->act8: the row quantisation fused into the GEMM (k_gemm_q8, rows of <= 8 * 11 entries); longer rows: quantisation launch
 // (into the gated tensor's scratch) + the plain int8 x int8 GEMM.
-void add_q8_gemm(mmi_lm* lm, const GemmW& g, const uint16_t* x, int in_features, uint16_t* out, int out_features, bool out_packed, int epi,
-                 const uint16_t* resid) {
+void add_q8_gemm(mmi_lm* lm, const GemmW& g, const uint16_t* x, int in_features, int epi, const GemmOut& out, const uint16_t* resid = nullptr) {
     const int T = g.T, mt = mmi_cdiv(lm->batch, g.T);
     const int kmax = q8_fused_kmax(g);
     if (!kmax || lm->knobs.no_norm_fusion) {
         add_quant_rows(lm, x, lm->hbq, lm->sx_hb, in_features, g.T);
-        Q8 q{3, lm->sx_hb};
-        add_gemm(lm, g, reinterpret_cast<const uint16_t*>(lm->hbq), out, out_features, out_packed, epi, resid, nullptr, nullptr, 0, false, nullptr, &q);
+        GemmOpt o;
+        o.resid = resid;
+        o.q8 = Q8{3, lm->sx_hb};
+        add_gemm(lm, g, lm->hbq, epi, out, o);
         return;
     }
-    GemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xp = reinterpret_cast<const u32x4*>(x); a.out = out; a.epi = epi; a.resid = resid; a.B = lm->batch; a.tok_rows = lm->gen_batch;
-    a.out_mode = out_packed ? MMI_OUT_PACKED : MMI_OUT_ROWMAJOR;
-    a.out_ld = out_features;
-    a.out_ksteps = packed_ksteps_t(lm, g.T, out_features);
-    a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT;
-    a.wscale = g.scale; a.wscb = g.scb; a.gate_rows = g.gate ? g.N : 0;
-    a.wq = 3; a.xinv = g.xinv;
+    GemmArgs a = gemm_args(lm, g.T, x, epi, lm->batch, lm->gen_batch, out, resid);
+    bind_weight(a, g);
+    a.wq = 3;
     // few n-tiles (the N = 1024 linears: 32 tiles for 256 CUs): share a tile's row octets out over several workgroups, as
     // plan_osplit does for the bf16 form of these GEMMs
     a.osplit = q8_fused_osplit(lm->knobs, g, epi, T);
@@ -1380,6 +1396,9 @@ int build_program(mmi_lm* lm) {
     const int kvf = lm->ring.form;
     const size_t kv_layer = lm->ring.layer_u16;  // in uint16 units: an fp8 ring is half as large
     Pending pending;   // split-K partials of the previous linear_out still to be folded into x
+    // the int8 linears that read the normalised rows (in_proj, ffn_in) take their int8 copy
+    const void* xn_in = a8 ? (const void*)lm->xnq : lm->xn;
+    const Q8 xn_q8 = a8 ? Q8{3, lm->sx_xn} : Q8{};
     for (int l = 0; l < c.num_layers; ++l) {
         const LayerW& L = lm->layers[l];
         P.site("L.norm1");
@@ -1394,16 +1413,10 @@ int build_program(mmi_lm* lm) {
         a.kv_soff = (long)lm->ring.scale_off;
         P.site("L.in_proj");
         {   // in_proj with RoPE + ring-KV write in its epilogue
-            GemmArgs ga;
-            memset(&ga, 0, sizeof(ga));
-            ga.xp = reinterpret_cast<const u32x4*>(lm->xn); ga.epi = MMI_EPI_ROPE_KV; ga.B = B;
-            if (a8) { ga.xp = reinterpret_cast<const u32x4*>(lm->xnq); ga.sx = lm->sx_xn; ga.wq = 3; }
-            ga.qrot = a.qrot; ga.kc = a.kc; ga.vc = a.vc; ga.offsets = lm->offsets_m; ga.H = H; ga.Dh = Dh; ga.cap = c.context; ga.kv8 = kvf;
-            ga.max_period = c.max_period; ga.rope = lm->rope;
-            if (kvf == 2) ga.kv_soff = a.kv_soff;
-            const u32x4* lt = add_lora_shrink(lm, L.in_proj, ga.xp);
-            GemmW gw = L.in_proj;
-            P.add([lm, gw, ga, lt](hipStream_t s) { return launch_gemm(lm, s, gw, ga, false, lt); }, (long)gw.bytes);
+            GemmOpt o;
+            o.ring = &a;
+            o.q8 = xn_q8;
+            add_gemm(lm, L.in_proj, xn_in, MMI_EPI_ROPE_KV, {}, o);
         }
         P.site("L.attn");
         const bool wave = attn_wave_kernel(lm->knobs);
@@ -1411,8 +1424,7 @@ int build_program(mmi_lm* lm) {
         P.site("L.out_proj");
         if (a8) {
             add_quant_rows(lm, lm->att, lm->attq, lm->sx_att, d);
-            Q8 q{3, lm->sx_att};
-            pending = add_gemm_resid(lm, L.out_proj, reinterpret_cast<const uint16_t*>(lm->attq), lm->x, d, &q);
+            pending = add_gemm_resid(lm, L.out_proj, lm->attq, lm->x, d, Q8{3, lm->sx_att});
         } else
         pending = add_gemm_resid(lm, L.out_proj, lm->att, lm->x, d);
         if (c.cross_attention) {   // x = x + cross_attention(norm_cross(x), src, src) (transformer.py:779-786)
@@ -1422,15 +1434,13 @@ int build_program(mmi_lm* lm) {
                 uint16_t *x = lm->x, *y = lm->xn; const float* partial = lm->partial;
                 const uint16_t *w = L.nx_w, *bb = L.nx_b;
                 P.add([=](hipStream_t s) {
-                    int nth = mmi_cdiv(d / 8, 64) * 64;
-                    if (nth > 1024) nth = 1024;
-                    MMI_LAUNCH(k_resid_layernorm, B, nth, 0, s, x, partial, Pn, B, w, bb, y, d, T, ksteps, 1e-5f);
+                    MMI_LAUNCH(k_resid_layernorm, B, row_threads(d), 0, s, x, partial, Pn, B, w, bb, y, d, T, ksteps, 1e-5f);
                     MMI_CHECK_LAUNCH();
                     return (int)MMI_OK;
                 });
             }
             P.site("L.cross_q");
-            add_gemm(lm, L.x_q, lm->xn, lm->qrot, d, false, MMI_EPI_STORE, nullptr);
+            add_gemm(lm, L.x_q, lm->xn, MMI_EPI_STORE, {lm->qrot, d});
             P.site("L.cross_attn");
             {
                 CrossAttnArgs ca;
@@ -1444,18 +1454,17 @@ int build_program(mmi_lm* lm) {
         P.site("L.norm2");
         add_resid_rmsnorm(lm, lm->x, pending, L.n2, lm->xn, d, a8 ? lm->xnq : nullptr, a8 ? lm->sx_xn : nullptr);
         P.site("L.ffn_in");
-        if (a8) {
-            Q8 qi{3, lm->sx_xn};
-            add_gemm(lm, L.ffn_in, reinterpret_cast<const uint16_t*>(lm->xnq), lm->hb, c.ffn_hidden, true, MMI_EPI_GATE, nullptr, nullptr, nullptr, 0,
-                     /*dominant=*/true, nullptr, &qi);
-            P.site("L.ffn_out");
-            add_quant_rows(lm, lm->hb, lm->hbq, lm->sx_hb, c.ffn_hidden);
-            Q8 qo{3, lm->sx_hb};
-            pending = add_gemm_resid(lm, L.ffn_out, reinterpret_cast<const uint16_t*>(lm->hbq), lm->x, d, &qo);
-            continue;
+        {
+            GemmOpt o;
+            o.dominant = true;
+            o.q8 = xn_q8;
+            add_gemm(lm, L.ffn_in, xn_in, MMI_EPI_GATE, {lm->hb, c.ffn_hidden, true}, o);
         }
-        add_gemm(lm, L.ffn_in, lm->xn, lm->hb, c.ffn_hidden, true, MMI_EPI_GATE, nullptr, nullptr, nullptr, 0, /*dominant=*/true);
         P.site("L.ffn_out");
+        if (a8) {
+            add_quant_rows(lm, lm->hb, lm->hbq, lm->sx_hb, c.ffn_hidden);
+            pending = add_gemm_resid(lm, L.ffn_out, lm->hbq, lm->x, d, Q8{3, lm->sx_hb});
+        } else
         pending = add_gemm_resid(lm, L.ffn_out, lm->hb, lm->x, d);
     }
     P.site("out_norm");
@@ -1463,17 +1472,17 @@ int build_program(mmi_lm* lm) {
     if (c.num_layers == 1) add_hidden_tap(lm, 0);
     add_hidden_tap(lm, 1);
     // the int8 linears that read transformer_out (text head, depformer_in) take its int8 copy
-    const uint16_t* tout_in = a8 ? reinterpret_cast<const uint16_t*>(lm->toutq) : lm->tout;
-    const Q8 q_tout{3, lm->sx_tout};
-    const Q8* qt = a8 ? &q_tout : nullptr;
+    const void* tout_in = a8 ? (const void*)lm->toutq : lm->tout;
+    GemmOpt from_tout;
+    if (a8) from_tout.q8 = Q8{3, lm->sx_tout};
     P.site("text_linear");
-    add_gemm(lm, lm->text_linear, tout_in, lm->text_logits, c.text_card_out, false, MMI_EPI_STORE, nullptr, nullptr, nullptr, 0, false, nullptr, qt);
+    add_gemm(lm, lm->text_linear, tout_in, MMI_EPI_STORE, {lm->text_logits, c.text_card_out}, from_tout);
     // depformer_in[k](transformer_out) for every micro-step in one launch; each sampler then adds its token's embedding row
     // and writes the next micro-step's input (lm.py:465-470) - 8 dependent launches less on the sequential chain
     const bool grouped = lm->dep_in_grouped && !lm->lora_on;     // (an adapter handle: one depformer_in, one bank, per micro-step)
     lm->op_depformer = P.ops.size();
     P.site("dep.in_all");
-    if (grouped) add_gemm(lm, lm->dep_in_all, tout_in, lm->dpre, lm->dep_nw * dd, false, MMI_EPI_STORE, nullptr, nullptr, nullptr, 0, false, nullptr, qt);
+    if (grouped) add_gemm(lm, lm->dep_in_all, tout_in, MMI_EPI_STORE, {lm->dpre, lm->dep_nw * dd}, from_tout);
     P.site("text_sample");
     // a demuxed text stream: the first input row is written by its own launch behind the sampler (and behind an on_text_hook,
     // which may mux a second token into the one sampled)
@@ -1524,11 +1533,18 @@ int build_program(mmi_lm* lm) {
     }
     // ---- depformer: dep_q sequential micro-steps
     const size_t dkv_layer = (size_t)B * Hd * c.dep_q * Dhd;
+    const GemmOut dx_out{lm->dx, dd, true};       // out_proj and linear_out: dx += linear(.), in place
+    GemmOpt onto_dx;
+    onto_dx.resid = lm->dx;
     for (int k = 0; k < c.dep_q; ++k) {
         const int* prev = k == 0 ? lm->text_tok : lm->audio_tok + (k - 1);
         const int prev_stride = k == 0 ? 1 : c.dep_q;
         P.site("dep.in");
-        if (!grouped) add_gemm(lm, lm->dep_in[k], tout_in, lm->dx, dd, true, MMI_EPI_EMB, nullptr, lm->dep_emb[k], prev, prev_stride, false, nullptr, qt);
+        if (!grouped) {
+            GemmOpt o = from_tout;
+            o.emb = lm->dep_emb[k]; o.tok = prev; o.tok_stride = prev_stride;
+            add_gemm(lm, lm->dep_in[k], tout_in, MMI_EPI_EMB, {lm->dx, dd, true}, o);
+        }
         for (int l = 0; l < c.depformer_num_layers; ++l) {
             const DepLayerW& L = lm->dep_layers[l];
             P.site("dep.in_proj");
@@ -1537,10 +1553,10 @@ int build_program(mmi_lm* lm) {
             // (bit-identical: 1 * v / 1; knobs.dep_attn0_launch keeps the launch)
             const bool skip_attn0 = k == 0 && Dhd % 8 == 0 && !lm->knobs.dep_attn0_launch;
             if (skip_attn0) {
-                DepKv kv{lm->dkc + l * dkv_layer, lm->dvc + l * dkv_layer, Hd, Dhd, c.dep_q};
-                add_norm_gemm(lm, L.in_proj[k], lm->dx, L.n1, lm->dxn, dd, lm->datt, dd, true, MMI_EPI_DEP_QKV0, &kv);
+                const DepKv kv{lm->dkc + l * dkv_layer, lm->dvc + l * dkv_layer, Hd, Dhd, c.dep_q};
+                add_norm_gemm(lm, L.in_proj[k], lm->dx, L.n1, lm->dxn, dd, MMI_EPI_DEP_QKV0, {lm->datt, dd, true}, kv);
             } else
-            add_norm_gemm(lm, L.in_proj[k], lm->dx, L.n1, lm->dxn, dd, lm->dqkv, 3 * dd, false, MMI_EPI_STORE);
+            add_norm_gemm(lm, L.in_proj[k], lm->dx, L.n1, lm->dxn, dd, MMI_EPI_STORE, {lm->dqkv, 3 * dd});
             DepAttnArgs da;
             da.qkv = lm->dqkv; da.kc = lm->dkc + l * dkv_layer; da.vc = lm->dvc + l * dkv_layer; da.out = lm->datt;
             da.B = B; da.H = Hd; da.Dh = Dhd; da.steps = c.dep_q; da.k = k;
@@ -1552,18 +1568,18 @@ int build_program(mmi_lm* lm) {
             // int8 activations: the chain's linears quantise their own input row inside the GEMM (k_gemm_q8)
             P.site("dep.out_proj");
             if (attn_in_gemm) add_dep_attn_out_proj(lm, L.out_proj[k], da, lm->dx, dd);
-            else if (a8) add_q8_gemm(lm, L.out_proj[k], lm->datt, dd, lm->dx, dd, true, MMI_EPI_RESID, lm->dx);
-            else add_gemm(lm, L.out_proj[k], lm->datt, lm->dx, dd, true, MMI_EPI_RESID, lm->dx);
+            else if (a8) add_q8_gemm(lm, L.out_proj[k], lm->datt, dd, MMI_EPI_RESID, dx_out, lm->dx);
+            else add_gemm(lm, L.out_proj[k], lm->datt, MMI_EPI_RESID, dx_out, onto_dx);
             P.site("dep.ffn_in");
-            add_norm_gemm(lm, L.ffn_in[k], lm->dx, L.n2, lm->dxn, dd, lm->dhb, c.depformer_ffn_hidden, true, MMI_EPI_GATE);
+            add_norm_gemm(lm, L.ffn_in[k], lm->dx, L.n2, lm->dxn, dd, MMI_EPI_GATE, {lm->dhb, c.depformer_ffn_hidden, true});
             P.site("dep.ffn_out");
-            if (a8) add_q8_gemm(lm, L.ffn_out[k], lm->dhb, c.depformer_ffn_hidden, lm->dx, dd, true, MMI_EPI_RESID, lm->dx);
-            else add_gemm(lm, L.ffn_out[k], lm->dhb, lm->dx, dd, true, MMI_EPI_RESID, lm->dx);
+            if (a8) add_q8_gemm(lm, L.ffn_out[k], lm->dhb, c.depformer_ffn_hidden, MMI_EPI_RESID, dx_out, lm->dx);
+            else add_gemm(lm, L.ffn_out[k], lm->dhb, MMI_EPI_RESID, dx_out, onto_dx);
         }
         uint16_t* lg = lm->dlogits + (size_t)k * B * c.card;
         P.site("dep.lin");
-        if (a8) add_q8_gemm(lm, lm->dep_lin[k], lm->dx, dd, lg, c.card, false, MMI_EPI_STORE, nullptr);
-        else add_gemm(lm, lm->dep_lin[k], lm->dx, lg, c.card, false, MMI_EPI_STORE, nullptr);
+        if (a8) add_q8_gemm(lm, lm->dep_lin[k], lm->dx, dd, MMI_EPI_STORE, {lg, c.card});
+        else add_gemm(lm, lm->dep_lin[k], lm->dx, MMI_EPI_STORE, {lg, c.card});
         P.site("dep.sample");
         add_sample(lm, lg, c.card, c.card, false, 1 + k, lm->audio_tok + k, c.dep_q, grouped && k + 1 < c.dep_q ? k + 1 : -1);
     }
@@ -1600,12 +1616,7 @@ int project_cross_source(mmi_lm* lm, const uint16_t* src, size_t slot0, int ncol
         MMI_LAUNCH(k_pack_rows, mmi_cdiv(n * d, 256), 256, 0, s, src + (size_t)col0 * d, n, d, xp, T, ksteps);
         MMI_CHECK_LAUNCH();
         for (int l = 0; l < c.num_layers; ++l) {
-            GemmArgs a;
-            memset(&a, 0, sizeof(a));
-            a.xp = reinterpret_cast<const u32x4*>(xp);
-            a.out = lm->xkv + ((size_t)l * slots + slot0 + col0) * 2 * d;
-            a.epi = MMI_EPI_STORE; a.B = n; a.out_mode = MMI_OUT_ROWMAJOR; a.out_ld = 2 * d; a.out_ksteps = ksteps;
-            a.tok_rows = n;
+            const GemmArgs a = gemm_args(lm, T, xp, MMI_EPI_STORE, n, n, {lm->xkv + ((size_t)l * slots + slot0 + col0) * 2 * d, 2 * d});
             int rc = launch_gemm(lm, s, lm->layers[l].x_kv, a, false);
             if (rc) return rc;
         }
@@ -2117,14 +2128,8 @@ static int launch_attn_prefill(hipStream_t s, const PfAttnArgs& a, int kvf, int 
 
 // One linear of a pass on `rows` rows: launch_gemm's own selection at that row count (k_gemm_rows above 64, k_gemm_xp / k_gemm_xlds
 // at or below)
-static int pf_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, int rows, const uint16_t* x, uint16_t* out, int out_features, bool out_packed,
-                   int epi, const uint16_t* resid) {
-    GemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.xp = reinterpret_cast<const u32x4*>(x); a.out = out; a.epi = epi; a.resid = resid; a.B = rows; a.tok_rows = rows;
-    a.out_mode = out_packed ? MMI_OUT_PACKED : MMI_OUT_ROWMAJOR;
-    a.out_ld = out_features;
-    a.out_ksteps = packed_ksteps_t(lm, g.T, out_features);
+static int pf_gemm(mmi_lm* lm, hipStream_t s, const GemmW& g, int rows, const uint16_t* x, int epi, const GemmOut& out, const uint16_t* resid = nullptr) {
+    GemmArgs a = gemm_args(lm, g.T, x, epi, rows, rows, out, resid);
     if (epi == MMI_EPI_PARTIAL) a.partial = lm->pf.partial;
     return launch_gemm(lm, s, g, a, false);
 }
@@ -2133,17 +2138,13 @@ static int pf_gemm_resid(mmi_lm* lm, hipStream_t s, const GemmW& g, int rows, co
     const GemmPlan p = plan_gemm(lm->knobs, g, true);
     if (p.ksplit > 4) return mmi_fail(MMI_ERR_UNSUPPORTED, "prefill: the split-K partials hold at most 4 parts (MMI_GEMM_KSPLIT)");     // pf.partial is [4][rows][dim]
     *pending = p.ksplit > 1 ? p.ksplit : 0;
-    if (p.ksplit <= 1) return pf_gemm(lm, s, g, rows, in, lm->pf.x, lm->cfg.dim, true, MMI_EPI_RESID, lm->pf.x);
-    return pf_gemm(lm, s, g, rows, in, nullptr, lm->cfg.dim, true, MMI_EPI_PARTIAL, nullptr);
+    if (p.ksplit <= 1) return pf_gemm(lm, s, g, rows, in, MMI_EPI_RESID, {lm->pf.x, lm->cfg.dim, true}, lm->pf.x);
+    return pf_gemm(lm, s, g, rows, in, MMI_EPI_PARTIAL, {nullptr, lm->cfg.dim, true});
 }
-static int pf_norm(mmi_lm* lm, hipStream_t s, int rows, int pending, const uint16_t* alpha) {
+// pf.x (+= the `pending` split-K partials), y = rms_norm(pf.x) * alpha: into pf.xn, or the last norm of a scoring pass into sc.tout
+static int pf_norm(mmi_lm* lm, hipStream_t s, int rows, int pending, const uint16_t* alpha, uint16_t* y = nullptr) {
     const int D = lm->cfg.dim;
-    int nth = mmi_cdiv(D / 8, 64) * 64;
-    if (nth > 1024) nth = 1024;
-    MMI_LAUNCH(k_resid_rmsnorm, rows, nth, 0, s, lm->pf.x, (const float*)lm->pf.partial, pending, rows, alpha, lm->pf.xn, D, lm->T, packed_ksteps(lm, D), 1e-8f,
-               (uint8_t*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-    MMI_CHECK_LAUNCH();
-    return MMI_OK;
+    return launch_rmsnorm(s, rows, lm->pf.x, lm->pf.partial, Pending{pending}, alpha, y ? y : lm->pf.xn, D, lm->T, packed_ksteps(lm, D));
 }
 
 // One pass: F frames (f0 .. f0 + F - 1 of the call's arrays) of the n sessions of `p`, eager launches on `s`
@@ -2156,12 +2157,7 @@ static int launch_score_rows(hipStream_t s, const ScoreArgs& a, int rows, int si
 // RMSNorm of the depth transformer's rows of a scoring pass (the norm launch of the step program's norm + GEMM form)
 static int sc_dep_norm(mmi_lm* lm, hipStream_t s, int rows, const uint16_t* alpha) {
     const int D = lm->cfg.depformer_dim;
-    int nth = mmi_cdiv(D / 8, 64) * 64;
-    if (nth > 1024) nth = 1024;
-    MMI_LAUNCH(k_resid_rmsnorm, rows, nth, 0, s, lm->sc.dx, (const float*)nullptr, 0, rows, alpha, lm->sc.dxn, D, lm->Td, packed_ksteps_t(lm, lm->Td, D), 1e-8f,
-               (uint8_t*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-    MMI_CHECK_LAUNCH();
-    return MMI_OK;
+    return launch_rmsnorm(s, rows, lm->sc.dx, nullptr, Pending{}, alpha, lm->sc.dxn, D, lm->Td, packed_ksteps_t(lm, lm->Td, D));
 }
 
 // The tail of a scoring pass, behind out_norm: the text head, the depth transformer as dep_q micro-steps on all R rows (micro-step
@@ -2175,7 +2171,7 @@ static int score_heads(mmi_lm* lm, hipStream_t s, const PfArgs& p, const int64_t
     int rc;
     MMI_LAUNCH(k_sc_targets, mmi_cdiv(R * sites, 256), 256, 0, s, p, sites, (const long*)toks, S.targets);
     MMI_CHECK_LAUNCH();
-    if ((rc = pf_gemm(lm, s, lm->text_linear, R, S.tout, S.tlog, c.text_card_out, false, MMI_EPI_STORE, nullptr))) return rc;
+    if ((rc = pf_gemm(lm, s, lm->text_linear, R, S.tout, MMI_EPI_STORE, {S.tlog, c.text_card_out}))) return rc;
     ScoreArgs a;
     memset(&a, 0, sizeof(a));
     a.logits = S.tlog; a.ld = c.text_card_out; a.N = c.text_card_out;
@@ -2188,7 +2184,7 @@ static int score_heads(mmi_lm* lm, hipStream_t s, const PfArgs& p, const int64_t
     const size_t dkv_layer = (size_t)rows * Hd * q * Dhd;
     const int dks = packed_ksteps_t(lm, lm->Td, dd);
     for (int k = 0; k < q; ++k) {
-        if ((rc = pf_gemm(lm, s, lm->dep_in[k], R, S.tout, S.dpre, dd, false, MMI_EPI_STORE, nullptr))) return rc;
+        if ((rc = pf_gemm(lm, s, lm->dep_in[k], R, S.tout, MMI_EPI_STORE, {S.dpre, dd}))) return rc;
         ScDepInArgs in;
         in.pre = S.dpre; in.ld = dd; in.emb = lm->dep_emb[k]; in.targets = S.targets; in.sites = sites; in.site = k;
         in.out = S.dx; in.D = dd; in.T = lm->Td; in.ksteps = dks;
@@ -2197,18 +2193,18 @@ static int score_heads(mmi_lm* lm, hipStream_t s, const PfArgs& p, const int64_t
         for (int l = 0; l < c.depformer_num_layers; ++l) {
             const DepLayerW& L = lm->dep_layers[l];
             if ((rc = sc_dep_norm(lm, s, R, L.n1))) return rc;
-            if ((rc = pf_gemm(lm, s, L.in_proj[k], R, S.dxn, S.dqkv, 3 * dd, false, MMI_EPI_STORE, nullptr))) return rc;
+            if ((rc = pf_gemm(lm, s, L.in_proj[k], R, S.dxn, MMI_EPI_STORE, {S.dqkv, 3 * dd}))) return rc;
             DepAttnArgs da;
             da.qkv = S.dqkv; da.kc = S.dkc + l * dkv_layer; da.vc = S.dvc + l * dkv_layer; da.out = S.datt;
             da.B = R; da.H = Hd; da.Dh = Dhd; da.steps = q; da.k = k;
             da.T = lm->Td; da.out_ksteps = dks;
             if ((rc = launch_dep_attn(s, da))) return rc;
-            if ((rc = pf_gemm(lm, s, L.out_proj[k], R, S.datt, S.dx, dd, true, MMI_EPI_RESID, S.dx))) return rc;
+            if ((rc = pf_gemm(lm, s, L.out_proj[k], R, S.datt, MMI_EPI_RESID, {S.dx, dd, true}, S.dx))) return rc;
             if ((rc = sc_dep_norm(lm, s, R, L.n2))) return rc;
-            if ((rc = pf_gemm(lm, s, L.ffn_in[k], R, S.dxn, S.dhb, c.depformer_ffn_hidden, true, MMI_EPI_GATE, nullptr))) return rc;
-            if ((rc = pf_gemm(lm, s, L.ffn_out[k], R, S.dhb, S.dx, dd, true, MMI_EPI_RESID, S.dx))) return rc;
+            if ((rc = pf_gemm(lm, s, L.ffn_in[k], R, S.dxn, MMI_EPI_GATE, {S.dhb, c.depformer_ffn_hidden, true}))) return rc;
+            if ((rc = pf_gemm(lm, s, L.ffn_out[k], R, S.dhb, MMI_EPI_RESID, {S.dx, dd, true}, S.dx))) return rc;
         }
-        if ((rc = pf_gemm(lm, s, lm->dep_lin[k], R, S.dx, S.alog + (size_t)k * rows * c.card, c.card, false, MMI_EPI_STORE, nullptr))) return rc;
+        if ((rc = pf_gemm(lm, s, lm->dep_lin[k], R, S.dx, MMI_EPI_STORE, {S.alog + (size_t)k * rows * c.card, c.card}))) return rc;
     }
     a.logits = S.alog; a.site_stride = (long)rows * c.card; a.ld = c.card; a.N = c.card;
     a.tgt_off = 1; a.out_off = 1;
@@ -2235,7 +2231,7 @@ static int prefill_pass(mmi_lm* lm, hipStream_t s, PfArgs p, const int64_t* user
     for (int l = 0; l < c.num_layers; ++l) {
         const LayerW& L = lm->layers[l];
         if ((rc = pf_norm(lm, s, R, pending, L.n1))) return rc;
-        if ((rc = pf_gemm(lm, s, L.in_proj, R, P.xn, P.qkv, 3 * d, false, MMI_EPI_STORE, nullptr))) return rc;
+        if ((rc = pf_gemm(lm, s, L.in_proj, R, P.xn, MMI_EPI_STORE, {P.qkv, 3 * d}))) return rc;
         PfRopeArgs ra;
         ra.qkv = P.qkv; ra.rope = P.rope; ra.q = P.q; ra.sk = P.sk; ra.sv = P.sv; ra.sks = P.sks; ra.svs = P.svs; ra.R = R; ra.H = H; ra.Dh = Dh;
         const int rblocks = (int)mmi_cdiv64((int64_t)R * 3 * d / 16, 256);
@@ -2262,15 +2258,11 @@ static int prefill_pass(mmi_lm* lm, hipStream_t s, PfArgs p, const int64_t* user
         if (last && !score) break;
         if ((rc = pf_gemm_resid(lm, s, L.out_proj, R, P.att, &pending))) return rc;
         if ((rc = pf_norm(lm, s, R, pending, L.n2))) return rc;
-        if ((rc = pf_gemm(lm, s, L.ffn_in, R, P.xn, P.hb, c.ffn_hidden, true, MMI_EPI_GATE, nullptr))) return rc;
+        if ((rc = pf_gemm(lm, s, L.ffn_in, R, P.xn, MMI_EPI_GATE, {P.hb, c.ffn_hidden, true}))) return rc;
         if ((rc = pf_gemm_resid(lm, s, L.ffn_out, R, P.hb, &pending))) return rc;
     }
     if (score) {
-        int nth = mmi_cdiv(d / 8, 64) * 64;
-        if (nth > 1024) nth = 1024;
-        MMI_LAUNCH(k_resid_rmsnorm, R, nth, 0, s, P.x, (const float*)P.partial, pending, R, (const uint16_t*)lm->out_norm, lm->sc.tout, d, lm->T,
-                   packed_ksteps(lm, d), 1e-8f, (uint8_t*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-        MMI_CHECK_LAUNCH();
+        if ((rc = pf_norm(lm, s, R, pending, lm->out_norm, lm->sc.tout))) return rc;
         if ((rc = score_heads(lm, s, p, toks, score))) return rc;
     }
     if (!commit) return MMI_OK;
@@ -2457,6 +2449,45 @@ extern "C" int64_t mmi_lm_debug_state_regions(const mmi_lm* lm, char* buf, int64
     return need;
 }
 
+// The scratch of a parity tap (mmi_lm_debug_*): an arena of its own - a streaming session is not disturbed - under the handle's
+// poison knob.  Leaving the tap by ANY return drains the stream and releases the arena, so the taps use the ordinary
+// MMI_HIP_CHECK / MMI_CHECK_LAUNCH early returns.
+namespace {
+struct TapScratch {
+    MmiArena A;
+    hipStream_t s;
+    const char* tap;      // the entry's name, for the texts of HIP failures
+    TapScratch(const mmi_lm* lm, hipStream_t stream, const char* name) : s(stream), tap(name) { A.poison = lm->knobs.debug_poison; }
+    TapScratch(const TapScratch&) = delete;
+    TapScratch& operator=(const TapScratch&) = delete;
+    ~TapScratch() {
+        hipStreamSynchronize(s);
+        A.release();
+    }
+    template <class T>
+    int alloc(T** p, size_t n) {
+        if (A.alloc(p, n) != hipSuccess) return mmi_fail(MMI_ERR_HIP, std::string("out of device memory (") + tap + ")");
+        return MMI_OK;
+    }
+    template <class T>
+    int zeroed(T** p, size_t n) {
+        const int rc = alloc(p, n);
+        if (rc) return rc;
+        MMI_HIP_CHECK(hipMemsetAsync(*p, 0, n * sizeof(T), s));
+        return MMI_OK;
+    }
+    // a zeroed packed tensor of rows x d at tile T (the padding rows and columns of a packed operand read as zero)
+    int packed(uint16_t** p, int rows, int T, int ksteps) { return zeroed(p, (size_t)mmi_cdiv(rows, T) * ksteps * 512); }
+    // ... unpacked into the caller's row-major [rows][d], and the tap's launches waited for
+    int unpack(const uint16_t* p, int rows, int d, int T, int ksteps, void* out_bf16) {
+        MMI_LAUNCH(k_unpack_rows, mmi_cdiv(rows * d, 256), 256, 0, s, p, rows, d, (uint16_t*)out_bf16, T, ksteps);
+        MMI_CHECK_LAUNCH();
+        if (hipStreamSynchronize(s) != hipSuccess) return mmi_fail(MMI_ERR_HIP, std::string(tap) + ": the launches failed");
+        return MMI_OK;
+    }
+};
+}  // namespace
+
 // Parity tap of the prefill attention (include/moshi_mi.h): launch_attn_prefill - the attention op of a pass - on caller-supplied
 // operands, with a packed output of its own.  Nothing of the handle but its device and its poison knob is read.
 extern "C" int mmi_lm_debug_prefill_attn(mmi_lm* lm, const void* q_bf16, const int32_t* row_ring, const int64_t* row_pos, const void* k_ring,
@@ -2491,14 +2522,11 @@ extern "C" int mmi_lm_debug_prefill_attn(mmi_lm* lm, const void* q_bf16, const i
                 return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_prefill_attn: a block's rows name one ring in [0, rings) and consecutive positions >= 0");
         }
     }
-    const int d = H * Dh, T = rows <= 16 ? 16 : 32, mt = mmi_cdiv(rows, T), ksteps = mmi_cdiv(d, mmi_kstep(T));
-    const size_t oelems = (size_t)mt * ksteps * 512;
-    MmiArena A;
-    A.poison = lm->knobs.debug_poison;
+    const int d = H * Dh, T = rows <= 16 ? 16 : 32, ksteps = mmi_cdiv(d, mmi_kstep(T));
+    TapScratch scratch(lm, s, "mmi_lm_debug_prefill_attn");
     uint16_t* att = nullptr;
-    auto done = [&](int rc) { hipStreamSynchronize(s); A.release(); return rc; };
-    if (hipSuccess != A.alloc(&att, oelems)) return done(mmi_fail(MMI_ERR_HIP, "out of device memory (mmi_lm_debug_prefill_attn)"));
-    if (hipMemsetAsync(att, 0, oelems * 2, s) != hipSuccess) return done(mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_prefill_attn: hipMemsetAsync failed"));
+    int rc = scratch.packed(&att, rows, T, ksteps);
+    if (rc) return rc;
     PfAttnArgs a;
     memset(&a, 0, sizeof(a));
     const size_t rowb = pf_row_bytes(kvf, Dh);
@@ -2508,13 +2536,8 @@ extern "C" int mmi_lm_debug_prefill_attn(mmi_lm* lm, const void* q_bf16, const i
     a.sks = a.sk + (size_t)rows * H * rowb; a.svs = a.sv + (size_t)rows * H * rowb;
     a.row_sess = row_ring; a.row_pos = reinterpret_cast<const long*>(row_pos);
     a.out = att; a.T = T; a.out_ksteps = ksteps; a.H = H; a.cap = cap; a.context = context; a.n = n_blocks; a.F = F;
-    int rc = launch_attn_prefill(s, a, kvf, Dh);
-    if (rc) return done(rc);
-    MMI_LAUNCH(k_unpack_rows, mmi_cdiv(rows * d, 256), 256, 0, s, (const uint16_t*)att, rows, d, (uint16_t*)out_bf16, T, ksteps);
-    if (hipGetLastError() != hipSuccess) return done(mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_prefill_attn: kernel launch failed"));
-    if (hipStreamSynchronize(s) != hipSuccess) { A.release(); return mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_prefill_attn: the launches failed"); }
-    A.release();
-    return MMI_OK;
+    if ((rc = launch_attn_prefill(s, a, kvf, Dh))) return rc;
+    return scratch.unpack(att, rows, d, T, ksteps, out_bf16);
 }
 
 // The streaming-state arena of the stream being started, buffer by buffer: add(member, count, name, rows, kind), then how it starts.
@@ -3523,19 +3546,7 @@ extern "C" int64_t mmi_lm_debug_kv_ring(mmi_lm* lm, int32_t layer, int32_t which
 }
 
 // Parity tap: ONE linear of the model on caller-supplied rows, through the kernels the step uses for it (include/moshi_mi.h).
-// Works on its own scratch (a streaming session is not disturbed) and synchronises.
-// failures after the scratch arena exists leave through done(): the launches are drained and the arena released
-#define MMI_DBG_HIP(call)                                                                                          \
-    do {                                                                                                           \
-        hipError_t e_ = (call);                                                                                    \
-        if (e_ != hipSuccess) return done(mmi_fail(MMI_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_))); \
-    } while (0)
-#define MMI_DBG_LAUNCHED()                                                                                         \
-    do {                                                                                                           \
-        hipError_t e_ = hipGetLastError();                                                                         \
-        if (e_ != hipSuccess) return done(mmi_fail(MMI_ERR_HIP, std::string("kernel launch failed: ") + hipGetErrorString(e_))); \
-    } while (0)
-
+// Works on its own scratch (TapScratch) and synchronises.
 // row_slots (mmi_lm_debug_linear_lora): the rows' adapter slots, a host array - the shrink launch, then the linear with its tail
 static int debug_linear_impl(mmi_lm* lm, const char* weight_name, const char* alpha_name, int32_t path, const void* x_bf16,
                              int32_t rows, void* out_bf16, int8_t* codes, float* absmax, void* norm_out, const int32_t* row_slots,
@@ -3564,60 +3575,38 @@ static int debug_linear_impl(mmi_lm* lm, const char* weight_name, const char* al
     if ((codes || absmax) && !(a8 && (path == MMI_DBG_PLAIN || path == MMI_DBG_SPLITK || path == MMI_DBG_NORM)))
         return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_linear: codes / absmax exist on the int8 x int8 paths that materialise the operand (plain, split-K, norm)");
     hipStream_t s = (hipStream_t)stream;
-    const int T = g.T, mt = mmi_cdiv(rows, T), KS = mmi_kstep(T);
+    const int T = g.T, mt = mmi_cdiv(rows, T);
     if (mt > 2 && (path == MMI_DBG_FUSED || path == MMI_DBG_NORM_FUSED))
         return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_linear: the fused forms are not selected above 64 rows (k_gemm_rows + a norm launch)");
     const int K = g.K, N = g.N, kin = packed_ksteps_t(lm, T, K), kout = packed_ksteps_t(lm, T, N);
-    const int nthK = [&] { int n = mmi_cdiv(K / 8, 64) * 64; return n > 1024 ? 1024 : n; }();
-    MmiArena A;
-    A.poison = lm->knobs.debug_poison;
+    TapScratch scratch(lm, s, row_slots ? "mmi_lm_debug_linear_lora" : "mmi_lm_debug_linear");
     uint16_t *xp = nullptr, *yp = nullptr, *xres = nullptr, *zeros = nullptr, *outp = (uint16_t*)out_bf16;
     uint8_t* xq = nullptr;
     float *sx = nullptr, *partial = nullptr;
-    const size_t xelems = (size_t)mt * kin * 512, oelems = (size_t)mt * kout * 512;
-    bool ok = true;
-    ok &= hipSuccess == A.alloc(&xp, xelems);
-    ok &= hipSuccess == A.alloc(&yp, xelems);
-    ok &= hipSuccess == A.alloc(&xq, (size_t)mt * (kin / 2 + 1) * 1024);
-    ok &= hipSuccess == A.alloc(&sx, (size_t)mt * T);
-    ok &= hipSuccess == A.alloc(&xres, oelems);
-    ok &= hipSuccess == A.alloc(&zeros, (size_t)N + 8);
-    ok &= hipSuccess == A.alloc(&partial, (size_t)4 * rows * N);
-    auto done = [&](int rc) { hipStreamSynchronize(s); A.release(); return rc; };
-    if (!ok) return done(mmi_fail(MMI_ERR_HIP, "out of device memory (mmi_lm_debug_linear)"));
-    MMI_DBG_HIP(hipMemsetAsync(xp, 0, xelems * 2, s));
-    MMI_DBG_HIP(hipMemsetAsync(yp, 0, xelems * 2, s));
-    MMI_DBG_HIP(hipMemsetAsync(xq, 0, (size_t)mt * (kin / 2 + 1) * 1024, s));
-    MMI_DBG_HIP(hipMemsetAsync(sx, 0, (size_t)mt * T * sizeof(float), s));
-    MMI_DBG_HIP(hipMemsetAsync(xres, 0, oelems * 2, s));
-    MMI_DBG_HIP(hipMemsetAsync(zeros, 0, ((size_t)N + 8) * 2, s));
+    int rc;
+    if ((rc = scratch.packed(&xp, rows, T, kin)) || (rc = scratch.packed(&yp, rows, T, kin)) ||
+        (rc = scratch.zeroed(&xq, (size_t)mt * (kin / 2 + 1) * 1024)) || (rc = scratch.zeroed(&sx, (size_t)mt * T)) ||
+        (rc = scratch.packed(&xres, rows, T, kout)) || (rc = scratch.zeroed(&zeros, (size_t)N + 8)) ||
+        (rc = scratch.alloc(&partial, (size_t)4 * rows * N)))
+        return rc;
     MMI_LAUNCH(k_pack_rows, mmi_cdiv(rows * K, 256), 256, 0, s, (const uint16_t*)x_bf16, rows, K, xp, T, kin);
-    MMI_DBG_LAUNCHED();
+    MMI_CHECK_LAUNCH();
     int* slots_dev = nullptr;
     uint16_t* lora_t = nullptr;
     if (row_slots) {
-        const size_t telems = (size_t)mt * (lm->lora_S * lm->lora_R / KS) * 512;
-        if (A.alloc(&slots_dev, (size_t)rows) != hipSuccess || A.alloc(&lora_t, telems) != hipSuccess)
-            return done(mmi_fail(MMI_ERR_HIP, "out of device memory (mmi_lm_debug_linear_lora)"));
-        MMI_DBG_HIP(hipMemcpyAsync(slots_dev, row_slots, (size_t)rows * sizeof(int), hipMemcpyHostToDevice, s));
-        MMI_DBG_HIP(hipMemsetAsync(lora_t, 0, telems * 2, s));
+        if ((rc = scratch.alloc(&slots_dev, (size_t)rows)) || (rc = scratch.packed(&lora_t, rows, T, lm->lora_S * lm->lora_R / mmi_kstep(T)))) return rc;
+        MMI_HIP_CHECK(hipMemcpyAsync(slots_dev, row_slots, (size_t)rows * sizeof(int), hipMemcpyHostToDevice, s));
     }
     const uint16_t* operand = xp;              // the packed bf16 rows the GEMM (or its quantiser) reads
     const bool gated = g.gate != 0;
-    GemmArgs a;
-    memset(&a, 0, sizeof(a));
-    a.out = outp; a.epi = gated ? MMI_EPI_GATE : MMI_EPI_STORE; a.B = rows; a.tok_rows = rows;
-    a.out_mode = MMI_OUT_ROWMAJOR; a.out_ld = N; a.out_ksteps = kout;
-    int rc = MMI_OK;
+    GemmArgs a = gemm_args(lm, T, nullptr, gated ? MMI_EPI_GATE : MMI_EPI_STORE, rows, rows, {outp, N});
     if (path == MMI_DBG_NORM) {                // the norm launch of the step: y (+ its int8 copy) = rms_norm(x) * alpha
-        MMI_LAUNCH(k_resid_rmsnorm, rows, nthK, 0, s, xp, (const float*)nullptr, 0, rows, alpha, yp, K, T, kin, 1e-8f,
-                   a8 ? xq : (uint8_t*)nullptr, a8 ? sx : (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
-        MMI_DBG_LAUNCHED();
+        if ((rc = launch_rmsnorm(s, rows, xp, nullptr, Pending{}, alpha, yp, K, T, kin, a8 ? xq : nullptr, a8 ? sx : nullptr))) return rc;
         operand = yp;
         if (norm_out) MMI_LAUNCH(k_unpack_rows, mmi_cdiv(rows * K, 256), 256, 0, s, (const uint16_t*)yp, rows, K, (uint16_t*)norm_out, T, kin);
     } else if (a8 && (path == MMI_DBG_PLAIN || path == MMI_DBG_SPLITK)) {
-        MMI_LAUNCH(k_quant_rows_i8, rows, nthK, 0, s, (const uint16_t*)xp, rows, K, T, kin, xq, sx);
-        MMI_DBG_LAUNCHED();
+        MMI_LAUNCH(k_quant_rows_i8, rows, row_threads(K), 0, s, (const uint16_t*)xp, rows, K, T, kin, xq, sx);
+        MMI_CHECK_LAUNCH();
     }
     if (path == MMI_DBG_PLAIN || path == MMI_DBG_NORM || path == MMI_DBG_SPLITK) {
         a.xp = reinterpret_cast<const u32x4*>(operand);
@@ -3625,54 +3614,44 @@ static int debug_linear_impl(mmi_lm* lm, const char* weight_name, const char* al
         Pending pd;
         if (path == MMI_DBG_SPLITK) {
             const GemmPlan p = plan_gemm(lm->knobs, g, true);
-            if (gated || p.ksplit <= 1) return done(mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_linear: the engine does not split this GEMM over K"));
+            if (gated || p.ksplit <= 1) return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_linear: the engine does not split this GEMM over K");
             a.epi = MMI_EPI_PARTIAL; a.partial = partial; a.out = nullptr;
             pd.P = p.ksplit;
             if (a8) { pd.sx = sx; pd.scb = g.scb; }
         }
-        if (row_slots) {
-            rc = launch_lora_shrink(lm, s, g, a.xp, rows, slots_dev, rows, lora_t);
-            if (rc) return done(rc);
-        }
-        rc = launch_gemm(lm, s, g, a, false, reinterpret_cast<const u32x4*>(lora_t));
-        if (rc) return done(rc);
+        if (row_slots && (rc = launch_lora_shrink(lm, s, g, a.xp, rows, slots_dev, rows, lora_t))) return rc;
+        if ((rc = launch_gemm(lm, s, g, a, false, reinterpret_cast<const u32x4*>(lora_t)))) return rc;
         if (path == MMI_DBG_SPLITK) {          // the fold of the next norm launch: x (= 0) + bf16(sum of the partials)
-            const int nthN = [&] { int n = mmi_cdiv(N / 8, 64) * 64; return n > 1024 ? 1024 : n; }();
-            if (N > 8 * 1024 * MMI_NORM_MAXP) return done(mmi_fail(MMI_ERR_UNSUPPORTED, "row too long for the norm kernel"));
+            if (N > 8 * 1024 * MMI_NORM_MAXP) return mmi_fail(MMI_ERR_UNSUPPORTED, "row too long for the norm kernel");
             uint16_t* ytmp = nullptr;
-            if (A.alloc(&ytmp, oelems) != hipSuccess) return done(mmi_fail(MMI_ERR_HIP, "out of device memory"));
-            MMI_LAUNCH(k_resid_rmsnorm, rows, nthN, 0, s, xres, (const float*)partial, pd.P, rows, (const uint16_t*)zeros, ytmp, N, T, kout, 1e-8f,
-                       (uint8_t*)nullptr, (float*)nullptr, pd.sx, pd.scb);
+            if ((rc = scratch.alloc(&ytmp, (size_t)mt * kout * 512))) return rc;
+            if ((rc = launch_rmsnorm(s, rows, xres, partial, pd, zeros, ytmp, N, T, kout))) return rc;
             MMI_LAUNCH(k_unpack_rows, mmi_cdiv(rows * N, 256), 256, 0, s, (const uint16_t*)xres, rows, N, outp, T, kout);
-            MMI_DBG_LAUNCHED();
+            MMI_CHECK_LAUNCH();
         }
     } else if (path == MMI_DBG_FUSED) {
         const int kmax = q8_fused_kmax(g);
-        if (!a8 || !kmax) return done(mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_linear: k_gemm_q8 needs an int8 x int8 model and rows of <= 88 entries"));
+        if (!a8 || !kmax) return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_linear: k_gemm_q8 needs an int8 x int8 model and rows of <= 88 entries");
         a.xp = reinterpret_cast<const u32x4*>(xp);
-        a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT; a.wscale = g.scale; a.wscb = g.scb; a.gate_rows = gated ? g.N : 0;
-        a.wq = 3; a.xinv = g.xinv;
+        bind_weight(a, g);
+        a.wq = 3;
         a.osplit = q8_fused_osplit(lm->knobs, g, a.epi, T);
-        rc = launch_q8_fused(s, T, mt, kmax, g.NT * a.osplit, !lm->knobs.q8_tiles_serial, a);
-        if (rc) return done(rc);
+        if ((rc = launch_q8_fused(s, T, mt, kmax, g.NT * a.osplit, !lm->knobs.q8_tiles_serial, a))) return rc;
     } else if (path == MMI_DBG_NORM_FUSED) {
         const int wq = (a8 && g.wq == 1) ? 3 : g.wq;
-        if (g.KSTEPS > norm_fused_max(wq)) return done(mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_linear: the row is too long for the norm-fused GEMM"));
+        if (g.KSTEPS > norm_fused_max(wq)) return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_linear: the row is too long for the norm-fused GEMM");
         a.xp = reinterpret_cast<const u32x4*>(xp);
         a.alpha = alpha; a.D = K; a.eps = 1e-8f;
-        a.wp = g.wp; a.N = g.N; a.KSTEPS = g.KSTEPS; a.NT = g.NT; a.wscale = g.scale; a.wscb = g.scb; a.ws4 = g.s4; a.gate_rows = gated ? g.N : 0;
-        a.wq = wq; a.xinv = g.xinv; a.osplit = 1;
-        rc = launch_norm_fused(s, T, mt, wq, g.NT, !lm->knobs.q8_tiles_serial, a);
-        if (rc) return done(rc);
+        bind_weight(a, g);
+        a.wq = wq; a.osplit = 1;
+        if ((rc = launch_norm_fused(s, T, mt, wq, g.NT, !lm->knobs.q8_tiles_serial, a))) return rc;
     } else {
-        return done(mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_linear: unknown path"));
+        return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_linear: unknown path");
     }
     if (codes) MMI_LAUNCH(k_unpack_q8, mmi_cdiv(rows * K, 256), 256, 0, s, (const uint8_t*)xq, rows, K, codes, T, kin);
-    if (absmax) MMI_DBG_HIP(hipMemcpyAsync(absmax, sx, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
-    MMI_DBG_LAUNCHED();
-    (void)KS;
-    if (hipStreamSynchronize(s) != hipSuccess) { A.release(); return mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_linear: the launches failed"); }
-    A.release();
+    if (absmax) MMI_HIP_CHECK(hipMemcpyAsync(absmax, sx, (size_t)rows * sizeof(float), hipMemcpyDeviceToDevice, s));
+    MMI_CHECK_LAUNCH();
+    if (hipStreamSynchronize(s) != hipSuccess) return mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_linear: the launches failed");
     return MMI_OK;
 }
 
@@ -3721,22 +3700,16 @@ extern "C" int mmi_lm_debug_attn(mmi_lm* lm, const void* q_bf16, const void* k_r
     MMI_HIP_CHECK(hipMemcpy(off.data(), offsets, (size_t)rows * sizeof(int64_t), hipMemcpyDeviceToHost));
     for (int b = 0; b < rows; ++b)
         if (off[b] < 0) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_attn: negative offset");
-    const int d = H * Dh, T = rows <= 16 ? 16 : 32, mt = mmi_cdiv(rows, T), ksteps = mmi_cdiv(d, mmi_kstep(T));
-    const size_t pairs = (size_t)rows * H, oelems = (size_t)mt * ksteps * 512;
-    MmiArena A;
-    A.poison = lm->knobs.debug_poison;
+    const int d = H * Dh, T = rows <= 16 ? 16 : 32, ksteps = mmi_cdiv(d, mmi_kstep(T));
+    const size_t pairs = (size_t)rows * H;
+    TapScratch scratch(lm, s, "mmi_lm_debug_attn");
     float *opart = nullptr, *ml = nullptr;
     unsigned* arrived = nullptr;
     uint16_t* att = nullptr;
-    bool ok = true;
-    ok &= hipSuccess == A.alloc(&opart, pairs * NS * Dh);
-    ok &= hipSuccess == A.alloc(&ml, pairs * NS * 2);
-    ok &= hipSuccess == A.alloc(&arrived, pairs);
-    ok &= hipSuccess == A.alloc(&att, oelems);
-    auto done = [&](int rc) { hipStreamSynchronize(s); A.release(); return rc; };
-    if (!ok) return done(mmi_fail(MMI_ERR_HIP, "out of device memory (mmi_lm_debug_attn)"));
-    MMI_DBG_HIP(hipMemsetAsync(arrived, 0, pairs * sizeof(unsigned), s));
-    MMI_DBG_HIP(hipMemsetAsync(att, 0, oelems * 2, s));
+    int rc;
+    if ((rc = scratch.alloc(&opart, pairs * NS * Dh)) || (rc = scratch.alloc(&ml, pairs * NS * 2)) || (rc = scratch.zeroed(&arrived, pairs)) ||
+        (rc = scratch.packed(&att, rows, T, ksteps)))
+        return rc;
     LmAttnArgs a;
     memset(&a, 0, sizeof(a));
     a.qrot = (uint16_t*)q_bf16; a.kc = (uint16_t*)k_ring; a.vc = (uint16_t*)v_ring;
@@ -3745,13 +3718,8 @@ extern "C" int mmi_lm_debug_attn(mmi_lm* lm, const void* q_bf16, const void* k_r
     a.T = T; a.out_ksteps = ksteps;
     a.done = arrived; a.solo_rows = solo_rows;
     a.kv_soff = kvf == 2 ? (long)pairs * cap * Dh / 2 : 0;
-    int rc = launch_attn(s, a, kvf, wave, NS > 1 && merge == MMI_ATTN_MERGE_LAUNCH);
-    if (rc) return done(rc);
-    MMI_LAUNCH(k_unpack_rows, mmi_cdiv(rows * d, 256), 256, 0, s, (const uint16_t*)att, rows, d, (uint16_t*)out_bf16, T, ksteps);
-    MMI_DBG_LAUNCHED();
-    if (hipStreamSynchronize(s) != hipSuccess) { A.release(); return mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_attn: the launches failed"); }
-    A.release();
-    return MMI_OK;
+    if ((rc = launch_attn(s, a, kvf, wave, NS > 1 && merge == MMI_ATTN_MERGE_LAUNCH))) return rc;
+    return scratch.unpack(att, rows, d, T, ksteps, out_bf16);
 }
 
 // Parity tap of the depth transformer's attention (include/moshi_mi.h): launch_dep_attn - the step's dep.attn op and the scoring
@@ -3779,24 +3747,16 @@ extern "C" int mmi_lm_debug_dep_attn(mmi_lm* lm, const void* qkv_bf16, void* k_c
     if (((uintptr_t)qkv_bf16 | (uintptr_t)k_cache | (uintptr_t)v_cache) % 16 || (uintptr_t)out_bf16 % 2)
         return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_dep_attn: qkv and the caches must be 16-byte aligned, out 2-byte");
     hipStream_t s = (hipStream_t)stream;
-    const int d = H * Dh, T = rows <= 16 ? 16 : 32, mt = mmi_cdiv(rows, T), ksteps = mmi_cdiv(d, mmi_kstep(T));
-    const size_t oelems = (size_t)mt * ksteps * 512;
-    MmiArena A;
-    A.poison = lm->knobs.debug_poison;
+    const int d = H * Dh, T = rows <= 16 ? 16 : 32, ksteps = mmi_cdiv(d, mmi_kstep(T));
+    TapScratch scratch(lm, s, "mmi_lm_debug_dep_attn");
     uint16_t* att = nullptr;
-    auto done = [&](int rc) { hipStreamSynchronize(s); A.release(); return rc; };
-    if (hipSuccess != A.alloc(&att, oelems)) return done(mmi_fail(MMI_ERR_HIP, "out of device memory (mmi_lm_debug_dep_attn)"));
-    MMI_DBG_HIP(hipMemsetAsync(att, 0, oelems * 2, s));
+    int rc = scratch.packed(&att, rows, T, ksteps);
+    if (rc) return rc;
     DepAttnArgs da;
     da.qkv = (const uint16_t*)qkv_bf16; da.kc = (uint16_t*)k_cache; da.vc = (uint16_t*)v_cache; da.out = att;
     da.B = rows; da.H = H; da.Dh = Dh; da.steps = steps; da.k = k; da.T = T; da.out_ksteps = ksteps;
     int ran = -1;
-    const int rc = launch_dep_attn(s, da, kernel, &ran);
-    if (rc) return done(rc);
-    MMI_LAUNCH(k_unpack_rows, mmi_cdiv(rows * d, 256), 256, 0, s, (const uint16_t*)att, rows, d, (uint16_t*)out_bf16, T, ksteps);
-    MMI_DBG_LAUNCHED();
-    if (hipStreamSynchronize(s) != hipSuccess) { A.release(); return mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_dep_attn: the launches failed"); }
-    A.release();
+    if ((rc = launch_dep_attn(s, da, kernel, &ran)) || (rc = scratch.unpack(att, rows, d, T, ksteps, out_bf16))) return rc;
     if (kernel_run) *kernel_run = ran;
     return MMI_OK;
 }
@@ -3820,38 +3780,26 @@ extern "C" int mmi_lm_debug_dep_attn_out_proj(mmi_lm* lm, int32_t layer, int32_t
         return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_dep_attn_out_proj: qkv and the caches must be 16-byte aligned, x and out 2-byte");
     hipStream_t s = (hipStream_t)stream;
     const int T = g.T, ksteps = packed_ksteps_t(lm, T, dd);
-    const size_t elems = (size_t)ksteps * 512;
-    MmiArena A;
-    A.poison = lm->knobs.debug_poison;
+    TapScratch scratch(lm, s, "mmi_lm_debug_dep_attn_out_proj");
     uint16_t *xp = nullptr, *att = nullptr;
-    auto done = [&](int rc) { hipStreamSynchronize(s); A.release(); return rc; };
-    if (hipSuccess != A.alloc(&xp, elems) || hipSuccess != A.alloc(&att, elems))
-        return done(mmi_fail(MMI_ERR_HIP, "out of device memory (mmi_lm_debug_dep_attn_out_proj)"));
-    MMI_DBG_HIP(hipMemsetAsync(xp, 0, elems * 2, s));
-    MMI_DBG_HIP(hipMemsetAsync(att, 0, elems * 2, s));
+    int ran = -1, rc;
+    if ((rc = scratch.packed(&xp, 1, T, ksteps)) || (rc = scratch.packed(&att, 1, T, ksteps))) return rc;
     MMI_LAUNCH(k_pack_rows, mmi_cdiv(dd, 256), 256, 0, s, (const uint16_t*)x_bf16, 1, dd, xp, T, ksteps);
-    MMI_DBG_LAUNCHED();
+    MMI_CHECK_LAUNCH();
     DepAttnArgs da;
     da.qkv = (const uint16_t*)qkv_bf16; da.kc = (uint16_t*)k_cache; da.vc = (uint16_t*)v_cache; da.out = att;
     da.B = 1; da.H = H; da.Dh = Dh; da.steps = steps; da.k = k; da.T = T; da.out_ksteps = ksteps;
-    int ran = -1, rc;
     if (fused) {
         rc = launch_dep_attn_out_proj_planned(s, plan_dep_attn_out_proj(lm, g, xp, dd, 1, 1), da);
         ran = MMI_DEP_ATTN_FUSED;
     } else {
-        if ((rc = launch_dep_attn(s, da, MMI_DEP_ATTN_AUTO, &ran))) return done(rc);
-        GemmArgs a;                                                 // add_gemm(lm, out_proj, datt, dx, dd, true, MMI_EPI_RESID, dx)
-        memset(&a, 0, sizeof(a));
-        a.xp = reinterpret_cast<const u32x4*>(att); a.out = xp; a.epi = MMI_EPI_RESID; a.resid = xp;
-        a.tok_rows = 1; a.B = 1; a.out_mode = MMI_OUT_PACKED; a.out_ld = dd; a.out_ksteps = ksteps;
-        rc = launch_gemm(lm, s, g, a, false);
+        if ((rc = launch_dep_attn(s, da, MMI_DEP_ATTN_AUTO, &ran))) return rc;
+        // the step's add_gemm(lm, out_proj, datt, MMI_EPI_RESID, {dx, dd, true}) with resid = dx, on one row
+        rc = launch_gemm(lm, s, g, gemm_args(lm, T, att, MMI_EPI_RESID, 1, 1, {xp, dd, true}, xp), false);
     }
-    if (rc) return done(rc);
-    MMI_LAUNCH(k_unpack_rows, mmi_cdiv(dd, 256), 256, 0, s, (const uint16_t*)xp, 1, dd, (uint16_t*)out_bf16, T, ksteps);
+    if (rc) return rc;
     if (att_bf16 && !fused) MMI_LAUNCH(k_unpack_rows, mmi_cdiv(dd, 256), 256, 0, s, (const uint16_t*)att, 1, dd, (uint16_t*)att_bf16, T, ksteps);
-    MMI_DBG_LAUNCHED();
-    if (hipStreamSynchronize(s) != hipSuccess) { A.release(); return mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_dep_attn_out_proj: the launches failed"); }
-    A.release();
+    if ((rc = scratch.unpack(xp, 1, dd, T, ksteps, out_bf16))) return rc;
     if (kernel_run) *kernel_run = ran;
     return MMI_OK;
 }
@@ -3874,24 +3822,16 @@ extern "C" int mmi_lm_debug_cross_attn(mmi_lm* lm, const void* q_bf16, const voi
     MMI_HIP_CHECK(hipMemcpy(L.data(), len, (size_t)rows * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int b = 0; b < rows; ++b)
         if (L[b] < 1 || L[b] > cap) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_cross_attn: every len must be in [1, cap]");
-    const int d = H * Dh, T = rows <= 16 ? 16 : 32, mt = mmi_cdiv(rows, T), ksteps = mmi_cdiv(d, mmi_kstep(T));
-    const size_t oelems = (size_t)mt * ksteps * 512;
-    MmiArena A;
-    A.poison = lm->knobs.debug_poison;
+    const int d = H * Dh, T = rows <= 16 ? 16 : 32, ksteps = mmi_cdiv(d, mmi_kstep(T));
+    TapScratch scratch(lm, s, "mmi_lm_debug_cross_attn");
     uint16_t* att = nullptr;
-    auto done = [&](int rc) { hipStreamSynchronize(s); A.release(); return rc; };
-    if (hipSuccess != A.alloc(&att, oelems)) return done(mmi_fail(MMI_ERR_HIP, "out of device memory (mmi_lm_debug_cross_attn)"));
-    MMI_DBG_HIP(hipMemsetAsync(att, 0, oelems * 2, s));
+    int rc = scratch.packed(&att, rows, T, ksteps);
+    if (rc) return rc;
     CrossAttnArgs ca;
     ca.q = (const uint16_t*)q_bf16; ca.kv = (const uint16_t*)kv_bf16; ca.out = att; ca.len = len;
     ca.B = rows; ca.H = H; ca.Dh = Dh; ca.cap = cap; ca.T = T; ca.out_ksteps = ksteps;
-    const int rc = launch_cross_attn(s, ca);
-    if (rc) return done(rc);
-    MMI_LAUNCH(k_unpack_rows, mmi_cdiv(rows * d, 256), 256, 0, s, (const uint16_t*)att, rows, d, (uint16_t*)out_bf16, T, ksteps);
-    MMI_DBG_LAUNCHED();
-    if (hipStreamSynchronize(s) != hipSuccess) { A.release(); return mmi_fail(MMI_ERR_HIP, "mmi_lm_debug_cross_attn: the launches failed"); }
-    A.release();
-    return MMI_OK;
+    if ((rc = launch_cross_attn(s, ca))) return rc;
+    return scratch.unpack(att, rows, d, T, ksteps, out_bf16);
 }
 
 extern "C" int64_t mmi_lm_stat(const mmi_lm* lm, int32_t which) {

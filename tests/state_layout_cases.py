@@ -29,6 +29,7 @@ import torch
 from moshi_amd import _capi
 from moshi_amd.config import tiny_lm_config
 from moshi_amd.lm import ConditionFuser, LMGen, LMModel
+from tests import mxfp4_cases as mx
 from tests import row_condition_cases as rc
 from tests import tts_machine_cases as tm
 from tests.lm_cases import cached_lm_state_dict
@@ -90,6 +91,15 @@ CONFIGS = {
     "adapters": ({}, lambda d, l: _tiny(d, l, 2, 2, adapters=(2, 32))),
     "hidden_taps": ({}, _taps),
     "prefill32_score": ({}, lambda d, l: _tiny(d, l, 2, 2, prefill_rows=32, score=True)),
+    # the launch forms the configurations above never reach: a split-K partial GEMM and its fold in the next norm launch, fp8 and
+    # MXFP4 weights, the int8 x int8 path with the norm and quantisation launches of their own (and its int32 partials), k_gemm_rows
+    # (recorded on the parent of the commit that added them, like the others: profiles/gemm_args/README.md)
+    "bf16_b2_ksplit2": ({"MMI_GEMM_KSPLIT": "2"}, lambda d, l: _tiny(d, l, 2, 2)),
+    "fp8": ({}, lambda d, l: _tiny(d, l, 2, 2, quantize="fp8")),
+    "mxfp4": ({}, lambda d, l: _tiny(d, l, 2, 2, cfg=mx.mx_config(), quantize="mxfp4")),
+    "int8_unfused": ({"MMI_NO_NORM_FUSION": "1"}, lambda d, l: _tiny(d, l, 2, 2, quantize=True)),
+    "int8_unfused_ksplit2": ({"MMI_NO_NORM_FUSION": "1", "MMI_GEMM_KSPLIT": "2"}, lambda d, l: _tiny(d, l, 2, 2, quantize=True)),
+    "bf16_rows65": ({}, lambda d, l: _tiny(d, l, 65, 32, max_rows=65)),                # three batch tiles
 }
 # `xkv` comes out of a GEMM: its bytes are the device's arithmetic, not a fill or a host copy
 GEMM_AT_START = ("cross_len3_cap5", "tts_machine")
