@@ -2222,6 +2222,16 @@ __global__ __launch_bounds__(256) void k_lm_attn_split(LmAttnArgs a) {
 // on the scores), the next round's 2 NB loads are issued before this round's arithmetic, and nothing but registers and
 // cross-lane shuffles is touched until the slots and the waves are merged once at the end.
 // KVF: the ring form, as for k_lm_attn_split (1 = e4m3, 2 = E2M1 under block scales: a 2-byte scale load beside each 16-byte load).
+// The 16-byte key and value loads are non-temporal, like every weight stream of the step: a ring row is read by exactly one wave
+// instruction of one workgroup per launch and by nobody else before the next frame, so it need not displace what the caches hold
+// (-0.07 .. -0.09 ms per flagship step, -0.4 ms on full rings; profiles/attn_ramp/README.md).  The query, the offsets, the 4-bit ring's
+// 2-byte scale loads and every store keep the default policy.
+#define MMI_AW_LD16(p) mmi_load_nt(reinterpret_cast<const u32x4*>(p))
+#ifndef MMI_ATTN_STAMP
+#define MMI_ATTN_STAMP(i, dep)       // scripts/attn_stamps.hip defines these three: device-clock stamps at the kernel's stages
+#define MMI_ATTN_STAMP_LANDED(i, first)
+#define MMI_ATTN_STAMP_STORED(i)
+#endif
 template <int DH, int KVF = 0>
 __global__ __launch_bounds__(256, KVF ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a) {      // bf16 ring: <= 128 VGPRs, 4 workgroups per CU
     constexpr bool KV8 = KVF == 1, KV4 = KVF == 2;
@@ -2285,13 +2295,14 @@ __global__ __launch_bounds__(256, KVF ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a)
 #pragma unroll
     for (int i = 0; i < NB; ++i) ksA[i] = vsA[i] = ksB[i] = vsB[i] = 0u;
     const bool early = gridDim.y == 1;
+    MMI_ATTN_STAMP(0, loff)
     if (early) {
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
             const int slot_ = min((wave + i * 4) * RPW + rsub, a.cap - 1);
             const unsigned o_ = (unsigned)slot_ * (unsigned)ROWB + loff;
-            kA[i] = *reinterpret_cast<const u32x4*>(kbase + o_);
-            vA[i] = *reinterpret_cast<const u32x4*>(vbase + o_);
+            kA[i] = MMI_AW_LD16(kbase + o_);
+            vA[i] = MMI_AW_LD16(vbase + o_);
             if constexpr (KV4) {
                 const unsigned so_ = (unsigned)slot_ * (unsigned)(DH / 16) + lsoff;
                 ksA[i] = *reinterpret_cast<const uint16_t*>(ksbase + so_);
@@ -2303,6 +2314,7 @@ __global__ __launch_bounds__(256, KVF ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a)
     // p * v with p = 0, which is 0 only for a finite v: once per launch - not per round - such a value row reads as zeros (4-bit
     // ring: scale byte 0 = the factor 0), so the result does not depend on what an unwritten slot holds (its key only feeds a score
     // that the mask replaces).  Every later load is clamped to L - 1.
+    MMI_ATTN_STAMP(1, L)
     if (early) {
 #pragma unroll
         for (int i = 0; i < NB; ++i)
@@ -2331,8 +2343,8 @@ __global__ __launch_bounds__(256, KVF ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a)
     _Pragma("unroll") for (int i = 0; i < NB; ++i) {                                            \
         const int slot_ = min((wg + ((j0) + i) * total) * RPW + rsub, L - 1);                   \
         const unsigned o_ = (unsigned)slot_ * (unsigned)ROWB + loff;                            \
-        KK[i] = *reinterpret_cast<const u32x4*>(kbase + o_);                                    \
-        VV[i] = *reinterpret_cast<const u32x4*>(vbase + o_);                                    \
+        KK[i] = MMI_AW_LD16(kbase + o_);                                                        \
+        VV[i] = MMI_AW_LD16(vbase + o_);                                                        \
         if constexpr (KV4) {                                                                     \
             const unsigned so_ = (unsigned)slot_ * (unsigned)(DH / 16) + lsoff;                 \
             KS[i] = *reinterpret_cast<const uint16_t*>(ksbase + so_);                           \
@@ -2394,13 +2406,16 @@ __global__ __launch_bounds__(256, KVF ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a)
         if (!early) { MMI_AW_LOAD(kA, vA, ksA, vsA, 0) }
         for (int r = 0; r < nrounds; r += 2) {
             MMI_AW_LOAD(kB, vB, ksB, vsB, (r + 1) * NB)          // clamped past the end: re-reads the last row (cache hit), masked on use
+            MMI_ATTN_STAMP_LANDED(2, r == 0)
             MMI_AW_USE(kA, vA, ksA, vsA, r * NB)
             MMI_AW_LOAD(kA, vA, ksA, vsA, (r + 2) * NB)
             MMI_AW_USE(kB, vB, ksB, vsB, (r + 1) * NB)
         }
     }
+    MMI_ATTN_STAMP(3, l_run)
 #undef MMI_AW_LOAD
 #undef MMI_AW_USE
+#undef MMI_AW_LD16
     // ---- merge the RPW row slots of the wave (lanes that share `seg`): butterflies over the slot bits
 #pragma unroll
     for (int mk = LPR; mk < 64; mk <<= 1) {
@@ -2412,6 +2427,7 @@ __global__ __launch_bounds__(256, KVF ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a)
         for (int e = 0; e < EPL; ++e) acc[e] = acc[e] * sa + mmi_shfl_xor(acc[e], mk) * sb;
         m_run = mn;
     }
+    MMI_ATTN_STAMP(4, l_run)
     // ---- merge the 4 waves through LDS (the only barrier of the kernel)
     MMI_SHARED float wm[4], wl[4];
     MMI_SHARED float wacc[4 * DH];
@@ -2430,8 +2446,10 @@ __global__ __launch_bounds__(256, KVF ? 2 : 4) void k_lm_attn_wave(LmAttnArgs a)
             num += sw * wacc[w * DH + tid];
             den += sw * wl[w];
         }
+        MMI_ATTN_STAMP(5, num)
         if (nsplit == 1) {
             a.out[mmi_xp_index(a.T, b, (bh % a.H) * DH + tid, a.out_ksteps)] = mmi_f32_to_bf16(num / den);
+            MMI_ATTN_STAMP_STORED(6)
         } else {
             a.opart[((long)bh * gridDim.y + blockIdx.y) * DH + tid] = num;
             if (tid == 0) {
