@@ -331,7 +331,10 @@ int plan_conv(const MmiKnobs& k, MmiArena& arena, ConvGemmArgs& a, ConvPlan* p) 
     if (N > 128) {
         if (a.first || a.x_packed || a.out_mode != MMI_GOUT_NATURAL)
             return mmi_fail(MMI_ERR_UNSUPPORTED, "more than 128 columns (sessions x time steps per frame) on a conv with replicate padding or packed "
-                                                 "operands: lower max_batch (the 25 Hz layers of the released codec take 64 sessions)");
+                                                 "operands: lower max_batch (the replicate-padded 12.5 Hz downsample, one column per session, "
+                                                 "caps a codec at 128 sessions; the released codec is capped before that, at 68 sessions, by "
+                                                 "the index range of its 1920-sample frames, and runs its 25 Hz transformers on plain "
+                                                 "buffers above 64)");
         p->wide = true;
         const int nsub = mmi_cdiv(N, 32);
         // m-tiles per wave (each gathered + ELU'd operand element is reused MTB times) vs. waves in flight:

@@ -67,6 +67,45 @@ def test_attention_head_dims_and_ring_wrap(factory, monkeypatch, heads, two_pass
     mimi_cases.oracle_vs_engine(factory, "cpu", cfg, seed=50 + heads, B=2, F=5, K=3)
 
 
+@pytest.mark.parametrize("B", [65, 97, 128])
+def test_tiny_codec_on_the_unpacked_transformer_program(factory, B):
+    """More than 128 columns at 25 Hz (2 per session): `add_transformer` leaves the packed operands - every norm is a
+    k_layernorm_ct launch, the linears run k_conv_wide on plain buffers.  The released codec runs this program at 65-68
+    sessions; the tiny codec's 64 sessions (`test_maximum_batch_sizes`) are still packed."""
+    def make(sd, cfg, K):
+        return factory(sd, cfg, K, max_batch=B)
+    res = mimi_cases.oracle_vs_engine(make, "cpu", tiny_mimi_config(), seed=300 + B, B=B, F=2, K=5)
+    assert res["decisions_differing"] == 0
+    for which in ("encode", "decode"):
+        assert "k_gemm_f32_ln" not in res["kernels"][which] and res["kernels"][which]["k_layernorm_ct"] > 2, res["kernels"]
+
+
+def test_tiny_codec_is_refused_past_128_sessions(factory):
+    """The 12.5 Hz downsample (replicate padding, one column per session) takes 128 columns: 129 sessions are refused by name."""
+    cfg = tiny_mimi_config()
+    m = factory(random_mimi_state_dict(cfg, seed=7), cfg, 5, max_batch=129)
+    with pytest.raises(NotImplementedError, match="lower max_batch"):
+        with m.streaming(129):
+            m.encode(torch.zeros(129, 1, cfg.frame_size))
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("B,rows", [(33, [0, 31, 32])])
+def test_full_size_codec_past_32_sessions(factory, B, rows):
+    """The released codec's own plans above 32 sessions, one frame: 33 (the 32-session table rows with a half-filled tile on the
+    512-channel layers, a third 25 Hz subtile, a second 12.5 Hz subtile of one column).  27-40 s of simulator time alone, 95 s
+    beside five other workers.  65 sessions (the unpacked transformer program; rows 0, 32, 64) pass the same check in 60-90 s
+    alone but took 173 s beside the other workers, too long for this suite: that program runs here on the tiny codec
+    (`test_tiny_codec_on_the_unpacked_transformer_program`) and at full size on the GPU (tests/test_a_mimi_gpu.py)."""
+    from moshi_amd import MimiConfig
+    def make(sd, cfg, K):
+        return factory(sd, cfg, K, max_batch=B)
+    res = mimi_cases.oracle_vs_engine(make, "cpu", MimiConfig(), seed=1234, B=B, F=1, K=8, use_masks=False, oracle_rows=rows)
+    print(f"[parity] mimi full size on the simulator B={B}: {res['decisions_differing']} index decisions differ; worst PCM error "
+          f"{res['worst_pcm_over_tol']:.3f} x tolerance")
+    assert ("k_gemm_f32_ln" in res["kernels"]["encode"]) == (B <= 64)
+
+
 def test_multi_frame_call_equals_frame_by_frame(factory):
     cfg = tiny_mimi_config()
     sd = random_mimi_state_dict(cfg, seed=3)
