@@ -786,6 +786,41 @@ int mmi_lm_score(mmi_lm* lm, const int32_t* sessions, int32_t n, const int64_t* 
 int mmi_lm_debug_score_rows(mmi_lm* lm, const void* logits_bf16, const int32_t* targets, int32_t rows, int32_t N, float* logp,
                             int32_t* argmax, float* logits_f32, mmi_stream stream);
 
+/* ---- log-probabilities of the stored tokens and top-N alternatives in the live step -----------------------------
+ * mmi_lm_enable_logprobs(lm, on, top_n): before streaming_start; top_n in 0..8 alternatives per site.  The stream then runs ONE
+ * more launch per step, k_step_logprob in front of the ring commit (site label "logprob"), on every handle the step works on:
+ * quantised linears and rings, guided streams, cross-attention, adapters, the TTS machine, hooks, the nucleus samplers.  It samples
+ * the tokens it sampled.  The results live in float rings beside the streaming-state arena: mmi_lm_state_bytes and snapshots are
+ * what they were; a handle without the option allocates and launches what it did.
+ *
+ * Per (session, site) - site 0 the text head, sites 1 .. dep_q the audio heads:
+ *   logp      ln softmax(logits)[token] in fp32 on the bf16 logits as they stand when the step commits (after the guidance mix and
+ *             the sampler's written-back padding bonus: what the step's parity taps return), for the token mmi_lm_last_tokens
+ *             returns - after forcing and after the hooks; under the TTS machine the SAMPLED audio token, even where the audio
+ *             rule stores another one.  -inf where the token lies outside the head's range (a forced initial-token id).
+ *             Temperature, penalties, top-k and top-p play no part.  The arithmetic is mmi_lm_score's, bit for bit.
+ *   top_id    the top_n entries first in the order (logit descending, index ascending); top_logp their log-probabilities.
+ *   A NaN logit makes logp NaN (the alternatives are then unspecified).
+ * Two stream-ordered read-outs (no synchronisation), valid until the next step, reset or seek; device outputs logp f32 [G][S],
+ * top_id i32 / top_logp f32 [G][S][top_n] (both or neither; S = 1 + dep_q):
+ *   mmi_lm_last_logprobs   step coordinates: lines up with mmi_lm_last_tokens.  A row that did not execute keeps its last executed
+ *                          step's values; one that has not executed since the start or its reset reads NaN / id -1.
+ *   mmi_lm_frame_logprobs  frame coordinates: lines up with the frame the last mmi_lm_step returned - NaN / -1 exactly where that
+ *                          frame holds -2, and elsewhere the values recorded when the frame's token was sampled.
+ * mmi_lm_reset, mmi_lm_state_load, mmi_lm_seek, mmi_lm_prefill and a committing mmi_lm_score return the rows they name to NaN / -1.
+ * Refusals, before anything is written: MMI_ERR_INVALID for top_n outside 0..8, a NULL logp, or top_* on a handle with top_n == 0;
+ * MMI_ERR_STATE for enabling while streaming and for a read-out on a handle without the option or not streaming.
+ *
+ * mmi_lm_debug_step_logprob: parity tap (tests) - k_step_logprob through the step op's launch function on caller rows: logits_bf16
+ * device bf16 [rows][N], targets device i32 [rows], logp f32 [rows], top_id / top_logp [rows][top_n] or NULL.  MMI_ERR_UNSUPPORTED
+ * for N % 8 != 0, N > 32768 or logits that are not 16-byte aligned.  Any handle; touches no stream state; synchronises. */
+int mmi_lm_enable_logprobs(mmi_lm* lm, int32_t on, int32_t top_n);
+int mmi_lm_logprobs_enabled(const mmi_lm* lm, int32_t* top_n_or_null);      /* 0 / 1; a negative status for a NULL handle */
+int mmi_lm_last_logprobs(mmi_lm* lm, float* logp, int32_t* top_id, float* top_logp, mmi_stream stream);
+int mmi_lm_frame_logprobs(mmi_lm* lm, float* logp, int32_t* top_id, float* top_logp, mmi_stream stream);
+int mmi_lm_debug_step_logprob(mmi_lm* lm, const void* logits_bf16, const int32_t* targets, int32_t rows, int32_t N, int32_t top_n,
+                              float* logp, int32_t* top_id, float* top_logp, mmi_stream stream);
+
 /* The regions of the streaming-state arena - the buffer of mmi_lm_state_save - by name (tests compare two streams region by
  * region): one line "name<TAB>offset<TAB>bytes<TAB>rows<TAB>kind" each.  rows > 0: the region is `rows` equal slices, one per
  * session (model row); kind 1 = state the next step reads ("exec", "offsets", "cache", "text_tok", "audio_tok", "rng", "rowtab",
@@ -961,6 +996,11 @@ int mmi_batcher_step(mmi_batcher* b, int32_t* n_active);
  * Frames produced while the LM's delay ring was still filling (tokens -2, lm.py:781-782) are never queued, exactly
  * like the reference server skips `None` (server.py:144-146). */
 int mmi_batcher_pop(mmi_batcher* b, int64_t channel_id, float* pcm, int64_t* tokens, int32_t* got);
+/* mmi_batcher_pop with the frame's log-probabilities (an LM handle with mmi_lm_enable_logprobs; MMI_ERR_STATE without): host
+ * logp f32 [1 + dep_q], top_id i32 / top_logp f32 [1 + dep_q][top_n] or NULL - mmi_lm_frame_logprobs of the step that produced the
+ * frame.  mmi_batcher_pop drops them with the frame. */
+int mmi_batcher_pop_logprobs(mmi_batcher* b, int64_t channel_id, float* pcm, int64_t* tokens, float* logp, int32_t* top_id,
+                             float* top_logp, int32_t* got);
 int mmi_batcher_get_stats(mmi_batcher* b, mmi_batcher_stats* out);
 
 #ifdef __cplusplus

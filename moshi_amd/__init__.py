@@ -5,8 +5,8 @@ include/moshi_mi.h); this package is the thin host mirror of the reference's Pyt
 """
 from .config import LMConfig, MimiConfig, tiny_lm_config, tiny_mimi_config  # noqa: F401
 from .mimi import MimiModel  # noqa: F401
-from .lm import ConditionFuser, LMGen, LMModel, ScoreOutput, SessionCondition, SessionSampling, TTSMachine, TTSScript, TTSScriptStatus  # noqa: F401
+from .lm import ConditionFuser, LMGen, LMModel, LogProbs, ScoreOutput, SessionCondition, SessionSampling, TTSMachine, TTSScript, TTSScriptStatus  # noqa: F401
 from .batcher import SessionBatcher  # noqa: F401
 
-__all__ = ["MimiConfig", "LMConfig", "MimiModel", "LMModel", "LMGen", "ConditionFuser", "SessionBatcher", "SessionSampling", "SessionCondition", "TTSMachine", "TTSScript", "TTSScriptStatus", "ScoreOutput",
+__all__ = ["MimiConfig", "LMConfig", "MimiModel", "LMModel", "LMGen", "ConditionFuser", "SessionBatcher", "SessionSampling", "SessionCondition", "TTSMachine", "TTSScript", "TTSScriptStatus", "ScoreOutput", "LogProbs",
            "tiny_mimi_config", "tiny_lm_config"]

@@ -22,7 +22,7 @@ import numpy as np
 
 from . import _capi
 from .errors import UnknownChannel  # noqa: F401  (re-exported: callers catch it from here)
-from .lm import LMModel, _apply_nucleus, check_top_p
+from .lm import LMModel, _apply_logprobs, _apply_nucleus, check_top_p
 from .mimi import MimiModel
 
 
@@ -38,7 +38,7 @@ class SessionBatcher:
                  temp_text: float = 0.7, top_k: int = 250, top_k_text: int = 25, seed: int = 0,
                  reset_codec_after_first_frame: bool = True, max_buffered_frames: int = 250, cfg_coef: float = 1.0,
                  cfg_is_no_text: bool = False, cfg_is_masked_until=None, condition_tensors=None, top_p: float = 0.0,
-                 top_p_text: float = 0.0, session_top_p: bool = False):
+                 top_p_text: float = 0.0, session_top_p: bool = False, logprobs: Optional[int] = None):
         assert mimi._lib is lm_model._lib, "both models must live in the same engine library"
         assert not mimi.is_streaming, "the batcher puts the models into streaming mode itself"
         _require_duplex_model(lm_model.config, "SessionBatcher")
@@ -86,6 +86,9 @@ class SessionBatcher:
         # nucleus sampling: the batcher's own values, and whether channels may bring theirs (SessionSampling.top_p, set_channel_top_p)
         check_top_p(top_p, top_p_text)
         self._nucleus = _apply_nucleus(self._lib, lm_model._handle, float(top_p), float(top_p_text), bool(session_top_p))
+        # log-probabilities of every popped frame: None = off, n in 0..8 = on with n alternatives
+        self.logprobs = None if logprobs is None else int(logprobs)
+        _apply_logprobs(self._lib, lm_model._handle, self.logprobs)
         mimi._sync()
         self._lib.check(self._lib.mmi_batcher_create(mimi._handle, lm_model._handle, C.byref(cfg), C.byref(self._handle)))
 
@@ -188,6 +191,20 @@ class SessionBatcher:
         got = C.c_int32(0)
         self._lib.check(self._lib.mmi_batcher_pop(self._handle, int(channel), pcm.ctypes.data, tok.ctypes.data, C.byref(got)))      # MMI_ERR_NO_CHANNEL -> UnknownChannel
         return (pcm, tok) if got.value else None
+
+    def pop_with_logprobs(self, channel: int):
+        """`pop` with the frame's log-probabilities (`SessionBatcher(logprobs=n)`): (pcm, tokens, logp f32 [1 + dep_q], top_ids i64
+        [1 + dep_q, n], top_logp f32 [1 + dep_q, n]) or None - `LMGen.frame_logprobs()` of the step that produced the frame."""
+        n = self.logprobs or 0
+        pcm = np.empty(self.frame_size, dtype=np.float32)
+        tok = np.empty(self.n_tokens, dtype=np.int64)
+        logp = np.empty(self.n_tokens, dtype=np.float32)
+        ids = np.empty((self.n_tokens, n), dtype=np.int32)
+        tlp = np.empty((self.n_tokens, n), dtype=np.float32)
+        got = C.c_int32(0)
+        self._lib.check(self._lib.mmi_batcher_pop_logprobs(self._handle, int(channel), pcm.ctypes.data, tok.ctypes.data, logp.ctypes.data,
+                                                           ids.ctypes.data if n else None, tlp.ctypes.data if n else None, C.byref(got)))
+        return (pcm, tok, logp, ids.astype(np.int64), tlp) if got.value else None
 
     # ---- model loop ----------------------------------------------------------------------------------
     def step(self) -> int:

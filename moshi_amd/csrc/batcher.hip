@@ -20,6 +20,8 @@ namespace {
 struct OutFrame {
     std::vector<float> pcm;
     std::vector<int64_t> tokens;
+    std::vector<float> logp, top_logp;       // mmi_lm_frame_logprobs of the frame's step (an LM handle with the option), else empty
+    std::vector<int32_t> top_id;
 };
 
 struct Channel {                 // batched_asr.rs:61-69
@@ -127,6 +129,12 @@ struct mmi_batcher {
     std::vector<uint8_t> row_has_top_p;  // the row currently holds a channel's own top_p
     struct TopPPlan { int what; float top_p, top_p_text; };   // what: 0 nothing, 1 the channel's values, 2 the handle's again
     std::vector<TopPPlan> top_p_plan;
+    // log-probabilities (mmi_lm_enable_logprobs on the LM handle): the frame read-out of every step, device and pinned host
+    bool lp_on = false;
+    int lp_top_n = 0;
+    float *d_lp = nullptr, *h_lp = nullptr;           // [B][NTOK]
+    int32_t *d_lp_id = nullptr, *h_lp_id = nullptr;   // [B][NTOK][top_n]
+    float *d_lp_top = nullptr, *h_lp_top = nullptr;
     int64_t next_id = 1;
     mmi_batcher_stats stats;
 };
@@ -154,6 +162,8 @@ void release(mmi_batcher* b) {
     if (b->h_cond) hipHostFree(b->h_cond);
     if (b->d_cond) hipFree(b->d_cond);
     if (b->d_def) hipFree(b->d_def);
+    for (void* p : {(void*)b->d_lp, (void*)b->d_lp_id, (void*)b->d_lp_top}) if (p) hipFree(p);
+    for (void* p : {(void*)b->h_lp, (void*)b->h_lp_id, (void*)b->h_lp_top}) if (p) hipHostFree(p);
     if (b->ev_begin) hipEventDestroy(b->ev_begin);
     if (b->ev_end) hipEventDestroy(b->ev_end);
     if (b->stream) hipStreamDestroy(b->stream);
@@ -197,6 +207,20 @@ int create_impl(mmi_batcher* b) {
     memset(hd, 0, probe.d2h_bytes);
     MMI_HIP_CHECK(hipMalloc((void**)&b->d_codes, (size_t)B * b->K * sizeof(int64_t)));
     MMI_HIP_CHECK(hipMalloc((void**)&b->d_dec_codes, (size_t)B * (b->dep_q > 0 ? b->dep_q : 1) * sizeof(int64_t)));
+    int32_t lp_top_n = 0;
+    b->lp_on = mmi_lm_logprobs_enabled(b->lm, &lp_top_n) == 1;
+    b->lp_top_n = b->lp_on ? lp_top_n : 0;
+    if (b->lp_on) {
+        const size_t n = (size_t)B * b->NTOK;
+        MMI_HIP_CHECK(hipMalloc((void**)&b->d_lp, n * sizeof(float)));
+        MMI_HIP_CHECK(hipHostMalloc((void**)&b->h_lp, n * sizeof(float), 0));
+        if (b->lp_top_n) {
+            MMI_HIP_CHECK(hipMalloc((void**)&b->d_lp_id, n * b->lp_top_n * sizeof(int32_t)));
+            MMI_HIP_CHECK(hipHostMalloc((void**)&b->h_lp_id, n * b->lp_top_n * sizeof(int32_t), 0));
+            MMI_HIP_CHECK(hipMalloc((void**)&b->d_lp_top, n * b->lp_top_n * sizeof(float)));
+            MMI_HIP_CHECK(hipHostMalloc((void**)&b->h_lp_top, n * b->lp_top_n * sizeof(float), 0));
+        }
+    }
     // streaming_forever(batch) on both models (server.py:59-60)
     if ((rc = mmi_mimi_streaming_start(b->mimi, B, b->stream))) return rc;
     b->models_streaming = true;
@@ -500,6 +524,15 @@ extern "C" int mmi_batcher_step(mmi_batcher* b, int32_t* n_active) {
     if (firsts && (rc = mmi_mimi_reset(b->mimi, d.first, s))) return rc;   // server.py:135-141
     int valid = 0;
     if ((rc = mmi_lm_step(b->lm, b->d_codes, b->K, d.tokens, nullptr, nullptr, nullptr, B, &valid, s))) return rc;
+    if (b->lp_on) {       // the frame's log-probabilities, lined up with d.tokens
+        const size_t n = (size_t)B * b->NTOK;
+        if ((rc = mmi_lm_frame_logprobs(b->lm, b->d_lp, b->d_lp_id, b->d_lp_top, s))) return rc;
+        MMI_HIP_CHECK(hipMemcpyAsync(b->h_lp, b->d_lp, n * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (b->lp_top_n) {
+            MMI_HIP_CHECK(hipMemcpyAsync(b->h_lp_id, b->d_lp_id, n * b->lp_top_n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            MMI_HIP_CHECK(hipMemcpyAsync(b->h_lp_top, b->d_lp_top, n * b->lp_top_n * sizeof(float), hipMemcpyDeviceToHost, s));
+        }
+    }
     MMI_LAUNCH(k_batcher_route, mmi_cdiv(B, 64), 64, 0, s, (const long*)d.tokens, (const uint8_t*)d.exec, d.played,
                (long*)b->d_dec_codes, B, b->dep_q, b->card);
     MMI_CHECK_LAUNCH();
@@ -528,15 +561,40 @@ extern "C" int mmi_batcher_step(mmi_batcher* b, int32_t* n_active) {
             OutFrame f;
             f.pcm.assign(h.pcm_out + (size_t)r * F, h.pcm_out + (size_t)(r + 1) * F);
             f.tokens.assign(h.tokens + (size_t)r * b->NTOK, h.tokens + (size_t)(r + 1) * b->NTOK);
+            if (b->lp_on) {
+                const size_t n = (size_t)b->NTOK, m = n * b->lp_top_n;
+                f.logp.assign(b->h_lp + r * n, b->h_lp + (r + 1) * n);
+                if (m) {
+                    f.top_id.assign(b->h_lp_id + r * m, b->h_lp_id + (r + 1) * m);
+                    f.top_logp.assign(b->h_lp_top + r * m, b->h_lp_top + (r + 1) * m);
+                }
+            }
             c.out.push_back(std::move(f));
         }
     }
     return MMI_OK;
 }
 
+static int pop_frame(mmi_batcher* b, int64_t channel_id, float* pcm, int64_t* tokens, float* logp, int32_t* top_id, float* top_logp, int32_t* got);
+
 extern "C" int mmi_batcher_pop(mmi_batcher* b, int64_t channel_id, float* pcm, int64_t* tokens, int32_t* got) {
     MmiDeviceGuard dev_guard_(b ? mmi_lm_device(b->lm) : -1);
     if (!b || !got) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    return pop_frame(b, channel_id, pcm, tokens, nullptr, nullptr, nullptr, got);
+}
+
+extern "C" int mmi_batcher_pop_logprobs(mmi_batcher* b, int64_t channel_id, float* pcm, int64_t* tokens, float* logp, int32_t* top_id,
+                                        float* top_logp, int32_t* got) {
+    MmiDeviceGuard dev_guard_(b ? mmi_lm_device(b->lm) : -1);
+    if (!b || !got) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (!logp) return mmi_fail(MMI_ERR_INVALID, "mmi_batcher_pop_logprobs: logp must not be null");
+    if (!b->lp_on) return mmi_fail(MMI_ERR_STATE, "mmi_batcher_pop_logprobs: log-probabilities are not enabled (mmi_lm_enable_logprobs before mmi_batcher_create)");
+    if ((top_id || top_logp) && b->lp_top_n == 0)
+        return mmi_fail(MMI_ERR_INVALID, "mmi_batcher_pop_logprobs: the handle records no alternatives (top_n == 0)");
+    return pop_frame(b, channel_id, pcm, tokens, logp, top_id, top_logp, got);
+}
+
+static int pop_frame(mmi_batcher* b, int64_t channel_id, float* pcm, int64_t* tokens, float* logp, int32_t* top_id, float* top_logp, int32_t* got) {
     std::lock_guard<std::mutex> g(b->mu);
     Channel* c = find_channel(b, channel_id);
     if (!c) return mmi_fail(MMI_ERR_NO_CHANNEL, "unknown channel");
@@ -545,6 +603,9 @@ extern "C" int mmi_batcher_pop(mmi_batcher* b, int64_t channel_id, float* pcm, i
     OutFrame& f = c->out.front();
     if (pcm) std::copy(f.pcm.begin(), f.pcm.end(), pcm);
     if (tokens) std::copy(f.tokens.begin(), f.tokens.end(), tokens);
+    if (logp) std::copy(f.logp.begin(), f.logp.end(), logp);
+    if (top_id) std::copy(f.top_id.begin(), f.top_id.end(), top_id);
+    if (top_logp) std::copy(f.top_logp.begin(), f.top_logp.end(), top_logp);
     c->out.pop_front();
     *got = 1;
     return MMI_OK;

@@ -5,6 +5,7 @@
 #include "lm_kernels.h"
 #include "lm_prefill_kernels.h"
 #include "lm_score_kernels.h"
+#include "lm_logprob_kernels.h"
 #include "mmi_graph.h"
 
 #include <math.h>
@@ -255,6 +256,12 @@ struct mmi_lm {
         uint16_t *dkc = nullptr, *dvc = nullptr;        // [dep_layers][rows][Hd][dep_q][Dhd]
         uint16_t* alog = nullptr;       // [dep_q][rows][card] bf16 audio logits
     } sc;
+    // log-probabilities in the live step (mmi_lm_enable_logprobs): the option belongs to the handle, the float rings
+    // to the stream - an arena of its own beside the streaming-state arena, so that mmi_lm_state_bytes and snapshots are what they were
+    bool lp_on = false;
+    int lp_top_n = 0;
+    MmiArena lp_mem;
+    LpRings lp{nullptr, nullptr, nullptr, 0, 0};    // lp.lp != null: this stream records them
     long offset_cpu = 0;
     int attn_ns = 1;                                // workgroups per (session, head) of the decode attention (attn_splits)
     long depth_bound = 0;                           // no session's offset exceeds this (steps since streaming_start / the last seek; resets
@@ -1359,6 +1366,37 @@ TokArgs tok_args(mmi_lm* lm) {
     return t;
 }
 
+// k_step_logprob: the op of the step program (and mmi_lm_debug_step_logprob, on caller rows)
+int launch_step_logprob(hipStream_t s, const LpArgs& a, int rows) {
+    MMI_LAUNCH(k_step_logprob, dim3(rows, a.r.sites), MMI_SCORE_THREADS, 0, s, a);
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+
+LpArgs step_logprob_args(mmi_lm* lm) {
+    const mmi_lm_cfg& c = lm->cfg;
+    LpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.t = tok_args(lm);
+    a.text_logits = lm->text_logits; a.text_N = c.text_card_out;
+    a.dlogits = lm->dlogits; a.dstride = (long)lm->batch * c.card; a.card = c.card;
+    a.text_tok = lm->text_tok; a.audio_tok = lm->audio_tok;
+    a.r = lm->lp;
+    return a;
+}
+
+// the rings of the stream's rows back to NaN / -1: by mmi_lm_reset's device mask (null = every row), or the n rows `sess`
+int clear_logprobs(mmi_lm* lm, hipStream_t s, const uint8_t* mask, const uint8_t* sess = nullptr, int n = -1) {
+    if (!lm->lp.lp) return MMI_OK;
+    LpClear c;
+    memset(&c, 0, sizeof(c));
+    c.r = lm->lp; c.CT = lm->CT; c.n = n; c.mask = mask;
+    if (n > 0) memcpy(c.sess, sess, (size_t)n);
+    MMI_LAUNCH(k_lp_clear, n >= 0 ? n : lm->gen_batch, 256, 0, s, c);
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+
 int build_program(mmi_lm* lm) {
     const mmi_lm_cfg& c = lm->cfg;
     const int B = lm->batch, d = c.dim, H = c.num_heads, Dh = d / H;
@@ -1584,8 +1622,15 @@ int build_program(mmi_lm* lm) {
         add_sample(lm, lg, c.card, c.card, false, 1 + k, lm->audio_tok + k, c.dep_q, grouped && k + 1 < c.dep_q ? k + 1 : -1);
     }
     // ---- token ring out
-    P.site("commit");
+    // log-probabilities of the tokens the commit is about to store (an enabled handle): one launch, and the hooked step's cut in
+    // front of it, so that it sees the tokens on_text_token / on_audio_tokens left
     lm->op_commit = P.ops.size();
+    if (lm->lp.lp) {
+        P.site("logprob");
+        const LpArgs la = step_logprob_args(lm);
+        P.add([=](hipStream_t s) { return launch_step_logprob(s, la, la.t.B); });
+    }
+    P.site("commit");
     {
         TokArgs t = tok_args(lm);
         const int *tt = lm->text_tok, *at = lm->audio_tok; int* out = lm->out_i32; unsigned long long* rng = lm->rng;
@@ -2094,6 +2139,19 @@ static void prefill_table(mmi_lm* lm, BufTable& t) {
     t.add(&P.partial, (size_t)4 * rows * d, "pf.partial");
 }
 
+// the float rings of an enabled handle's stream: an arena of its own, see mmi_lm::lp_mem
+static int logprobs_alloc(mmi_lm* lm, hipStream_t s) {
+    const size_t n = (size_t)lm->gen_batch * (1 + lm->cfg.dep_q) * lm->CT;
+    LpRings r{nullptr, nullptr, nullptr, 1 + lm->cfg.dep_q, lm->lp_top_n};
+    lm->lp_mem.poison = lm->st.poison;
+    hipError_t e = lm->lp_mem.alloc(&r.lp, n);
+    if (e == hipSuccess && r.top_n) e = lm->lp_mem.alloc(&r.top_id, n * r.top_n);
+    if (e == hipSuccess && r.top_n) e = lm->lp_mem.alloc(&r.top_lp, n * r.top_n);
+    if (e != hipSuccess) return mmi_fail(MMI_ERR_HIP, "out of device memory (log-probability rings)");
+    lm->lp = r;
+    return clear_logprobs(lm, s, nullptr);
+}
+
 // the scratch of a stream's prefill passes (and of its scoring): an arena of its own, see mmi_lm::pf_mem
 static int prefill_alloc(mmi_lm* lm, hipStream_t s) {
     int rc = prefill_refusal(lm, lm->prefill_rows);           // (adapters or the TTS machine may have been enabled after the prefill was)
@@ -2322,6 +2380,7 @@ extern "C" int mmi_lm_prefill(mmi_lm* lm, const int32_t* sessions, int32_t n, co
         const int rc = prefill_pass(lm, s, p, user_codes, tokens);
         if (rc) return rc;
     }
+    if (const int rc = clear_logprobs(lm, s, nullptr, p.sess, n)) return rc;      // given tokens: nothing was sampled
     lm->offset_cpu += T;
     if (lm->depth_bound < (1L << 40)) lm->depth_bound += T;
     return MMI_OK;
@@ -2382,6 +2441,7 @@ extern "C" int mmi_lm_score(mmi_lm* lm, const int32_t* sessions, int32_t n, cons
         if (rc) return rc;
     }
     if (commit) {
+        if (const int rc = clear_logprobs(lm, s, nullptr, p.sess, n)) return rc;
         lm->offset_cpu += T;
         if (lm->depth_bound < (1L << 40)) lm->depth_bound += T;
     }
@@ -2416,6 +2476,45 @@ extern "C" int mmi_lm_last_tokens(mmi_lm* lm, int64_t* out, mmi_stream stream) {
     MMI_LAUNCH(k_pf_last_tokens, mmi_cdiv(G * (1 + q), 256), 256, 0, (hipStream_t)stream, (const int*)lm->text_tok, (const int*)lm->audio_tok, G, q, (long*)out);
     MMI_CHECK_LAUNCH();
     return MMI_OK;
+}
+
+// ---- log-probabilities in the live step -------------------------------------------------------------------------
+extern "C" int mmi_lm_enable_logprobs(mmi_lm* lm, int32_t on, int32_t top_n) {
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (top_n < 0 || top_n > MMI_LP_MAX_TOP) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_enable_logprobs: top_n must lie in [0, 8]");
+    if (lm->streaming) return mmi_fail(MMI_ERR_STATE, "mmi_lm_enable_logprobs: not while streaming");
+    lm->lp_on = on != 0;
+    lm->lp_top_n = on ? top_n : 0;
+    return MMI_OK;
+}
+
+extern "C" int mmi_lm_logprobs_enabled(const mmi_lm* lm, int32_t* top_n_or_null) {
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (top_n_or_null) *top_n_or_null = lm->lp_top_n;
+    return lm->lp_on ? 1 : 0;
+}
+
+static int read_logprobs(mmi_lm* lm, const char* who, int frame, float* logp, int32_t* top_id, float* top_logp, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (!logp) return mmi_fail(MMI_ERR_INVALID, std::string(who) + ": logp must not be null");
+    if (!lm->lp_on) return mmi_fail(MMI_ERR_STATE, std::string(who) + ": log-probabilities are not enabled (mmi_lm_enable_logprobs before streaming_start)");
+    if (!lm->streaming || !lm->lp.lp) return mmi_fail(MMI_ERR_STATE, "not streaming");
+    if ((top_id || top_logp) && lm->lp.top_n == 0)
+        return mmi_fail(MMI_ERR_INVALID, std::string(who) + ": the handle records no alternatives (top_n == 0)");
+    if ((top_id == nullptr) != (top_logp == nullptr)) return mmi_fail(MMI_ERR_INVALID, std::string(who) + ": top_id and top_logp go together");
+    const int n = lm->gen_batch * lm->lp.sites;
+    MMI_LAUNCH(k_lp_read, mmi_cdiv(n, 256), 256, 0, (hipStream_t)stream, tok_args(lm), lm->lp, (const int*)lm->out_i32, frame, logp, top_id, top_logp);
+    MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+
+extern "C" int mmi_lm_last_logprobs(mmi_lm* lm, float* logp, int32_t* top_id, float* top_logp, mmi_stream stream) {
+    return read_logprobs(lm, "mmi_lm_last_logprobs", 0, logp, top_id, top_logp, stream);
+}
+
+extern "C" int mmi_lm_frame_logprobs(mmi_lm* lm, float* logp, int32_t* top_id, float* top_logp, mmi_stream stream) {
+    return read_logprobs(lm, "mmi_lm_frame_logprobs", 1, logp, top_id, top_logp, stream);
 }
 
 // The regions of the streaming-state arena (mmi_lm_state_save's buffer) by name: "name<TAB>offset<TAB>bytes<TAB>rows<TAB>kind" per
@@ -2487,6 +2586,35 @@ struct TapScratch {
     }
 };
 }  // namespace
+
+// Parity tap of the step's log-probability op (include/moshi_mi.h): k_step_logprob through launch_step_logprob - the launch function
+// of the step program's op - on caller rows: one site of width N, every row executing, a ring of one slot, which is the caller's
+// [rows] / [rows][top_n] layout.  Alternatives the caller does not take land in scratch of the tap's own.
+extern "C" int mmi_lm_debug_step_logprob(mmi_lm* lm, const void* logits_bf16, const int32_t* targets, int32_t rows, int32_t N, int32_t top_n,
+                                         float* logp, int32_t* top_id, float* top_logp, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm || !logits_bf16 || !targets) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    if (!logp) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_step_logprob: logp must not be null");
+    if (top_n < 0 || top_n > MMI_LP_MAX_TOP) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_step_logprob: top_n must lie in [0, 8]");
+    if ((top_id || top_logp) && top_n == 0) return mmi_fail(MMI_ERR_INVALID, "mmi_lm_debug_step_logprob: no alternatives were asked for (top_n == 0)");
+    if (rows < 1 || rows > (1 << 20)) return mmi_fail(MMI_ERR_SHAPE, "mmi_lm_debug_step_logprob: 1 <= rows <= 2^20");
+    if (N < 8 || N % 8 || N > 8 * MMI_SCORE_THREADS * MMI_SCORE_PIECES)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_step_logprob: N must be a multiple of 8 in [8, 32768]");
+    if ((uintptr_t)logits_bf16 % 16 || (uintptr_t)targets % 4 || (uintptr_t)logp % 4 || (uintptr_t)top_id % 4 || (uintptr_t)top_logp % 4)
+        return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_debug_step_logprob: the logits must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    TapScratch scratch(lm, s, "mmi_lm_debug_step_logprob");
+    int rc;
+    if (top_n && !top_id && (rc = scratch.alloc(&top_id, (size_t)rows * top_n))) return rc;
+    if (top_n && !top_logp && (rc = scratch.alloc(&top_logp, (size_t)rows * top_n))) return rc;
+    LpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.t.CT = 1; a.t.B = rows;
+    a.text_logits = (const uint16_t*)logits_bf16; a.text_N = N;
+    a.text_tok = targets;
+    a.r = LpRings{logp, top_id, top_logp, 1, top_n};
+    return launch_step_logprob(s, a, rows);
+}
 
 // Parity tap of the prefill attention (include/moshi_mi.h): launch_attn_prefill - the attention op of a pass - on caller-supplied
 // operands, with a packed output of its own.  Nothing of the handle but its device and its poison knob is read.
@@ -2711,6 +2839,7 @@ extern "C" int mmi_lm_streaming_start_guided(mmi_lm* lm, int32_t batch, const mm
             for (int r = 0; lm->cross_cap != lm->cross_len && r < B && !rc; ++r)
                 rc = project_cross_source(lm, src + (size_t)r * lm->cross_len * d, (size_t)r * lm->cross_cap, lm->cross_len, s);
         }
+        if (!rc && lm->lp_on) rc = logprobs_alloc(lm, s);
         if (!rc) rc = build_program(lm);
         if (!rc && lm->prefill_rows > 0) rc = prefill_alloc(lm, s);
         if (rc) return rc;
@@ -2743,6 +2872,8 @@ extern "C" int mmi_lm_streaming_stop(mmi_lm* lm) {
     lm->prog.clear();
     lm->st.release();
     lm->pf_mem.release();
+    lm->lp_mem.release();
+    lm->lp = LpRings{nullptr, nullptr, nullptr, 0, 0};
     for (BufTable* t : {&lm->st_table, &lm->pf_table}) {      // no member keeps pointing into the freed arenas
         for (BufDecl& e : *t) *e.slot = nullptr;
         t->clear();
@@ -2777,6 +2908,8 @@ extern "C" int mmi_lm_reset(mmi_lm* lm, const uint8_t* mask, mmi_stream stream) 
     TokArgs t = tok_args(lm);
     MMI_LAUNCH(k_lm_reset, mmi_cdiv(lm->gen_batch, 64), 64, 0, (hipStream_t)stream, t, mask, lm->exec);
     MMI_CHECK_LAUNCH();
+    const int rc = clear_logprobs(lm, (hipStream_t)stream, mask);
+    if (rc) return rc;
     lm->offset_cpu = 0;   // lm.py:540: any reset, even partial, zeroes the host-side step counter
     return MMI_OK;
 }
@@ -3463,7 +3596,7 @@ extern "C" int mmi_lm_state_load(mmi_lm* lm, const void* src, int64_t bytes, int
     }
     lm->forced_armed = false;
     lm->noise_on = true;               // the snapshot carries its own use_noise word: the next step rewrites it
-    return MMI_OK;
+    return clear_logprobs(lm, (hipStream_t)stream, nullptr);      // a snapshot carries no log-probabilities
 }
 
 extern "C" int mmi_lm_extra_heads(mmi_lm* lm, float* probs, mmi_stream stream) {
@@ -3509,7 +3642,7 @@ extern "C" int mmi_lm_seek(mmi_lm* lm, const int64_t* offsets, mmi_stream stream
     if (lm->offsets_m != lm->offsets) MMI_HIP_CHECK(hipMemcpy(lm->offsets_m, off.data(), (size_t)lm->batch * sizeof(long), hipMemcpyHostToDevice));
     lm->offset_cpu = mx;
     lm->depth_bound = mx;
-    return MMI_OK;
+    return clear_logprobs(lm, s, nullptr);
 }
 
 // Test aids of the KV ring (include/moshi_mi.h)

@@ -3202,6 +3202,14 @@ __global__ void k_lm_prepare(TokArgs t, const int* __restrict__ user, int n_user
     tokens[idx] = tok;
 }
 
+// The ring slots of a row whose offset, the step's included, is off_new: where the step's tokens are stored, and (declaring `i`)
+// where site c of the returned frame is gathered.  k_step_logprob / k_lp_read (lm_logprob_kernels.h) keep their float rings by
+// the same two.  The gather is a macro: as an inline function it moved two instructions of k_lm_commit's code.
+__device__ __forceinline__ int mmi_ring_store_slot(long off_new, int CT) { return (int)(off_new % CT); }
+#define MMI_RING_FRAME_SLOT(i, t, off_new, c)                   \
+    long i = ((off_new) - (t).max_delay + (t).delays[c]) % (t).CT; \
+    if (i < 0) i += (t).CT
+
 // 4./5. advance offsets, store the sampled tokens, gather the delayed output frame
 __global__ void k_lm_commit(TokArgs t, const int* __restrict__ text_tok, const int* __restrict__ audio_tok,
                             int* __restrict__ out, unsigned long long* __restrict__ rng) {
@@ -3211,7 +3219,7 @@ __global__ void k_lm_commit(TokArgs t, const int* __restrict__ text_tok, const i
     const bool ex = t.exec[b] != 0;
     const long off_new = t.offsets[b] + (ex ? 1 : 0);
     t.offsets[b] = off_new;
-    const int pos = (int)(off_new % t.CT);
+    const int pos = mmi_ring_store_slot(off_new, t.CT);
     int* rows = t.cache + (long)b * t.NC * t.CT;
     if (ex) {
         const int tt = text_tok[b];
@@ -3232,8 +3240,7 @@ __global__ void k_lm_commit(TokArgs t, const int* __restrict__ text_tok, const i
     }
     const bool hide = off_new <= (long)t.max_delay || !ex;
     for (int c = 0; c <= t.dep_q; ++c) {
-        long i = (off_new - t.max_delay + t.delays[c]) % t.CT;
-        if (i < 0) i += t.CT;
+        MMI_RING_FRAME_SLOT(i, t, off_new, c);
         int v = rows[c * t.CT + (int)i];
         out[(long)b * (t.dep_q + 1) + c] = hide ? -2 : v;
     }

@@ -410,6 +410,23 @@ class LMModel:
                                                           _capi.stream_ptr(self.device)))
         return logp, argmax, wide
 
+    def debug_step_logprob(self, logits: torch.Tensor, targets: torch.Tensor, top_n: int = 0) -> "LogProbs":
+        """Parity tap (tests; `mmi_lm_debug_step_logprob`): the log-probability op of the step alone, through its launch function.
+        `logits` bf16 [rows, N] (N a multiple of 8, at most 32768), `targets` int32 [rows].  Returns LogProbs with logp f32 [rows],
+        top_ids i64 / top_logp f32 [rows, top_n]."""
+        logits = logits.to(device=self.device, dtype=torch.bfloat16).contiguous()
+        rows, N = logits.shape
+        targets = targets.to(device=self.device, dtype=torch.int32).contiguous()
+        assert targets.shape == (rows,), "one token per row"
+        logp = torch.empty(rows, dtype=torch.float32, device=self.device)
+        ids = torch.empty(rows, int(top_n), dtype=torch.int32, device=self.device)
+        tlp = torch.empty(rows, int(top_n), dtype=torch.float32, device=self.device)
+        some = 0 < int(top_n) <= 8
+        self._lib.check(self._lib.mmi_lm_debug_step_logprob(self._handle, logits.data_ptr(), targets.data_ptr(), rows, N, int(top_n),
+                                                            logp.data_ptr(), ids.data_ptr() if some else None,
+                                                            tlp.data_ptr() if some else None, _capi.stream_ptr(self.device)))
+        return LogProbs(logp, ids.to(torch.int64), tlp)
+
     def debug_linear(self, weight_name: str, x: torch.Tensor, path: str = "plain", alpha_name: Optional[str] = None,
                      want_codes: bool = False) -> dict:
         """Parity tap (tests; `mmi_lm_debug_linear`): ONE linear of the model - the module stored under `weight_name`, i.e.
@@ -618,6 +635,22 @@ class SessionCondition:
 
 
 @dataclass
+class LogProbs:
+    """What `LMGen.last_logprobs` / `LMGen.frame_logprobs` return; site 0 is the text head, sites 1 .. dep_q the
+    audio heads, n the alternatives the stream records."""
+    logp: torch.Tensor                       # f32 [B, 1 + dep_q]: ln softmax(logits)[stored token]; -inf outside the head's range; NaN = nothing recorded
+    top_ids: torch.Tensor                    # i64 [B, 1 + dep_q, n]: the first n in the order (logit descending, index ascending); -1 = nothing recorded
+    top_logp: torch.Tensor                   # f32 [B, 1 + dep_q, n]
+
+
+def _apply_logprobs(lib, handle, logprobs: Optional[int]) -> None:
+    """`logprobs=None | 0..8` onto the handle, before a stream starts (the option belongs to the handle, like the TTS machine)."""
+    if logprobs is None and not hasattr(lib.cdll, "mmi_lm_enable_logprobs"):
+        return                                            # an older build of the engine has nothing to switch off
+    lib.check(lib.mmi_lm_enable_logprobs(handle, 0 if logprobs is None else 1, 0 if logprobs is None else int(logprobs)))
+
+
+@dataclass
 class ScoreOutput:
     """What `LMGen.score` returns for n sessions and T frames; site 0 is the text head, sites 1 .. dep_q the audio heads."""
     logp: torch.Tensor                       # f32 [n, 1 + dep_q, T]: ln softmax(logits)[given token]; -inf outside the head's range
@@ -697,8 +730,10 @@ class LMGen:
                  condition_tensors=None, on_text_hook=None, on_text_logits_hook=None, on_audio_hook=None,
                  support_out_of_sync: bool = False, cfg_is_masked_until=None, cfg_is_no_text: bool = False,
                  seed: int = 0, tts_machine: Optional[TTSMachine] = None, top_p: float = 0.0, top_p_text: float = 0.0,
-                 session_top_p: bool = False):
+                 session_top_p: bool = False, logprobs: Optional[int] = None):
         assert not lm_model.training, "generation shouldn't be used in training mode."
+        # log-probabilities of the stored tokens in the live step: None = off, n in 0..8 = on with n alternatives
+        self.logprobs = None if logprobs is None else int(logprobs)
         # nucleus sampling (sampling.py:97-98: top_p > 0 overrides top_k): the stream runs the nucleus samplers iff a value is
         # positive or `session_top_p` asks for them (sessions then get their own values with `set_session_top_p`)
         check_top_p(top_p, top_p_text)
@@ -799,6 +834,7 @@ class LMGen:
         elif hasattr(self._lib.cdll, "mmi_lm_enable_tts_machine"):       # (an older build of the engine has no machine to switch off)
             self._lib.check(self._lib.mmi_lm_enable_tts_machine(lm._handle, None, 0, 0, 0))
         self._nucleus = _apply_nucleus(self._lib, lm._handle, self.top_p, self.top_p_text, self.session_top_p)
+        _apply_logprobs(self._lib, lm._handle, self.logprobs)
         if self.device.type == "cuda":
             torch.cuda.current_stream(self.device).synchronize()
         self._lib.check(self._lib.mmi_lm_streaming_start_guided(lm._handle, int(batch_size), C.byref(s), C.byref(g), self._stream()))
@@ -1228,6 +1264,26 @@ class LMGen:
         out = torch.empty(self._batch, 1 + self.lm_model.dep_q, dtype=torch.int64, device=self.device)
         self._lib.check(self._lib.mmi_lm_last_tokens(self.lm_model._handle, out.data_ptr(), self._stream()))
         return out
+
+    def _logprobs(self, call) -> LogProbs:
+        assert self.is_streaming
+        B, S, n = self._batch, 1 + self.lm_model.dep_q, self.logprobs or 0
+        logp = torch.empty(B, S, dtype=torch.float32, device=self.device)
+        ids = torch.empty(B, S, n, dtype=torch.int32, device=self.device)
+        tlp = torch.empty(B, S, n, dtype=torch.float32, device=self.device)
+        self._lib.check(call(self.lm_model._handle, logp.data_ptr(), ids.data_ptr() if n else None, tlp.data_ptr() if n else None,
+                             self._stream()))
+        return LogProbs(logp, ids.to(torch.int64), tlp)
+
+    def last_logprobs(self) -> LogProbs:
+        """Step coordinates (`LMGen(logprobs=n)`): lines up with `last_tokens()`.  A session that did not execute keeps its last
+        executed step's values; one that has not executed since the start or its reset reads NaN / -1."""
+        return self._logprobs(self._lib.mmi_lm_last_logprobs)
+
+    def frame_logprobs(self) -> LogProbs:
+        """Frame coordinates: lines up with the frame the last `step` returned - NaN / -1 exactly where that frame holds -2
+        (`step` then returned None for the batch, or the session did not execute)."""
+        return self._logprobs(self._lib.mmi_lm_frame_logprobs)
 
     @torch.no_grad()
     def step(self, input_tokens: torch.Tensor, depformer_replace_tokens: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
