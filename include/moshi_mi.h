@@ -127,6 +127,14 @@ int mmi_mimi_reset(mmi_mimi* m, const uint8_t* mask_or_null, mmi_stream stream);
 int64_t mmi_mimi_state_bytes(const mmi_mimi* m);
 int mmi_mimi_state_save(mmi_mimi* m, void* dst, int64_t bytes, mmi_stream stream);
 int mmi_mimi_state_load(mmi_mimi* m, const void* src, int64_t bytes, mmi_stream stream);
+/* Fork session `src` into the sessions dst[0 .. n_dst) of the same stream (dst: a host array).  No reference counterpart: the
+ * nearest is get_streaming_state / set_streaming_state on a batch of one (streaming.py:158-181); a whole-handle snapshot cannot
+ * place one session's state into another slot.  Stream-ordered (no host synchronisation): after the call each destination is the
+ * session `src` is - conv histories, conv-transpose partials, both transformer offsets and the valid rows of both KV rings,
+ * the replicate-padding flag - its previous state is gone as after mmi_mimi_reset, and its exec bit is 1.  MMI_ERR_STATE when
+ * not streaming; MMI_ERR_INVALID for src or a dst outside [0, batch), dst == src, a repeated dst, n_dst outside [1, 16]; a
+ * refused call changes nothing. */
+int mmi_mimi_fork_session(mmi_mimi* m, int32_t src, const int32_t* dst, int32_t n_dst, mmi_stream stream);
 
 /* MimiModel.encode in streaming mode (compression.py:376-388, 338-374):
  * pcm f32 [batch,1,n_frames*frame_size] -> codes i64 [batch,num_codebooks,n_frames]. */
@@ -310,6 +318,19 @@ int mmi_lm_state_load(mmi_lm* lm, const void* src, int64_t bytes, int64_t host_w
 int mmi_lm_streaming_stop(mmi_lm* lm);
 int mmi_lm_set_exec_mask(mmi_lm* lm, const uint8_t* mask, mmi_stream stream);        /* lm.py:544-547 */
 int mmi_lm_reset(mmi_lm* lm, const uint8_t* mask_or_null, mmi_stream stream);        /* lm.py:537-542 */
+/* Fork session `src` into the sessions dst[0 .. n_dst) of the same stream (dst: a host array): a parked template session copied
+ * at admission instead of a prefill per caller, or N candidates continued from one conversation state.  No reference
+ * counterpart: the nearest is get_streaming_state / set_streaming_state on a batch of one (streaming.py:158-181).
+ * Stream-ordered: no host synchronisation and no device read-back; only the valid rows of the source's KV ring are moved (their
+ * number is read on the device).  After the call each destination is the session `src` is: offset, delay ring, last tokens,
+ * text history, sampling entry (a seeded draw stream continues with the same draws: set another mmi_row_sampling afterwards for
+ * different candidates), top_p, condition rows and guidance coefficient, cross-attention source and length, TTS script position,
+ * adapter slot; on a guided stream the twin model rows follow.  A destination's previous state is gone as after mmi_lm_reset,
+ * its exec bit is 1 whatever the source's is, and its rows of the log-probability rings are cleared as mmi_lm_reset clears
+ * them.  The handle-wide RNG counter, the host step counter and the ring-depth bound stay as they are.  Works on every handle
+ * mmi_lm_step works on.  MMI_ERR_STATE when not streaming; MMI_ERR_INVALID for src or a dst outside [0, batch), dst == src, a
+ * repeated dst, n_dst outside [1, 16]; a refused call changes nothing. */
+int mmi_lm_fork_session(mmi_lm* lm, int32_t src, const int32_t* dst, int32_t n_dst, mmi_stream stream);
 
 /* Per-session sampling settings (no counterpart in the reference's Python LMGen; its Rust server takes them from each
  * connection's query string, rust/moshi-backend/src/stream_both.rs:95-105, and applies them to that session alone,
@@ -986,6 +1007,14 @@ int mmi_batcher_open_lora(mmi_batcher* b, const mmi_row_sampling* settings_or_nu
  * with mmi_lm_enable_nucleus before mmi_batcher_create); the row returns to the handle's values at the step after the close, as an
  * adapter slot does.  What mmi_lm_set_row_top_p would refuse is refused here with the same status. */
 int mmi_batcher_set_channel_top_p(mmi_batcher* b, int64_t channel_id, float top_p, float top_p_text);
+/* A new channel that continues from `parent_channel`'s state (no reference counterpart: batched_asr.rs opens every slot fresh;
+ * the nearest is get_streaming_state / set_streaming_state on a batch of one, streaming.py:158-181).  Claims a free slot
+ * (MMI_ERR_BUSY: none; MMI_ERR_NO_CHANNEL: unknown parent; MMI_ERR_STATE: the parent was opened since the last step and has no
+ * state yet) and runs mmi_mimi_fork_session and mmi_lm_fork_session on the batcher's stream, behind the last step and in front
+ * of the next.  The child takes the parent's bookkeeping (own sampling, condition, adapter, top_p, frame counter), starts with
+ * empty input and output FIFOs and is not reset at its first step; settings_or_null != NULL: its row then gets those settings
+ * (mmi_lm_set_row_sampling) - a seed of its own makes it a different candidate.  Closing the parent later leaves the child. */
+int mmi_batcher_fork(mmi_batcher* b, int64_t parent_channel, const mmi_row_sampling* settings_or_null, int64_t* channel_id);
 int mmi_batcher_close(mmi_batcher* b, int64_t channel_id);
 /* Append 24 kHz mono PCM (host f32) to the channel's FIFO (batched_asr.rs:77-90 extend_data). */
 int mmi_batcher_push_pcm(mmi_batcher* b, int64_t channel_id, const float* pcm, int32_t n_samples);

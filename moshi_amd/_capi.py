@@ -247,6 +247,9 @@ SIGNATURES = {
     "mmi_lm_debug_step_logprob": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     "mmi_batcher_pop_logprobs": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(C.c_int32)]),
     "mmi_lm_debug_state_regions": (C.c_int64, [_P, _P, C.c_int64]),
+    "mmi_lm_fork_session": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _P]),
+    "mmi_mimi_fork_session": (C.c_int, [_P, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _P]),
+    "mmi_batcher_fork": (C.c_int, [_P, C.c_int64, C.POINTER(RowSampling), C.POINTER(C.c_int64)]),
     "mmi_lm_launch_list": (C.c_int64, [_P, _P, C.c_int64]),
     "mmi_mimi_launch_list": (C.c_int64, [_P, C.c_int32, _P, C.c_int64]),
     "mmi_lm_seek": (C.c_int, [_P, _P, _P]),
@@ -273,10 +276,12 @@ _SINCE_PREFILL = ("mmi_lm_enable_prefill", "mmi_lm_prefill_rows", "mmi_lm_prefil
 _SINCE_SCORE = ("mmi_lm_enable_score", "mmi_lm_score_enabled", "mmi_lm_score", "mmi_lm_debug_score_rows")
 _SINCE_LOGPROBS = ("mmi_lm_enable_logprobs", "mmi_lm_logprobs_enabled", "mmi_lm_last_logprobs", "mmi_lm_frame_logprobs",
                    "mmi_lm_debug_step_logprob", "mmi_batcher_pop_logprobs")
+_SINCE_FORK = ("mmi_lm_fork_session", "mmi_mimi_fork_session", "mmi_batcher_fork")
 
 
 def _missing(name, path):
-    what = ("log-probabilities in the step" if name in _SINCE_LOGPROBS else
+    what = ("forking a session" if name in _SINCE_FORK else
+            "log-probabilities in the step" if name in _SINCE_LOGPROBS else
             "teacher-forced scoring" if name in _SINCE_SCORE else
             "chunked prefill" if name in _SINCE_PREFILL else
             "the attention tap" if name in _SINCE_ATTN_TAP else
@@ -299,7 +304,7 @@ class Lib:
         self.path = Path(path)
         self.cdll = C.CDLL(str(self.path))
         for name, (res, args) in SIGNATURES.items():
-            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION + _SINCE_TTS_MACHINE + _SINCE_MANY_ROWS + _SINCE_ADAPTERS + _SINCE_NUCLEUS + _SINCE_KV4 + _SINCE_ATTN_TAP + _SINCE_PREFILL + _SINCE_SCORE + _SINCE_LOGPROBS and not hasattr(self.cdll, name):
+            if name in _SINCE_ROW_SAMPLING + _SINCE_ROW_CONDITION + _SINCE_TTS_MACHINE + _SINCE_MANY_ROWS + _SINCE_ADAPTERS + _SINCE_NUCLEUS + _SINCE_KV4 + _SINCE_ATTN_TAP + _SINCE_PREFILL + _SINCE_SCORE + _SINCE_LOGPROBS + _SINCE_FORK and not hasattr(self.cdll, name):
                 # an older build of the engine (MMI_LIB_PATH, A/B runs against a parent build): everything else works, these refuse
                 setattr(self, name, _missing(name, self.path))
                 continue

@@ -171,6 +171,29 @@ class SessionBatcher:
                 raise
         return int(ch.value)
 
+    def fork(self, channel: int, sampling=None) -> int:
+        """A new channel that continues from `channel`'s state: both engines' sessions are copied into a free slot on the batcher's
+        stream (`LMGen.fork_session`, `MimiModel.fork_session`), between two steps.  The child takes the parent's settings,
+        condition, adapter and frame count and starts with empty FIFOs; `sampling`: a `moshi_amd.SessionSampling` of its own - with
+        another seed it is another candidate from the same conversation (N-best), without one it repeats the parent under greedy
+        or a seeded parent.  Closing the parent leaves the child.  Raises BufferError without a free slot, `UnknownChannel` for an
+        unknown parent, RuntimeError for a parent that has not run a step since `open`."""
+        own_p = sampling is not None and (sampling.top_p > 0 or sampling.top_p_text > 0)
+        if sampling is not None:
+            check_top_p(sampling.top_p, sampling.top_p_text)
+        if own_p and not self._nucleus:
+            raise RuntimeError("SessionSampling.top_p > 0 needs a batcher with the nucleus samplers: SessionBatcher(session_top_p=True)")
+        ch = C.c_int64(0)
+        sp = C.byref(sampling.to_c()) if sampling is not None else None
+        self._lib.check(self._lib.mmi_batcher_fork(self._handle, int(channel), sp, C.byref(ch)))
+        if sampling is not None and self._nucleus:
+            try:
+                self.set_channel_top_p(int(ch.value), sampling.top_p, sampling.top_p_text)
+            except BaseException:
+                self._lib.mmi_batcher_close(self._handle, int(ch.value))
+                raise
+        return int(ch.value)
+
     def set_channel_top_p(self, channel: int, top_p: float, top_p_text: float) -> None:
         """The channel samples with its own nucleus values from the next step on, for its life; `close` returns the row to the
         batcher's values at the following step."""

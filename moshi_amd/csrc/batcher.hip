@@ -109,6 +109,7 @@ struct mmi_batcher {
     int64_t* d_codes = nullptr;   // [B][K][1] user codes from the encoder
     int64_t* d_dec_codes = nullptr;
     std::mutex mu;                // guards channels / stats (batched_asr.rs:438 Channels = Arc<Mutex<..>>)
+    std::mutex step_mu;           // held by a whole step and by a fork (taken before `mu`): their launches never interleave
     std::vector<Channel> channels;
     std::vector<int64_t> row_owner;   // channel id that owned each row when the current step started
     std::vector<uint8_t> m_set, m_clear;      // rows opened since the last step: with / without settings of their own
@@ -360,6 +361,51 @@ extern "C" int mmi_batcher_open_lora(mmi_batcher* b, const mmi_row_sampling* set
     return mmi_fail(MMI_ERR_BUSY, "no free slot");   // py_module.rs:443-470: `channels()` yields None
 }
 
+// A live channel duplicated into a free slot.  No reference counterpart: batched_asr.rs opens a slot fresh; the
+// nearest is get_streaming_state / set_streaming_state on a batch of one (streaming.py:158-181).  Both engine forks run on the
+// batcher's stream, so they are ordered behind the last step and in front of the next one.
+extern "C" int mmi_batcher_fork(mmi_batcher* b, int64_t parent_channel, const mmi_row_sampling* settings, int64_t* channel_id) {
+    MmiDeviceGuard dev_guard_(b ? mmi_lm_device(b->lm) : -1);
+    if (!b || !channel_id) return mmi_fail(MMI_ERR_INVALID, "null argument");
+    int rc;
+    if (settings && (rc = mmi_row_sampling_check(settings))) return rc;
+    std::lock_guard<std::mutex> step_guard(b->step_mu);
+    std::lock_guard<std::mutex> g(b->mu);
+    Channel* parent = find_channel(b, parent_channel);
+    if (!parent) return mmi_fail(MMI_ERR_NO_CHANNEL, "unknown channel");
+    if (parent->pending_reset) return mmi_fail(MMI_ERR_STATE, "mmi_batcher_fork: the parent was opened since the last step: it has no state yet");
+    const int src = (int)(parent - b->channels.data());
+    int32_t dst = -1;
+    for (int r = 0; r < b->B && dst < 0; ++r)
+        if (!b->channels[r].live) dst = r;
+    if (dst < 0) return mmi_fail(MMI_ERR_BUSY, "no free slot");
+    if ((rc = mmi_mimi_fork_session(b->mimi, src, &dst, 1, b->stream))) return rc;
+    if ((rc = mmi_lm_fork_session(b->lm, src, &dst, 1, b->stream))) return rc;
+    if (settings) {
+        std::vector<uint8_t> mask((size_t)b->B, 0);
+        std::vector<mmi_row_sampling> rows((size_t)b->B, *settings);
+        mask[dst] = 1;
+        if ((rc = mmi_lm_set_row_sampling(b->lm, mask.data(), rows.data(), b->stream))) return rc;
+    }
+    Channel& c = b->channels[dst];
+    c = Channel();
+    c.live = true;
+    c.own_sampling = settings ? true : parent->own_sampling;
+    c.sampling = settings ? *settings : parent->sampling;
+    c.own_cond = parent->own_cond; c.coef = parent->coef; c.cross_len = parent->cross_len;
+    c.adapter = parent->adapter;
+    c.own_top_p = parent->own_top_p; c.top_p_dirty = parent->top_p_dirty; c.top_p = parent->top_p; c.top_p_text = parent->top_p_text;
+    c.frames = parent->frames;
+    // the rows' mirrors follow the engine: the child's rows hold what the parent's hold
+    b->row_has_cond[dst] = b->row_has_cond[src];
+    b->row_adapter[dst] = b->row_adapter[src];
+    b->row_has_top_p[dst] = b->row_has_top_p[src];
+    c.id = b->next_id++;
+    *channel_id = c.id;
+    b->stats.used_slots += 1;
+    return MMI_OK;
+}
+
 int32_t mmi_lm_nucleus_enabled(const mmi_lm* lm);
 
 extern "C" int mmi_batcher_set_channel_top_p(mmi_batcher* b, int64_t channel_id, float top_p, float top_p_text) {
@@ -404,6 +450,7 @@ extern "C" int mmi_batcher_push_pcm(mmi_batcher* b, int64_t channel_id, const fl
 extern "C" int mmi_batcher_step(mmi_batcher* b, int32_t* n_active) {
     MmiDeviceGuard dev_guard_(b ? mmi_lm_device(b->lm) : -1);
     if (!b) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    std::lock_guard<std::mutex> step_guard(b->step_mu);
     const int B = b->B, F = b->F;
     Staging& h = b->host;
     Staging& d = b->dev;

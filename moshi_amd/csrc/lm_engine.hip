@@ -6,6 +6,7 @@
 #include "lm_prefill_kernels.h"
 #include "lm_score_kernels.h"
 #include "lm_logprob_kernels.h"
+#include "mmi_fork_kernels.h"
 #include "mmi_graph.h"
 
 #include <math.h>
@@ -2911,6 +2912,71 @@ extern "C" int mmi_lm_reset(mmi_lm* lm, const uint8_t* mask, mmi_stream stream) 
     const int rc = clear_logprobs(lm, (hipStream_t)stream, mask);
     if (rc) return rc;
     lm->offset_cpu = 0;   // lm.py:540: any reset, even partial, zeroes the host-side step counter
+    return MMI_OK;
+}
+
+// ---- forking a session ---------------------------------------------------------------------------------------
+// No reference counterpart (the nearest: get_streaming_state / set_streaming_state on a batch of one, streaming.py:158-181).
+// Stream-ordered: two launches (the ring, the per-session rows) and the clearing of the destinations' log-probability rings; the
+// ring's valid length is read on the device, its grid sized by depth_bound.  What a session is comes from state_table(): every
+// entry with per-session slices except the ring (k_fork_ring) and `exec` (set to 1), plus the per-layer slices of `xkv` and the
+// nucleus tail behind `rowtab`.
+extern "C" int mmi_lm_fork_session(mmi_lm* lm, int32_t src, const int32_t* dst, int32_t n_dst, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(lm ? lm->device : -1);
+    if (!lm) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (!lm->streaming) return mmi_fail(MMI_ERR_STATE, "not streaming");
+    const int G = lm->gen_batch, B = lm->batch;
+    ForkSessions fs;
+    int rc = mmi_fork_sessions("mmi_lm_fork_session", G, src, dst, n_dst, &fs);
+    if (rc) return rc;
+    fs.n_rows = B > G ? 2 : 1;
+    fs.twin = G;
+    hipStream_t s = (hipStream_t)stream;
+    const mmi_lm_cfg& c = lm->cfg;
+    const KvRing& ring = lm->ring;
+    const int H = c.num_heads, Dh = c.dim / H;
+    ForkRingArgs ra;
+    memset(&ra, 0, sizeof(ra));
+    ra.base[0] = reinterpret_cast<uint8_t*>(lm->kc); ra.base[1] = reinterpret_cast<uint8_t*>(lm->vc);
+    ra.n_base = 2; ra.layers = c.num_layers; ra.layer_stride = (long)(ring.layer_u16 * sizeof(uint16_t));
+    ra.n_planes = ring.form == 2 ? 2 : 1;
+    ra.pos_bytes[0] = ring.form == 2 ? Dh / 2 : (ring.form == 1 ? Dh : 2 * Dh);
+    ra.plane_off[1] = (long)ring.scale_off; ra.pos_bytes[1] = Dh / 16;
+    ra.H = H; ra.cap = c.context; ra.s = fs;
+    ra.len = lm->offsets;       // (not offsets_m: on a guided stream that is the last step's copy, one behind after the commit)
+    for (int p = 0; p < ra.n_planes; ++p)
+        ra.vec[p] = ((size_t)ra.layer_stride | (size_t)ra.plane_off[p] | ((size_t)ra.cap * ra.pos_bytes[p])) % 16 == 0 ? 1 : 0;
+    ForkRowArgs rows;
+    memset(&rows, 0, sizeof(rows));
+    rows.exec = lm->exec; rows.s = fs;
+    bool full = false;
+    for (const BufDecl& e : lm->st_table) {
+        const bool is_ring = e.slot == (void**)&lm->kc || e.slot == (void**)&lm->vc;
+        if (e.slot == (void**)&lm->xkv) {         // [layers][B][cross_cap][2 * dim]: a slice per layer and model row
+            const size_t slice = (size_t)lm->cross_cap * 2 * c.dim * e.elem;
+            full = full || !mmi_fork_add(rows, *e.slot, c.num_layers, (size_t)B * slice, slice, slice, true);
+        }
+        if (e.rows <= 0 || is_ring || e.slot == (void**)&lm->exec) continue;
+        const size_t slice = e.count * e.elem / (size_t)e.rows;
+        full = full || !mmi_fork_add(rows, *e.slot, 1, 0, slice, slice, e.rows == B && B > G);
+        if (e.tail && e.slot == (void**)&lm->rowtab)      // the sessions' nucleus values behind the row table
+            full = full || !mmi_fork_add(rows, lm->rowtab + G, 1, 0, sizeof(RowTopP), sizeof(RowTopP), false);
+    }
+    if (full) return mmi_fail(MMI_ERR_UNSUPPORTED, "mmi_lm_fork_session: the state table outgrew the descriptor list");
+    // depth_bound bounds the sessions' offsets - except on a guided stream restored from a snapshot: mmi_lm_state_load takes it from
+    // offsets_m, which is one behind offsets there (k_lm_cfg_twins writes it at the head of a step), and every later step keeps
+    // that distance.  One more position covers it; the valid length itself is read on the device
+    if ((rc = mmi_launch_fork_ring(s, ra, lm->depth_bound + (B > G ? 1 : 0)))) return rc;
+    if ((rc = mmi_launch_fork_rows(s, rows))) return rc;
+    uint8_t sess[MMI_FORK_MAX_DST];
+    for (int i = 0; i < n_dst; ++i) sess[i] = (uint8_t)dst[i];
+    if ((rc = clear_logprobs(lm, s, nullptr, sess, n_dst))) return rc;
+    // the host's mirrors of per-session device values (the ones mmi_lm_state_load refreshes)
+    for (int i = 0; i < n_dst; ++i) {
+        lm->row_active[dst[i]] = lm->row_active[src];
+        if (lm->nucleus_live) lm->row_top_p[dst[i]] = lm->row_top_p[src];
+        if (lm->row_slot) lm->row_slot_h[dst[i]] = lm->row_slot_h[src];
+    }
     return MMI_OK;
 }
 

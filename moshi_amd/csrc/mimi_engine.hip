@@ -2,6 +2,7 @@
 // (reference: moshi/moshi/models/compression.py:338-433) as a fixed per-frame launch list over the kernels
 // of mimi_kernels.h, captured into one hipGraph per direction.
 #include "mimi_kernels.h"
+#include "mmi_fork_kernels.h"
 #include "mmi_graph.h"
 
 #include <math.h>
@@ -78,6 +79,7 @@ struct mmi_mimi {
     HistDesc* enc_hist = nullptr;
     HistDesc* dec_hist = nullptr;
     int enc_nhist = 0, dec_nhist = 0, enc_hist_rows = 0, dec_hist_rows = 0;
+    std::vector<HistDesc> hist_h;              // the host's copy of both tables (mmi_mimi_fork_session builds its descriptors from it)
     MmiProgram enc_prog, dec_prog;
     hipStream_t cap_stream = nullptr;
     bool use_graph = true;
@@ -742,6 +744,7 @@ int upload_hist(mmi_mimi* m, std::vector<HistDesc>& h, int B, HistDesc** dev, in
     }
     *n = (int)keep.size();
     *rows = acc;
+    m->hist_h.insert(m->hist_h.end(), keep.begin(), keep.end());
     if (tab) {                                   // by-value copy for k_commit_all (n = -1: too many descriptors, two-launch path)
         memset(tab, 0, sizeof(*tab));
         tab->n = keep.size() <= MMI_HIST_MAX ? (int)keep.size() : -1;
@@ -1193,6 +1196,7 @@ extern "C" int mmi_mimi_streaming_stop(mmi_mimi* m) {
     m->st.release();
     m->partials.clear();
     m->partial_sizes.clear();
+    m->hist_h.clear();
     m->streaming = false;
     m->batch = 0;
     return MMI_OK;
@@ -1244,6 +1248,57 @@ extern "C" int mmi_mimi_reset(mmi_mimi* m, const uint8_t* mask, mmi_stream strea
         MMI_LAUNCH(k_reset_rows_f32, (int)mmi_cdiv64((int64_t)B * m->partial_sizes[i], 256), 256, 0, s, m->partials[i], m->partial_sizes[i], B, mask);
     MMI_LAUNCH(k_reset_counters, mmi_cdiv(B, 64), 64, 0, s, m->counters, 2, m->first, m->exec, B, mask);
     MMI_CHECK_LAUNCH();
+    return MMI_OK;
+}
+
+// Forking a session (no reference counterpart - the nearest: get_streaming_state / set_streaming_state on a batch
+// of one, streaming.py:158-181): what mmi_mimi_reset clears - the history columns of every conv, the overlap-add partials, both
+// counters, the `first` flag - copied from `src`, plus the valid prefix of both transformer rings.  Stream-ordered.
+extern "C" int mmi_mimi_fork_session(mmi_mimi* m, int32_t src, const int32_t* dst, int32_t n_dst, mmi_stream stream) {
+    MmiDeviceGuard dev_guard_(m ? m->device : -1);
+    if (!m) return mmi_fail(MMI_ERR_INVALID, "null handle");
+    if (!m->streaming) return mmi_fail(MMI_ERR_STATE, "not streaming");
+    ForkSessions fs;
+    int rc = mmi_fork_sessions("mmi_mimi_fork_session", m->batch, src, dst, n_dst, &fs);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const mmi_mimi_cfg& c = m->cfg;
+    const int B = m->batch, H = c.tr_num_heads, Dh = c.tr_d_model / (H > 0 ? H : 1);
+    float* kv[2] = {m->enc_kv, m->dec_kv};
+    for (int w = 0; w < 2; ++w) {               // [2 * layer][B][H][cap][Dh] fp32; the valid length is the transformer's counter
+        if (!kv[w]) continue;
+        ForkRingArgs ra;
+        memset(&ra, 0, sizeof(ra));
+        ra.base[0] = reinterpret_cast<uint8_t*>(kv[w]);
+        ra.n_base = 1; ra.layers = 2 * c.tr_num_layers; ra.n_planes = 1;
+        ra.pos_bytes[0] = Dh * (int)sizeof(float);
+        ra.H = H; ra.cap = c.tr_context;
+        ra.layer_stride = (long)B * H * ra.cap * ra.pos_bytes[0];
+        ra.vec[0] = ((size_t)ra.cap * ra.pos_bytes[0]) % 16 == 0 ? 1 : 0;
+        ra.len = m->counters + (size_t)w * B; ra.s = fs;
+        if ((rc = mmi_launch_fork_ring(s, ra, ra.cap))) return rc;
+    }
+    const size_t total = m->hist_h.size() + m->partials.size() + 2;
+    size_t done = 0;
+    while (done < total) {                      // one launch, unless the lists outgrow the descriptors of one
+        ForkRowArgs rows;
+        memset(&rows, 0, sizeof(rows));
+        rows.exec = m->exec; rows.s = fs;
+        for (; done < total && rows.n < MMI_FORK_MAX_ENT; ++done) {
+            if (done < m->hist_h.size()) {
+                const HistDesc& h = m->hist_h[done];
+                mmi_fork_add(rows, h.p, h.C, (size_t)h.ld * sizeof(float), (size_t)h.C * h.ld * sizeof(float), (size_t)h.H * sizeof(float), false);
+            } else if (done < m->hist_h.size() + m->partials.size()) {
+                const size_t i = done - m->hist_h.size(), nb = (size_t)m->partial_sizes[i] * sizeof(float);
+                if (nb) mmi_fork_add(rows, m->partials[i], 1, 0, nb, nb, false);
+            } else if (done + 2 == total) {
+                mmi_fork_add(rows, m->counters, 2, (size_t)B * sizeof(long), sizeof(long), sizeof(long), false);
+            } else {
+                mmi_fork_add(rows, m->first, 1, 0, 1, 1, false);
+            }
+        }
+        if (rows.n && (rc = mmi_launch_fork_rows(s, rows))) return rc;
+    }
     return MMI_OK;
 }
 

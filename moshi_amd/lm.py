@@ -903,6 +903,21 @@ class LMGen:
         keep, ptr = self._mask_ptr(reset_mask)
         self._lib.check(self._lib.mmi_lm_reset(self.lm_model._handle, ptr, self._stream()))
 
+    # ---- forking a session (mmi_lm_fork_session) ---------------------------------------------------
+    def fork_session(self, src: int, dst) -> None:
+        """Sessions `dst` (an int or a sequence of at most 16) become copies of session `src`: offset, KV ring, delay ring, last
+        tokens, text history, sampling entry, top_p, condition and guidance coefficient, cross-attention source, TTS script
+        position and adapter slot; what they held is gone as after `reset_streaming`, their exec bit is 1 whatever the source's
+        is (a template parked under the exec mask stays parked), and their `last_logprobs()` read NaN / -1 until their next step.
+        Stream-ordered, no host synchronisation; only the valid rows of the source's ring are moved.  A seeded `SessionSampling`
+        continues with the same draws in the copy: set another afterwards for a different candidate.  No reference counterpart
+        (the nearest: `get_streaming_state` / `set_streaming_state` on a batch of one).  With a `DuplexStream` call it after
+        `join()`: the LM's own stream must have passed the last submitted frame."""
+        assert self.is_streaming
+        d = [int(dst)] if isinstance(dst, int) else [int(v) for v in dst]
+        arr = (C.c_int32 * max(len(d), 1))(*d)
+        self._lib.check(self._lib.mmi_lm_fork_session(self.lm_model._handle, int(src), arr, len(d), self._stream()))
+
     # ---- per-session sampling (mmi_lm_set_row_sampling) --------------------------------------------
     def _host_mask(self, mask):
         if mask is None:

@@ -175,6 +175,16 @@ class MimiModel:
         keep, ptr = self._mask_arg(reset_mask)
         self._lib.check(self._lib.mmi_mimi_reset(self._handle, ptr, self._stream()))
 
+    def fork_session(self, src: int, dst) -> None:
+        """Sessions `dst` (an int or a sequence of at most 16) become copies of session `src`: conv histories, overlap-add
+        partials, transformer offsets and the valid rows of both KV rings.  What they held is gone as after `reset_streaming`;
+        their exec bit is 1.  Stream-ordered, no host synchronisation.  No reference counterpart (the nearest:
+        `get_streaming_state` / `set_streaming_state` on a batch of one).  With a `DuplexStream` call it after `join()`."""
+        assert self.is_streaming
+        d = [int(dst)] if isinstance(dst, int) else [int(v) for v in dst]
+        arr = (C.c_int32 * max(len(d), 1))(*d)
+        self._lib.check(self._lib.mmi_mimi_fork_session(self._handle, int(src), arr, len(d), self._stream()))
+
     def set_streaming_detached(self, streaming_detached: bool) -> None:
         """streaming.py:78-86: keeps a parent module's `.streaming()` from reaching this one.  An engine handle has no parent and
         enters streaming mode only through its own `streaming()` / `streaming_forever()`: always detached; the flag is kept."""
